@@ -17,11 +17,16 @@ the setup (all-reduce(MIN) of the election keys + all-gather of the elected rows
 reported as `pivot_row_exchange_rank0`; SPASM_BENCH_EXCHANGE=0 replicates the matrix instead, explicitly); the timed
 region has no data-path collective.  A failing exchange ends the run with a non-zero exit code.
 
-Prints ONE JSON line on rank 0.  `roofline` describes the dominant kernel (the scatter launch of
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, the round's counters); everything else is measured only with `--full`:
+`roofline` describes the dominant kernel (the scatter launch of
 the busiest hash-table class): algorithmic bytes per launch over its HIP-event duration on the
-launch stream; `roofline.valu` holds the same launch against the ceiling it actually runs into (wave64 VALU issue: DESIGN.md section 8).
-`cpu_baseline` times the CPU oracle (oracle/liboracle.so, OpenMP) on a bounded
-sample of the same round, on rank 0 at N = 1 only.
+launch stream, from one extra step with an event pair around every class; `roofline.valu` holds the same launch against the ceiling it
+actually runs into (wave64 VALU issue: DESIGN.md section 8).  `echelonize_round0` (N = 1) times the same step inside a real
+spasm_echelonize.  `cpu_baseline` times the CPU oracle (oracle/liboracle.so, OpenMP) on a bounded
+sample of the same round, on rank 0 at N = 1 only (`--no-cpu-baseline` leaves it out).
+`--dump-outputs DIR` writes what the last timed step computed -- the Schur complement as spasm_amd_schur_plan_fetch hands it to a
+caller -- as DIR/*.npy (see dump_outputs), so that two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -29,6 +34,8 @@ import json
 import os
 import sys
 import time
+
+import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -51,8 +58,12 @@ def main():
     ap.add_argument("--n", type=int, default=int(os.environ.get("SPASM_BENCH_N", 1_000_000)), help="rows = columns of the synthetic matrix")
     ap.add_argument("--row-nnz", type=int, default=20)
     ap.add_argument("--prime", type=int, default=65521)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline of the dominant kernel (one extra profiled step), echelonize_round0 and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target duration of the CPU baseline sample (--full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the Schur complement of the last timed step (a seeded sample of it) as DIR/*.npy")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -119,7 +130,8 @@ def main():
         # (an exchange that fails is fatal: a run that silently replicated the matrix instead would not measure config 4)
         engine = sharded.GpuShardEngine(A, lo, hi, stride=stride)
         xt = []
-        for rep in range(3):  # the exchange alone, timed: all-reduce(MIN) of the keys + all-gather of the rows + import (U, Uinv, W build)
+        # the exchange alone, timed: all-reduce(MIN) of the keys + all-gather of the rows + import (U, Uinv, W build); repeated with --full
+        for rep in range(3 if args.full else 1):
             if rep:
                 engine.close()
                 engine = sharded.GpuShardEngine(A, lo, hi, stride=stride)
@@ -167,14 +179,22 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # one more step, outside the timed region, with an event pair around every scatter class (roofline of the dominant kernel)
-    lib.spasm_amd_schur_plan_class_timing(plan, 1)
-    step()
-    torch.cuda.synchronize()
-    st = S._abi.RoundStats()
-    if lib.spasm_amd_schur_plan_stats(plan, C.byref(st)) != 0:
-        raise SystemExit("plan_stats failed: " + S._abi.last_error())
-    d = st.as_dict()
+    def stats():
+        st = S._abi.RoundStats()
+        if lib.spasm_amd_schur_plan_stats(plan, C.byref(st)) != 0:
+            raise SystemExit("plan_stats failed: " + S._abi.last_error())
+        return st.as_dict()
+
+    d = stats()  # the counters of the last timed step
+    if args.dump_outputs:
+        dump_outputs(lib, S, plan, my_rows, d, args.dump_outputs, prefix=f"rank{rank}_" if world > 1 else "",
+                     budget=(64 << 20) // world)
+    if args.full:
+        # one more step, outside the timed region, with an event pair around every scatter class (roofline of the dominant kernel)
+        lib.spasm_amd_schur_plan_class_timing(plan, 1)
+        step()
+        torch.cuda.synchronize()
+        d = stats()
     counters = torch.tensor([d["nnz_reduced"], d["applications"], d["nnz_out"], d["read_bytes"], my_rows], dtype=torch.int64, device=cdev)
     if world > 1:
         dist.all_reduce(counters, op=dist.ReduceOp.SUM)
@@ -183,7 +203,7 @@ def main():
     ms_per_step = 1e3 * elapsed / max(args.steps, 1)
     value = nnz_reduced * args.steps / elapsed
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # dominant kernel: the scatter launch of the busiest class (HIP events on the launch stream, last step)
         cls = max(range(16), key=lambda c: d["ms_class"][c])
         k_bytes = 8 * d["ent_class"][cls] + 16 * d["seg_class"][cls]
@@ -217,7 +237,7 @@ def main():
                 pass
         # the same kernel against the OTHER ceiling it runs into: a CU retires one wave64 VALU instruction per clock (four 16-lane
         # SIMDs, four clocks each).  SQ_INSTS_VALU per launch from the committed PMC pass (profiles/*_instruction_mix.txt, a separate
-        # run as the guide prescribes), over the live duration of this run; only for the workload it was measured on.
+        # run), over the live duration of this run; only for the workload it was measured on.
         valu = None
         if world == 1 and n == 1_000_000 and args.row_nnz == 20 and args.prime == 65521 and prefix and not fused and k_ms > 0:
             try:
@@ -288,6 +308,7 @@ def main():
                                              "fetch_over_algorithmic_read": round(fetch / d["read_bytes"], 3) if d["read_bytes"] else None}
             except Exception:
                 pass
+    if rank == 0:
         out = {
             "metric": "Schur nnz reduced/sec (GF(p) echelonize), 1Mx1M CSR",
             "value": value,
@@ -311,10 +332,11 @@ def main():
                 "parallelism": (f"rows r, r+{world}, ... on rank r (x{world}), pivot rows exchanged by all-reduce(MIN)+all-gather" if world > 1 else "single GPU")
                 + (" -- REHEARSAL: all ranks on one GPU over gloo, timings meaningless" if rehearse else ""),
             },
-            "roofline": roofline,
             "setup_s": {"generate": round(t_gen, 2), "upload_elect_buildU": round(t_setup, 2)},
         }
-        if world == 1:
+        if args.full:
+            out["roofline"] = roofline
+        if world == 1 and args.full:
             # the same Schur step inside a real spasm_echelonize (src/SpaSM.jl:863): one sparse round, leftmost pivots as in the plan,
             # no finish (enable_dense = enable_GPLU = 0: "Cannot finish", U = the round's pivot rows).  Device time of the W build, of
             # the plan of the rows (with the host synchronisation that reads the total of the bounds) and of the scatter, from the
@@ -334,7 +356,7 @@ def main():
                 out["echelonize_round0"] = {"error": repr(exc)}
         if exchange is not None:
             out["pivot_row_exchange_rank0"] = exchange
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(A, args.cpu_seconds)
         print(json.dumps(out), flush=True)
 
@@ -344,6 +366,72 @@ def main():
         lib.spasm_amd_schur_plan_free(plan)
     if world > 1:
         dist.destroy_process_group()
+
+
+def _exact_float(a):
+    """float32 when every value of the integer array `a` is exact in it, float64 otherwise."""
+    a = np.asarray(a, dtype=np.int64)
+    return a.astype(np.float32 if a.size == 0 or int(np.abs(a).max()) < (1 << 24) else np.float64)
+
+
+def dump_outputs(lib, S, plan, plan_rows, d, dirname, prefix="", budget=64 << 20, sample_rows=4096):
+    """What the last timed step computed, as a caller receives it: the Schur complement of the plan's rows
+    (spasm_amd_schur_plan_fetch: CSR of balanced residues + the originating row of A of every output row).  Written as .npy,
+    rows in the order of their originating row:
+      schur_round_counters  npiv, nnz_reduced, applications, nnz_out, rows_out of the step (float64)
+      schur_row_origin      originating row of A of every Schur row
+      schur_row_nnz         entries of every Schur row
+      schur_row_value_sum   sum of the balanced values of every Schur row (float64, exact)
+      schur_sample_rows / _indptr / _cols / _vals   a fixed, seeded sample of whole rows (positions into the arrays above),
+                            entries sorted by column: the scatter leaves the order inside a row unspecified
+    Integer data are stored as float32 where exact, float64 otherwise; all files together stay within `budget` bytes (the sample
+    is cut short when they would not)."""
+    os.makedirs(dirname, exist_ok=True)
+    orig = np.zeros(max(plan_rows, 1), dtype=np.int32)  # at most one Schur row per row of the plan
+    ptr = lib.spasm_amd_schur_plan_fetch(plan, orig.ctypes.data_as(C.POINTER(C.c_int32)))
+    if not ptr:
+        raise SystemExit("plan_fetch failed: " + S._abi.last_error())
+    Sc = S.CSR(ptr)
+    n = Sc.n
+    assert n <= plan_rows, (n, plan_rows)
+    p = Sc.p.astype(np.int64)
+    nnz = int(p[n])
+    j, x = Sc.j[:nnz], Sc.x[:nnz]
+    order = np.argsort(orig[:n], kind="stable")
+    lens = np.diff(p)
+    sums = np.zeros(n, np.int64)
+    full = lens > 0  # reduceat over the starts of the non-empty rows: each segment then ends where the next one starts
+    if full.any():
+        sums[full] = np.add.reduceat(x, p[:-1][full], dtype=np.int64)
+
+    arrays = {
+        "schur_round_counters": np.array([d["npiv"], d["nnz_reduced"], d["applications"], d["nnz_out"], d["rows_out"]], np.float64),
+        "schur_row_origin": _exact_float(orig[:n][order]),
+        "schur_row_nnz": _exact_float(lens[order]),
+        "schur_row_value_sum": sums[order].astype(np.float64),
+    }
+    left = budget - sum(a.nbytes for a in arrays.values()) - 4 * 8 * (sample_rows + 1)
+    pick = np.sort(np.random.default_rng(0x5A5A0003).choice(n, size=min(n, sample_rows), replace=False)) if n else np.zeros(0, np.int64)
+    cols, vals, indptr = [], [], [0]
+    wide = 8 if (Sc.m >= (1 << 24) or Sc.prime >= (1 << 25)) else 4  # bytes per stored column / value
+    for r in pick:
+        lo, hi = int(p[order[r]]), int(p[order[r] + 1])
+        if 2 * wide * (indptr[-1] + hi - lo) > left:
+            pick = pick[: len(indptr) - 1]
+            break
+        k = np.argsort(j[lo:hi], kind="stable")
+        cols.append(j[lo:hi][k])
+        vals.append(x[lo:hi][k])
+        indptr.append(indptr[-1] + hi - lo)
+    ftype = np.float64 if wide == 8 else np.float32
+    arrays["schur_sample_rows"] = pick.astype(np.float64)
+    arrays["schur_sample_indptr"] = np.array(indptr, np.float64)
+    arrays["schur_sample_cols"] = (np.concatenate(cols) if cols else np.zeros(0)).astype(ftype)
+    arrays["schur_sample_vals"] = (np.concatenate(vals) if vals else np.zeros(0)).astype(ftype)
+    assert sum(a.nbytes for a in arrays.values()) <= budget
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, prefix + name + ".npy"), a)
+    del Sc
 
 
 def cpu_baseline(A, target_seconds):

@@ -1,5 +1,5 @@
 """print the mean per-dispatch PMC values of tools/pmc_insts.sh for kernels matching a prefix:
-   python tools/pmc_show.py gpurun_out/pmc_<tag> 'k_scatter<11' [rows]"""
+   python tools/pmc_show.py profile_out/pmc_<tag> 'k_scatter<11' [rows]"""
 import csv, glob, collections, sys
 d, prefix = sys.argv[1], sys.argv[2]
 rows = float(sys.argv[3]) if len(sys.argv) > 3 else None

@@ -1,6 +1,6 @@
 """Summarise the rocprofv3 PMC passes of tools/final_profile.sh into profiles/<tag>_traffic.json.
 
-    python tools/pmc_summary.py gpurun_out/final profiles/r01_final_traffic.json
+    python tools/pmc_summary.py profile_out/final profiles/r01_final_traffic.json
 
 Reads <dir>/pmc_FETCH_SIZE, <dir>/pmc_WRITE_SIZE, <dir>/pmc_TCC_HIT_sum_TCC_MISS_sum (one counter set per pass, as the
 MI355X guide prescribes) and writes, per kernel of the Schur round, the mean per dispatch of
@@ -53,7 +53,7 @@ def main():
             "l2_hit_rate": round(hit / (hit + miss), 3) if hit + miss > 0 else None,
         }
     note = ("rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / TCC_HIT_sum TCC_MISS_sum in separate passes "
-            "(python3 bench.py --steps 3 --warmup 1), mean per dispatch, KiB * 1024. Calibrated with tools/fetch_calib.hip "
+            "(python3 bench.py --full --steps 3 --warmup 1), mean per dispatch, KiB * 1024. Calibrated with tools/fetch_calib.hip "
             "on the same box: FETCH_SIZE = 1.000 x bytes for 8-byte-per-lane reads in 64-byte segments (the pivot-row "
             "access shape of k_scatter), 0.500 x for a coalesced 8-byte-per-lane stream; WRITE_SIZE = 1.000 x for "
             "compacted 8-byte stores.")

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 for so in spasm.jl_amd/variants/*.so; do
   echo "== $so"
-  SPASM_AMD_LIB=$PWD/$so timeout -k 10 120 python bench.py --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+  SPASM_AMD_LIB=$PWD/$so timeout -k 10 120 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 r=d['roofline']
