@@ -209,6 +209,25 @@ void spasm_scatter(const struct spasm_csr *A, int i, spasm_ZZp beta, spasm_ZZp *
  * (spasm_amd_triangular_solve does all rows of B in one pass). */
 int spasm_sparse_triangular_solve(const struct spasm_csr *U, const struct spasm_csr *B, int k, int *xj, spasm_ZZp *x, const int *qinv);
 
+/* ---- spasm_spmv.c as SpaSM.jl binds it (src/SpaSM.jl:640-658: xapy!, axpy!, x * A, A * x) ----
+ * Host arrays.  spasm_Axpy: y <- A x + y, x has A->m entries, y has A->n.  spasm_xApy: y <- x A + y, x has A->n entries, y has
+ * A->m.  Any int32 in x or y is accepted (reduced like the values of A); on return y holds balanced residues.  On failure (no
+ * device, A->x == NULL, out of memory) y is unchanged and spasm_amd_last_error() says why.  Exact, on the device (csrc/spmv.hpp). */
+void spasm_Axpy(const struct spasm_csr *A, const spasm_ZZp *x, spasm_ZZp *y);  /* src/SpaSM.jl:656 */
+void spasm_xApy(const spasm_ZZp *x, const struct spasm_csr *A, spasm_ZZp *y);  /* src/SpaSM.jl:643 */
+
+/* Engine extension: A resident on the device for repeated products (A may be freed once the operator exists).
+ * spasm_amd_spmv_apply: Y <- op(A) X + Y for k vectors at once.  trans = 0: op(A) = A, X is m x k, Y is n x k; trans = 1:
+ * op(A) = A^T, i.e. the k products x_i A, X is n x k, Y is m x k.  Row-major, leading dimensions ldx, ldy >= k (in entries).
+ * The transpose is built on the device on the first trans = 1 apply and kept.  Returns 0, or -1 with Y unchanged.
+ * spasm_amd_spmv_apply_dev: the same on device arrays (X and Y must not overlap); stream NULL: returns when Y is written, else
+ * the products are enqueued on that hipStream_t.  One apply at a time per operator. */
+typedef struct spasm_amd_spmv spasm_amd_spmv;
+spasm_amd_spmv *spasm_amd_spmv_create(const struct spasm_csr *A);
+int spasm_amd_spmv_apply(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy);
+int spasm_amd_spmv_apply_dev(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy, void *stream);
+void spasm_amd_spmv_free(spasm_amd_spmv *op);
+
 /* ---- spasm_transpose.c ---- */
 struct spasm_csr *spasm_transpose(const struct spasm_csr *A);        /* src/SpaSM.jl:589 (one-argument form) */
 

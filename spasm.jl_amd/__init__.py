@@ -11,9 +11,11 @@ from .api import (
     EchelonizeOpts,
     Field,
     SpasmError,
+    SpMV,
     Triplet,
     ZZp,
     RankCertificate,
+    axpy,
     balanced,
     certificate_rank_create,
     certificate_rank_verify,
@@ -38,9 +40,11 @@ from .api import (
     sparse_triangular_solve_row,
     synth_csr,
     transpose,
+    xapy,
 )
 
 __all__ = [
     "Block", "blocks", "CSR", "LU", "Triplet", "load", "save", "EchelonizeOpts", "Field", "SpasmError", "ZZp", "balanced", "RankCertificate", "certificate_rank_create", "certificate_rank_verify", "rank_certificate_save", "rank_certificate_load", "echelonize", "echelonize_multi", "factorization_verify", "gesv", "solve", "kernel",
     "last_rounds", "nnz", "prime0", "rank", "rref", "sparse", "sparse_triangular_solve", "sparse_triangular_solve_row", "scatter", "synth_csr", "transpose",
+    "axpy", "xapy", "SpMV",
 ]

@@ -243,6 +243,12 @@ SIGNATURES = {
     "spasm_amd_dshard_finish": (C.c_int32, [C.c_void_p]),
     "spasm_amd_dshard_fetch_U": (_P(CsrStruct), [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     "spasm_amd_dshard_close": (None, [C.c_void_p]),
+    "spasm_Axpy": (None, [_P(CsrStruct), C.c_void_p, C.c_void_p]),
+    "spasm_xApy": (None, [C.c_void_p, _P(CsrStruct), C.c_void_p]),
+    "spasm_amd_spmv_create": (C.c_void_p, [_P(CsrStruct)]),
+    "spasm_amd_spmv_apply": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
+    "spasm_amd_spmv_apply_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_spmv_free": (None, [C.c_void_p]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

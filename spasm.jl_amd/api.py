@@ -206,6 +206,19 @@ class CSR:
             out.append(sorted(zip(j[lo:hi].tolist(), x[lo:hi].tolist())))
         return out
 
+    # `ndarray @ CSR` reaches __rmatmul__ only when numpy steps aside
+    __array_ufunc__ = None
+
+    def __matmul__(self, x):
+        """A @ x (reference src/SpaSM.jl:658, A * x): x of shape (m,) or (m, k), integers (reduced mod p); a new int32 array of
+        shape (n,) or (n, k)."""
+        return _product(self, x, trans=False)
+
+    def __rmatmul__(self, x):
+        """x @ A (reference src/SpaSM.jl:645, x * A): x of shape (n,) or (k, n), integers (reduced mod p); a new int32 array of
+        shape (m,) or (k, m)."""
+        return _product(self, x, trans=True)
+
     def todense(self):
         """Dense libspasm-side matrix (n x m) of balanced residues."""
         D = np.zeros((self.n, self.m), dtype=np.int64)
@@ -238,6 +251,175 @@ def transpose(A):
     if not t:
         raise SpasmError("spasm_transpose failed: " + _abi.last_error())
     return CSR(t)
+
+
+# ---------------------------------------------------------------------------------------------
+# Exact products y <- A x + y, y <- x A + y  (reference src/SpaSM.jl:640-658; csrc/spmv.hpp)
+# ---------------------------------------------------------------------------------------------
+def _host_vec(a, n, name):
+    if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+        raise TypeError(f"{name} must be an int32 numpy array")
+    if a.shape != (n,):
+        raise ValueError(f"{name} must have shape ({n},), not {a.shape}")
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{name} must be contiguous")
+    return a
+
+
+def _check_void(who):
+    err = _abi.last_error()
+    if err:
+        raise SpasmError(err if err.startswith(who) else f"{who} failed: {err}")
+
+
+def axpy(A, x, y):
+    """axpy!(A, x, y) (reference src/SpaSM.jl:653-657): y <- A x + y in place and returned.  x: int32, A.m entries; y: int32,
+    A.n entries (any int32 values; y ends as balanced residues)."""
+    _host_vec(x, A.m, "x")
+    _host_vec(y, A.n, "y")
+    if not y.flags["WRITEABLE"]:
+        raise ValueError("y must be writable")
+    _abi.lib().spasm_Axpy(A.data, x.ctypes.data, y.ctypes.data)
+    _check_void("spasm_Axpy")
+    return y
+
+
+def xapy(x, A, y):
+    """xapy!(x, A, y) (reference src/SpaSM.jl:640-644): y <- x A + y in place and returned.  x: int32, A.n entries; y: int32,
+    A.m entries."""
+    _host_vec(x, A.n, "x")
+    _host_vec(y, A.m, "y")
+    if not y.flags["WRITEABLE"]:
+        raise ValueError("y must be writable")
+    _abi.lib().spasm_xApy(x.ctypes.data, A.data, y.ctypes.data)
+    _check_void("spasm_xApy")
+    return y
+
+
+def _product(A, x, trans):
+    """A @ x (trans=False) or x @ A (trans=True) as a new int32 array."""
+    x = np.asarray(x)
+    if x.dtype.kind not in "iu":
+        raise TypeError("integer entries expected")
+    inner, outer = (A.n, A.m) if trans else (A.m, A.n)
+    if x.ndim == 1:
+        if x.shape[0] != inner:
+            raise ValueError(f"dimension mismatch: {A.shape} matrix and vector of {x.shape[0]} entries")
+        xr = balanced(x, A.prime)
+        y = np.zeros(outer, dtype=np.int32)
+        return xapy(xr, A, y) if trans else axpy(A, xr, y)
+    if x.ndim != 2:
+        raise ValueError("a vector or a matrix expected")
+    # x @ A with x of shape (k, n) is the block of the k products x_i A: the operator takes it as n x k
+    X = balanced(x.T if trans else x, A.prime)
+    if X.shape[0] != inner:
+        raise ValueError(f"dimension mismatch: {A.shape} matrix and block of shape {x.shape}")
+    with SpMV(A) as op:
+        Y = op.apply(np.ascontiguousarray(X), trans=trans)
+    return np.ascontiguousarray(Y.T) if trans else Y
+
+
+class SpMV:
+    """A resident on the device for repeated exact products (spasm_amd_spmv_*; engine extension).  A is the stored CSR, n x m
+    (A.shape), and may be dropped once the operator exists.
+
+    apply(X, Y=None, trans=False): Y <- A X + Y (trans=False: X is m x k, Y is n x k) or Y <- A^T X + Y, i.e. the k products
+    x_i A with x_i the columns of X (trans=True: X is n x k, Y is m x k); X of shape (rows,) is one vector.  Y is updated in place
+    and returned (None: zeros).  int32 numpy arrays, or int32 torch tensors on the current device (enqueued on the current
+    stream).  The transpose is built on the device by the first trans=True apply and kept."""
+
+    def __init__(self, A):
+        self.shape = A.shape
+        self.prime = A.prime
+        self._op = _abi.lib().spasm_amd_spmv_create(A.data)
+        if not self._op:
+            raise SpasmError(_abi.last_error() or "spasm_amd_spmv_create failed")
+
+    def close(self):
+        op, self._op = getattr(self, "_op", None), None
+        if op:
+            _abi.lib().spasm_amd_spmv_free(op)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def apply(self, X, Y=None, trans=False):
+        if not self._op:
+            raise SpasmError("the operator is closed")
+        n, m = self.shape
+        rin, rout = (n, m) if trans else (m, n)
+        if type(X).__module__.startswith("torch"):
+            return self._apply_torch(X, Y, bool(trans), rin, rout)
+        if not isinstance(X, np.ndarray) or X.dtype != np.int32:
+            raise TypeError("X must be an int32 numpy array or torch tensor")
+        if X.ndim not in (1, 2) or X.shape[0] != rin:
+            raise ValueError(f"X must have shape ({rin},) or ({rin}, k), not {X.shape}")
+        k = 1 if X.ndim == 1 else X.shape[1]
+        if Y is None:
+            Y = np.zeros((rout,) + X.shape[1:], dtype=np.int32)
+        if not isinstance(Y, np.ndarray) or Y.dtype != np.int32:
+            raise TypeError("Y must be an int32 numpy array")
+        if Y.shape != (rout,) + X.shape[1:]:
+            raise ValueError(f"Y must have shape {(rout,) + X.shape[1:]}, not {Y.shape}")
+        if not Y.flags["WRITEABLE"]:
+            raise ValueError("Y must be writable")
+        Xc = _rows_view(X, "X")
+        Yc = _rows_view(Y, "Y")
+        ldx = k if X.ndim == 1 else max(Xc.strides[0] // 4, k)
+        ldy = k if Y.ndim == 1 else max(Yc.strides[0] // 4, k)
+        rc = _abi.lib().spasm_amd_spmv_apply(self._op, int(trans), int(k), Xc.ctypes.data, ldx, Yc.ctypes.data, ldy)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return Y
+
+    def _apply_torch(self, X, Y, trans, rin, rout):
+        import torch
+
+        if X.dtype != torch.int32 or X.device.type != "cuda" or X.device.index != torch.cuda.current_device():
+            raise TypeError("X must be an int32 tensor on the current device")
+        if X.dim() not in (1, 2) or X.shape[0] != rin:
+            raise ValueError(f"X must have shape ({rin},) or ({rin}, k), not {tuple(X.shape)}")
+        k = 1 if X.dim() == 1 else X.shape[1]
+        if Y is None:
+            Y = torch.zeros((rout,) + tuple(X.shape[1:]), dtype=torch.int32, device=X.device)
+        if Y.dtype != torch.int32 or Y.device != X.device:
+            raise TypeError("Y must be an int32 tensor on the device of X")
+        if tuple(Y.shape) != (rout,) + tuple(X.shape[1:]):
+            raise ValueError(f"Y must have shape {(rout,) + tuple(X.shape[1:])}, not {tuple(Y.shape)}")
+        for t, name in ((X, "X"), (Y, "Y")):
+            if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < k):
+                raise ValueError(f"{name} must have unit stride along its rows")
+        if X.data_ptr() == Y.data_ptr():
+            raise ValueError("X and Y must not overlap")
+        ldx = k if X.dim() == 1 else max(X.stride(0), k)
+        ldy = k if Y.dim() == 1 else max(Y.stride(0), k)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _abi.lib().spasm_amd_spmv_apply_dev(self._op, int(trans), int(k), C.c_void_p(X.data_ptr()), ldx, C.c_void_p(Y.data_ptr()), ldy,
+                                                  C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return Y
+
+
+def _rows_view(a, name):
+    """a itself when its rows are unit-stride and laid out at a positive leading dimension (what the C call takes)"""
+    if a.ndim == 1:
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError(f"{name} must be contiguous")
+        return a
+    if a.strides[1] != 4 or (a.shape[0] > 1 and a.strides[0] < 4 * a.shape[1]) or a.strides[0] % 4:
+        raise ValueError(f"{name} must have unit stride along its rows")
+    return a
 
 
 # ---------------------------------------------------------------------------------------------

@@ -11,6 +11,7 @@
 #include "fused.hpp"
 #include "greedy.hpp"
 #include "dense.hpp"
+#include "spmv.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -5833,6 +5834,205 @@ struct spasm_csr *dshard_fetch_U(spasm_amd_dshard *ds, int *pivcol_out, int *row
 
 } // namespace
 
+// ------------------------------------------------------------------------------------------------
+// Exact products with A (spmv.hpp): the operator keeps A on the device, and its transpose once a product x A is asked for.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// one orientation as gather-by-row, with its rows binned by length (spmv.hpp)
+struct SpmvView {
+    int rows = 0, cols = 0;
+    const i64d *start = nullptr;
+    const int *len = nullptr;
+    const int2 *ent = nullptr;
+    DevBuf<int> tlen;                      // transposed view: row lengths from the row pointers
+    int nshort = 0, nmid = 0, nlong = 0, nseg = 0;
+    bool short_all = false;                // every row is short: the short kernel runs over 0 .. rows-1 without a list
+    DevBuf<int> short_rows, mid_rows, long_rows, long_off, seg_row, seg_beg, part;
+
+    // hlen: an upper bound of every row's length (the host CSR's, before zeros are dropped, or the transpose's)
+    void bin(const std::vector<i64> &hlen, hipStream_t s)
+    {
+        std::vector<int> sr, mr, lr, lo, sg, sb;
+        for (int i = 0; i < rows; i++) {
+            const i64 l = hlen[(size_t)i];
+            if (l <= SPMV_SHORT) sr.push_back(i);
+            else if (l <= SPMV_SEG) mr.push_back(i);
+            else {
+                lr.push_back(i);
+                lo.push_back((int)sg.size());
+                for (i64 b = 0; b < l; b += SPMV_SEG) { sg.push_back(i); sb.push_back((int)b); }
+            }
+        }
+        lo.push_back((int)sg.size());
+        nshort = (int)sr.size();
+        nmid = (int)mr.size();
+        nlong = (int)lr.size();
+        nseg = (int)sg.size();
+        short_all = nshort == rows;
+        auto up = [&](DevBuf<int> &d, const std::vector<int> &h) {
+            d.alloc(h.size());
+            if (!h.empty()) HIPCHK(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        };
+        if (!short_all) up(short_rows, sr);
+        up(mid_rows, mr);
+        up(long_rows, lr);
+        up(long_off, lo);
+        up(seg_row, sg);
+        up(seg_beg, sb);
+        part.alloc((size_t)nseg * 64);
+        HIPCHK(hipStreamSynchronize(s)); // the host vectors go out of scope
+    }
+};
+
+template <bool SMALL, int KW>
+void spmv_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, i64 ldx, int *Y, i64 ldy, hipStream_t s)
+{
+    constexpr int TS = spmv_short_team(KW);
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp;
+    if (V.nshort > 0)
+        hipLaunchKernelGGL((k_spmv<SMALL, KW, TS, false>), dim3(cdiv((i64)V.nshort * TS, 256)), dim3(256), 0, s, V.nshort,
+                           V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, nullptr);
+    if (V.nmid > 0)
+        hipLaunchKernelGGL((k_spmv<SMALL, KW, 64, false>), dim3(cdiv((i64)V.nmid * 64, 256)), dim3(256), 0, s, V.nmid, V.mid_rows.p, nullptr, V.start,
+                           V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, nullptr);
+    if (V.nlong > 0) {
+        hipLaunchKernelGGL((k_spmv<SMALL, KW, 64, true>), dim3(cdiv((i64)V.nseg * 64, 256)), dim3(256), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p, V.start,
+                           V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, V.part.p);
+        hipLaunchKernelGGL(k_spmv_combine, dim3(cdiv((i64)V.nlong * KW, 256)), dim3(256), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p, KW, kc,
+                           F, Y, (i64d)ldy);
+    }
+    HIPCHK(hipGetLastError());
+}
+
+template <bool SMALL>
+void spmv_chunk(const SpmvView &V, const ZpField &F, int kw, int kc, const int *X, i64 ldx, int *Y, i64 ldy, hipStream_t s)
+{
+    switch (kw) {
+    case 1: spmv_launch<SMALL, 1>(V, F, kc, X, ldx, Y, ldy, s); break;
+    case 2: spmv_launch<SMALL, 2>(V, F, kc, X, ldx, Y, ldy, s); break;
+    case 4: spmv_launch<SMALL, 4>(V, F, kc, X, ldx, Y, ldy, s); break;
+    case 8: spmv_launch<SMALL, 8>(V, F, kc, X, ldx, Y, ldy, s); break;
+    case 16: spmv_launch<SMALL, 16>(V, F, kc, X, ldx, Y, ldy, s); break;
+    case 32: spmv_launch<SMALL, 32>(V, F, kc, X, ldx, Y, ldy, s); break;
+    default: spmv_launch<SMALL, 64>(V, F, kc, X, ldx, Y, ldy, s); break;
+    }
+}
+
+} // namespace
+
+struct spasm_amd_spmv {
+    int dev = 0;
+    ZpField F;
+    DevMat A;
+    TransposeOut T;
+    bool have_t = false;
+    SpmvView fwd, tr;
+    DevBuf<int> hx, hy;   // staging of the host-array applies
+
+    // the transposed view, built on the first x A: the device counting sort of the engine, then its rows binned
+    void build_transpose()
+    {
+        if (have_t) return;
+        hipStream_t s = nullptr;
+        Scanner scan;
+        device_transpose(A, A.n, nullptr, nullptr, 0, scan, s, T);
+        tr.rows = A.m;
+        tr.cols = A.n;
+        tr.start = T.Tp.p;
+        tr.tlen.alloc((size_t)A.m + 1);
+        if (A.m > 0) {
+            hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(A.m, 256)), dim3(256), 0, s, A.m, T.Tp.p, tr.tlen.p);
+            HIPCHK(hipGetLastError());
+        }
+        tr.len = tr.tlen.p;
+        tr.ent = T.Tent.p;
+        std::vector<i64d> tp((size_t)A.m + 1);
+        HIPCHK(hipMemcpyAsync(tp.data(), T.Tp.p, tp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        std::vector<i64> hl((size_t)A.m);
+        for (int i = 0; i < A.m; i++) hl[(size_t)i] = tp[(size_t)i + 1] - tp[(size_t)i];
+        tr.bin(hl, s);
+        have_t = true;
+    }
+
+    // Y <- op(A) X + Y on device arrays, enqueued on s
+    void apply_dev(int trans, int k, const int *X, i64 ldx, int *Y, i64 ldy, hipStream_t s)
+    {
+        if (trans) build_transpose();
+        const SpmvView &V = trans ? tr : fwd;
+        for (int k0 = 0; k0 < k; k0 += 64) {
+            const int rem = k - k0;
+            int kw = 1;
+            while (kw < rem && kw < 64) kw <<= 1;
+            const int kc = rem < kw ? rem : kw;
+            if (F.small) spmv_chunk<true>(V, F, kw, kc, X + k0, ldx, Y + k0, ldy, s);
+            else spmv_chunk<false>(V, F, kw, kc, X + k0, ldx, Y + k0, ldy, s);
+        }
+    }
+
+    // the same on host arrays, through device copies packed with leading dimension k; Y is written only once all went well
+    void apply_host(int trans, int k, const int *X, i64 ldx, int *Y, i64 ldy)
+    {
+        if (trans) build_transpose();
+        const SpmvView &V = trans ? tr : fwd;
+        const size_t xr = (size_t)V.cols, yr = (size_t)V.rows, kk = (size_t)k;
+        if (k == 0 || yr == 0) return;
+        hipStream_t s = nullptr;
+        hx.ensure(xr * kk);
+        hy.ensure(yr * kk);
+        if (xr > 0) HIPCHK(hipMemcpy2DAsync(hx.p, kk * sizeof(int), X, (size_t)ldx * sizeof(int), kk * sizeof(int), xr, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(hy.p, kk * sizeof(int), Y, (size_t)ldy * sizeof(int), kk * sizeof(int), yr, hipMemcpyHostToDevice, s));
+        apply_dev(trans, k, hx.p, k, hy.p, k, s);
+        std::vector<int> out(yr * kk);
+        HIPCHK(hipMemcpyAsync(out.data(), hy.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (size_t i = 0; i < yr; i++) memcpy(Y + i * (size_t)ldy, out.data() + i * kk, kk * sizeof(int));
+    }
+};
+
+namespace {
+
+spasm_amd_spmv *spmv_create(const struct spasm_csr *A, const char *who)
+{
+    require_device();
+    check_input(A, who);
+    if (!A->x) throw EngineError(std::string(who) + ": matrix without values (A->x == NULL)");
+    std::unique_ptr<spasm_amd_spmv> op(new spasm_amd_spmv());
+    HIPCHK(hipGetDevice(&op->dev));
+    op->F = zp_field_make(A->field->p);
+    hipStream_t s = nullptr;
+    upload_csr(A, 0, A->n, op->A, s);
+    SpmvView &V = op->fwd;
+    V.rows = A->n;
+    V.cols = A->m;
+    V.start = op->A.start.p;
+    V.len = op->A.len.p;
+    V.ent = op->A.ent.p;
+    std::vector<i64> hl((size_t)A->n);
+    for (int i = 0; i < A->n; i++) hl[(size_t)i] = A->p[i + 1] - A->p[i];
+    V.bin(hl, s);
+    return op.release();
+}
+
+void spmv_check(const spasm_amd_spmv *op, int trans, int k, const void *X, i64 ldx, const void *Y, i64 ldy, const char *who)
+{
+    if (!op) throw EngineError(std::string(who) + ": NULL operator");
+    if (k < 0 || ldx < k || ldy < k || (trans != 0 && trans != 1)) throw EngineError(std::string(who) + ": bad arguments (trans 0/1, k >= 0, ldx >= k, ldy >= k)");
+    const int xr = trans ? op->A.n : op->A.m, yr = trans ? op->A.m : op->A.n;
+    if (k > 0 && ((xr > 0 && !X) || (yr > 0 && !Y))) throw EngineError(std::string(who) + ": NULL array");
+}
+
+// spasm_Axpy / spasm_xApy: y <- op(A) x + y through a temporary operator
+void spmv_once(const struct spasm_csr *A, int trans, const spasm_ZZp *x, spasm_ZZp *y, const char *who)
+{
+    std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, who));
+    spmv_check(op.get(), trans, 1, x, 1, y, 1, who);
+    op->apply_host(trans, 1, x, 1, y, 1);
+}
+
+} // namespace
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -6433,6 +6633,78 @@ SPASM_API struct spasm_csr *spasm_amd_dshard_fetch_U(spasm_amd_dshard *ds, int *
     DSHARD_TRY("spasm_amd_dshard_fetch_U", DSHARD_BUILT(ds); return dshard_fetch_U(ds, pivcol_out, row_out, n_out);, nullptr)
 }
 SPASM_API void spasm_amd_dshard_close(spasm_amd_dshard *ds) { delete ds; }
+
+// reference src/SpaSM.jl:640-658 (axpy!, xapy!, A * x, x * A): host arrays; on failure y is left as it was
+SPASM_API void spasm_Axpy(const struct spasm_csr *A, const spasm_ZZp *x, spasm_ZZp *y)
+{
+    spasm_clear_error();
+    try {
+        spmv_once(A, 0, x, y, "spasm_Axpy");
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_Axpy: %s", e.what());
+    }
+}
+
+SPASM_API void spasm_xApy(const spasm_ZZp *x, const struct spasm_csr *A, spasm_ZZp *y)
+{
+    spasm_clear_error();
+    try {
+        spmv_once(A, 1, x, y, "spasm_xApy");
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_xApy: %s", e.what());
+    }
+}
+
+SPASM_API spasm_amd_spmv *spasm_amd_spmv_create(const struct spasm_csr *A)
+{
+    spasm_clear_error();
+    try {
+        return spmv_create(A, "spasm_amd_spmv_create");
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_amd_spmv_create: %s", e.what());
+        return nullptr;
+    }
+}
+
+SPASM_API int spasm_amd_spmv_apply(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy)
+{
+    spasm_clear_error();
+    try {
+        spmv_check(op, trans, k, X, ldx, Y, ldy, "spasm_amd_spmv_apply");
+        DeviceGuard g;
+        HIPCHK(hipSetDevice(op->dev));
+        op->apply_host(trans, k, X, ldx, Y, ldy);
+        return 0;
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_amd_spmv_apply: %s", e.what());
+        return -1;
+    }
+}
+
+SPASM_API int spasm_amd_spmv_apply_dev(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy, void *stream)
+{
+    spasm_clear_error();
+    try {
+        spmv_check(op, trans, k, X, ldx, Y, ldy, "spasm_amd_spmv_apply_dev");
+        DeviceGuard g;
+        HIPCHK(hipSetDevice(op->dev));
+        hipStream_t s = (hipStream_t)stream;
+        if (k > 0) op->apply_dev(trans, k, X, ldx, Y, ldy, s);
+        if (!stream) HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_amd_spmv_apply_dev: %s", e.what());
+        return -1;
+    }
+}
+
+SPASM_API void spasm_amd_spmv_free(spasm_amd_spmv *op)
+{
+    if (!op) return;
+    DeviceGuard g;
+    (void)hipSetDevice(op->dev);
+    delete op;
+}
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
 {
