@@ -228,6 +228,34 @@ int spasm_amd_spmv_apply(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *
 int spasm_amd_spmv_apply_dev(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy, void *stream);
 void spasm_amd_spmv_free(spasm_amd_spmv *op);
 
+/* ---- spasm_triangular.c, dense right-hand sides (src/SpaSM.jl:663-692: dense_back_solve, dense_forward_solve) ----
+ * Solve x T = b, T n x m.  Participating row i has the pivot column c(i) and the diagonal d(i) = T[i][c(i)]:
+ *   forward: c(i) = q[i] (n entries, q[i] < 0: row i does not participate), d(i) must be 1;
+ *   back:    c(p[j]) = j for every j with p[j] >= 0 (m entries), d(i) must be non-zero.
+ * The pivot graph (edge i -> k when row i has an entry on c(k), k != i) must be acyclic; the rows need not be stored in a
+ * triangular order.  x (n entries) is 0 on the rows that do not participate and on the others the unique vector with
+ * (x T)[c(k)] = b[c(k)] for every participating k.  On return b holds the residual b - x T (balanced residues); the result is
+ * true iff it is zero.  Any int32 in b or x is accepted.  Errors (a NULL argument, a pivot out of range or claimed twice, a
+ * non-unit pivot (forward), a zero diagonal (back), a cycle, no device): false, b and x unchanged, spasm_amd_last_error() says
+ * why; after a solve the error text is empty whether or not a solution exists.  Exact, on the device (csrc/trsolve.hpp). */
+bool spasm_dense_forward_solve(const struct spasm_csr *U, spasm_ZZp *b, spasm_ZZp *x, const int *q);   /* src/SpaSM.jl:691 */
+bool spasm_dense_back_solve(const struct spasm_csr *L, spasm_ZZp *b, spasm_ZZp *x, const int *p);      /* src/SpaSM.jl:676 */
+
+/* Engine extension: T resident on the device for repeated solves (T may be freed once the operator exists).
+ * spasm_amd_trsolve_create: kind 0 forward (piv = q, n entries), kind 1 back (piv = p, m entries); does every structural check
+ * above once (cycle included) and returns NULL with the reason on failure.
+ * spasm_amd_trsolve_apply: k systems at once.  B is m x k (right-hand sides in, residuals out), X is n x k, row-major with leading
+ * dimensions ldb, ldx >= k; vector v is column v; ok[v] = 1 iff residual v is zero.  Returns 0, or -1 with B and X unchanged.
+ * spasm_amd_trsolve_apply_dev: the same on device arrays (ok too), enqueued on the hipStream_t stream (NULL: returns when done).
+ * spasm_amd_trsolve_stats: out[8] = n, m, participating rows, levels, wide panels, chunks, kernels of one apply (k <= 64),
+ * stored entries.  One apply at a time per operator. */
+typedef struct spasm_amd_trsolve spasm_amd_trsolve;
+spasm_amd_trsolve *spasm_amd_trsolve_create(const struct spasm_csr *T, const int *piv, int kind);
+int spasm_amd_trsolve_apply(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok);
+int spasm_amd_trsolve_apply_dev(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream);
+void spasm_amd_trsolve_stats(const spasm_amd_trsolve *op, i64 *out);
+void spasm_amd_trsolve_free(spasm_amd_trsolve *op);
+
 /* ---- spasm_transpose.c ---- */
 struct spasm_csr *spasm_transpose(const struct spasm_csr *A);        /* src/SpaSM.jl:589 (one-argument form) */
 

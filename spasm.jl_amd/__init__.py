@@ -12,11 +12,14 @@ from .api import (
     Field,
     SpasmError,
     SpMV,
+    TriangularSolver,
     Triplet,
     ZZp,
     RankCertificate,
     axpy,
     balanced,
+    dense_back_solve,
+    dense_forward_solve,
     certificate_rank_create,
     certificate_rank_verify,
     rank_certificate_load,
@@ -46,5 +49,5 @@ from .api import (
 __all__ = [
     "Block", "blocks", "CSR", "LU", "Triplet", "load", "save", "EchelonizeOpts", "Field", "SpasmError", "ZZp", "balanced", "RankCertificate", "certificate_rank_create", "certificate_rank_verify", "rank_certificate_save", "rank_certificate_load", "echelonize", "echelonize_multi", "factorization_verify", "gesv", "solve", "kernel",
     "last_rounds", "nnz", "prime0", "rank", "rref", "sparse", "sparse_triangular_solve", "sparse_triangular_solve_row", "scatter", "synth_csr", "transpose",
-    "axpy", "xapy", "SpMV",
+    "axpy", "xapy", "SpMV", "dense_forward_solve", "dense_back_solve", "TriangularSolver",
 ]

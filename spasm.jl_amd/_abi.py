@@ -249,6 +249,13 @@ SIGNATURES = {
     "spasm_amd_spmv_apply": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "spasm_amd_spmv_apply_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_spmv_free": (None, [C.c_void_p]),
+    "spasm_dense_forward_solve": (C.c_bool, [_P(CsrStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spasm_dense_back_solve": (C.c_bool, [_P(CsrStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "spasm_amd_trsolve_create": (C.c_void_p, [_P(CsrStruct), C.c_void_p, C.c_int32]),
+    "spasm_amd_trsolve_apply": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_trsolve_apply_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spasm_amd_trsolve_stats": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_trsolve_free": (None, [C.c_void_p]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -423,6 +423,161 @@ def _rows_view(a, name):
 
 
 # ---------------------------------------------------------------------------------------------
+# Dense triangular solves x T = b  (reference src/SpaSM.jl:663-692; csrc/trsolve.hpp)
+# ---------------------------------------------------------------------------------------------
+def _dense_solve(sym, T, b, x, piv, npiv):
+    _host_vec(b, T.m, "b")
+    _host_vec(x, T.n, "x")
+    _host_vec(piv, npiv, "q" if sym == "spasm_dense_forward_solve" else "p")
+    if not b.flags["WRITEABLE"] or not x.flags["WRITEABLE"]:
+        raise ValueError("b and x must be writable")
+    ok = getattr(_abi.lib(), sym)(T.data, b.ctypes.data, x.ctypes.data, piv.ctypes.data)
+    if not ok:
+        _check_void(sym)
+    return bool(ok)
+
+
+def dense_forward_solve(U, b, x, q):
+    """dense_forward_solve(U, b, x, q) (reference src/SpaSM.jl:688-692): solves x U = b.  U: n x m with unit pivots, q[i] the
+    pivot column of row i (< 0: none); b: int32, m entries, overwritten by the residual b - x U; x: int32, n entries, filled.
+    True iff the residual is zero; SpasmError on a malformed U (pivot out of range or twice, non-unit pivot, cycle)."""
+    return _dense_solve("spasm_dense_forward_solve", U, b, x, q, U.n)
+
+
+def dense_back_solve(L, b, x, p):
+    """dense_back_solve(L, b, x, p) (reference src/SpaSM.jl:673-677): solves x L = b.  L: n x m, p[j] the row whose diagonal
+    entry (non-zero) is on column j (< 0: none); b: int32, m entries, overwritten by the residual; x: int32, n entries, filled.
+    True iff the residual is zero; SpasmError on a malformed L (pivot out of range or twice, zero diagonal, cycle)."""
+    return _dense_solve("spasm_dense_back_solve", L, b, x, p, L.m)
+
+
+class TriangularSolver:
+    """T resident on the device for repeated solves x T = b (spasm_amd_trsolve_*; engine extension).  kind="forward": piv = q
+    (n entries, pivot column of each row, unit pivots); kind="back": piv = p (m entries, row of each column's diagonal).  T may be
+    dropped once the solver exists.
+
+    solve(B, X=None) -> (X, ok): B is m x k (the right-hand sides as columns; shape (m,) is one vector) and is overwritten by the
+    residuals; X (n x k, filled) and ok (k flags, or one for a vector) are returned.  int32 numpy arrays, or int32 torch tensors
+    on the current device (enqueued on the current stream; ok is then a bool tensor)."""
+
+    def __init__(self, T, piv, kind="forward"):
+        if kind not in ("forward", "back"):
+            raise ValueError('kind must be "forward" or "back"')
+        n, m = T.shape
+        if not isinstance(piv, np.ndarray) or piv.dtype != np.int32:
+            raise TypeError("piv must be an int32 numpy array")
+        npiv = n if kind == "forward" else m
+        if piv.shape != (npiv,):
+            raise ValueError(f"piv must have shape ({npiv},), not {piv.shape}")
+        piv = np.ascontiguousarray(piv)
+        self.shape = (n, m)
+        self.prime = T.prime
+        self.kind = kind
+        self._op = _abi.lib().spasm_amd_trsolve_create(T.data, piv.ctypes.data, 0 if kind == "forward" else 1)
+        if not self._op:
+            raise SpasmError(_abi.last_error() or "spasm_amd_trsolve_create failed")
+
+    @classmethod
+    def from_lu(cls, fact):
+        """The forward solver on fact.U, with q the inverse of fact.qinv"""
+        U = fact.U
+        qinv = np.asarray(fact.qinv)
+        q = np.full(U.n, -1, dtype=np.int32)
+        cols = np.flatnonzero(qinv >= 0)
+        q[qinv[cols]] = cols
+        return cls(U, q, "forward")
+
+    def stats(self):
+        """n, m, participating rows, levels, wide panels, chunks, kernels per apply (k <= 64), stored entries"""
+        out = (C.c_int64 * 8)()
+        _abi.lib().spasm_amd_trsolve_stats(self._op, out)
+        keys = ("n", "m", "rows", "levels", "wide_panels", "chunks", "launches", "entries")
+        return dict(zip(keys, [int(v) for v in out]))
+
+    def close(self):
+        op, self._op = getattr(self, "_op", None), None
+        if op:
+            _abi.lib().spasm_amd_trsolve_free(op)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def solve(self, B, X=None):
+        if not self._op:
+            raise SpasmError("the solver is closed")
+        n, m = self.shape
+        if type(B).__module__.startswith("torch"):
+            return self._solve_torch(B, X, n, m)
+        if not isinstance(B, np.ndarray) or B.dtype != np.int32:
+            raise TypeError("B must be an int32 numpy array or torch tensor")
+        if B.ndim not in (1, 2) or B.shape[0] != m:
+            raise ValueError(f"B must have shape ({m},) or ({m}, k), not {B.shape}")
+        if not B.flags["WRITEABLE"]:
+            raise ValueError("B must be writable")
+        k = 1 if B.ndim == 1 else B.shape[1]
+        if X is None:
+            X = np.zeros((n,) + B.shape[1:], dtype=np.int32)
+        if not isinstance(X, np.ndarray) or X.dtype != np.int32:
+            raise TypeError("X must be an int32 numpy array")
+        if X.shape != (n,) + B.shape[1:]:
+            raise ValueError(f"X must have shape {(n,) + B.shape[1:]}, not {X.shape}")
+        if not X.flags["WRITEABLE"]:
+            raise ValueError("X must be writable")
+        if k == 0:
+            return X, np.zeros(0, dtype=bool)
+        Bc = _rows_view(B, "B")
+        Xc = _rows_view(X, "X")
+        ldb = k if B.ndim == 1 else max(Bc.strides[0] // 4, k)
+        ldx = k if X.ndim == 1 else max(Xc.strides[0] // 4, k)
+        ok = np.zeros(k, dtype=np.uint8)
+        rc = _abi.lib().spasm_amd_trsolve_apply(self._op, int(k), Bc.ctypes.data, ldb, Xc.ctypes.data, ldx, ok.ctypes.data)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        ok = ok.astype(bool)
+        return X, (bool(ok[0]) if B.ndim == 1 else ok)
+
+    def _solve_torch(self, B, X, n, m):
+        import torch
+
+        if B.dtype != torch.int32 or B.device.type != "cuda" or B.device.index != torch.cuda.current_device():
+            raise TypeError("B must be an int32 tensor on the current device")
+        if B.dim() not in (1, 2) or B.shape[0] != m:
+            raise ValueError(f"B must have shape ({m},) or ({m}, k), not {tuple(B.shape)}")
+        k = 1 if B.dim() == 1 else B.shape[1]
+        if X is None:
+            X = torch.zeros((n,) + tuple(B.shape[1:]), dtype=torch.int32, device=B.device)
+        if X.dtype != torch.int32 or X.device != B.device:
+            raise TypeError("X must be an int32 tensor on the device of B")
+        if tuple(X.shape) != (n,) + tuple(B.shape[1:]):
+            raise ValueError(f"X must have shape {(n,) + tuple(B.shape[1:])}, not {tuple(X.shape)}")
+        for t, name in ((B, "B"), (X, "X")):
+            if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < k):
+                raise ValueError(f"{name} must have unit stride along its rows")
+        if n > 0 and m > 0 and B.data_ptr() == X.data_ptr():
+            raise ValueError("B and X must not overlap")
+        ldb = k if B.dim() == 1 else max(B.stride(0), k)
+        ldx = k if X.dim() == 1 else max(X.stride(0), k)
+        ok = torch.empty(max(k, 1), dtype=torch.uint8, device=B.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _abi.lib().spasm_amd_trsolve_apply_dev(self._op, int(k), C.c_void_p(B.data_ptr()), ldb, C.c_void_p(X.data_ptr()), ldx,
+                                                    C.c_void_p(ok.data_ptr()), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        ok = ok[:k].bool()
+        return X, (ok[0] if B.dim() == 1 else ok)
+
+
+# ---------------------------------------------------------------------------------------------
 # LU / echelonize / kernel / rank  (reference src/SpaSM.jl:262-305, :814-884, :1147-1149)
 # ---------------------------------------------------------------------------------------------
 class EchelonizeOpts:

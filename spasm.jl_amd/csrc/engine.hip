@@ -12,6 +12,7 @@
 #include "greedy.hpp"
 #include "dense.hpp"
 #include "spmv.hpp"
+#include "trsolve.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -6033,6 +6034,477 @@ void spmv_once(const struct spasm_csr *A, int trans, const spasm_ZZp *x, spasm_Z
 
 } // namespace
 
+// ------------------------------------------------------------------------------------------------
+// Dense triangular solves x T = b (trsolve.hpp): the operator keeps T on the device in the order of its pivot graph's levels,
+// cut into panels, with each panel's entries gathered by the later position they feed.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+struct TrsPanel {
+    int beg = 0, cnt = 0;   // positions beg .. beg + cnt - 1
+    bool wide = false;      // one level of >= TRS_WIDE rows; else a chunk of <= TRS_CHUNK rows
+    int nsteps = 0;         // chunk: its levels, ends at steps[step_off ..]; 1: no dependency inside, no diagonal block
+    i64 step_off = 0, diag_off = 0;
+    i64 desc_off = 0, nent = 0;
+    int ndesc = 0;
+    bool long_team = false; // push with a whole wave per descriptor
+};
+
+} // namespace
+
+struct spasm_amd_trsolve {
+    int dev = 0;
+    int n = 0, m = 0, kind = 0, npart = 0, nlevels = 0, nwide = 0, nchunk = 0;
+    i64 stored = 0;
+    ZpField F;
+    std::vector<TrsPanel> panels;
+    bool res_long = false;
+    DevBuf<int> pcol, pdinv, rowpos, colpos, steps, diag, dtgt, dlen;
+    DevBuf<i64d> dstart, rstart;
+    DevBuf<int2> gent, rent;
+    DevBuf<int> acc, xs;                   // per apply: npart x kw
+    DevBuf<int> hb, hx;                    // staging of the host-array applies
+    DevBuf<unsigned char> hok;
+
+    // kernels of one apply of at most 64 vectors
+    i64 launches() const
+    {
+        i64 c = 0;
+        for (const TrsPanel &P : panels) c += 1 + (P.ndesc > 0);
+        return c + (m > 0) + (n > 0);
+    }
+
+    template <bool SMALL, int KW>
+    void run(int kc, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
+    {
+        constexpr int TS = spmv_short_team(KW);
+        if (npart > 0) {
+            acc.ensure((size_t)npart * KW);
+            xs.ensure((size_t)npart * KW);
+            HIPCHK(hipMemsetAsync(acc.p, 0, (size_t)npart * KW * sizeof(int), s));
+            for (const TrsPanel &P : panels) {
+                if (P.wide)
+                    hipLaunchKernelGGL(k_trs_wide_solve, dim3(cdiv((i64)P.cnt * kc, 256)), dim3(256), 0, s, P.beg, P.cnt, pcol.p, pdinv.p, F, KW, kc, B,
+                                       (i64d)ldb, acc.p, xs.p);
+                else
+                    hipLaunchKernelGGL(k_trs_chunk_solve<SMALL>, dim3(1, cdiv(kc, TRS_CV)), dim3(TRS_CHUNK * TRS_CV), 0, s, P.beg, P.cnt, diag.p + P.diag_off,
+                                       steps.p + P.step_off, P.nsteps, pcol.p, pdinv.p, F, KW, kc, B, (i64d)ldb, acc.p, xs.p);
+                if (P.ndesc > 0) {
+                    if (P.long_team)
+                        hipLaunchKernelGGL((k_trs_push<SMALL, KW, 64>), dim3(cdiv((i64)P.ndesc * 64, 256)), dim3(256), 0, s, P.ndesc, dtgt.p + P.desc_off,
+                                           dstart.p + P.desc_off, dlen.p + P.desc_off, gent.p, F, kc, xs.p, acc.p);
+                    else
+                        hipLaunchKernelGGL((k_trs_push<SMALL, KW, TS>), dim3(cdiv((i64)P.ndesc * TS, 256)), dim3(256), 0, s, P.ndesc, dtgt.p + P.desc_off,
+                                           dstart.p + P.desc_off, dlen.p + P.desc_off, gent.p, F, kc, xs.p, acc.p);
+                }
+            }
+        }
+        if (m > 0) {
+            if (res_long)
+                hipLaunchKernelGGL((k_trs_residual<SMALL, KW, 64>), dim3(cdiv((i64)m * 64, 256)), dim3(256), 0, s, m, colpos.p, rstart.p, rent.p, F, kc, xs.p,
+                                   B, (i64d)ldb, ok);
+            else
+                hipLaunchKernelGGL((k_trs_residual<SMALL, KW, TS>), dim3(cdiv((i64)m * TS, 256)), dim3(256), 0, s, m, colpos.p, rstart.p, rent.p, F, kc, xs.p,
+                                   B, (i64d)ldb, ok);
+        }
+        if (n > 0) hipLaunchKernelGGL(k_trs_write_x, dim3(cdiv((i64)n * kc, 256)), dim3(256), 0, s, n, rowpos.p, KW, kc, xs.p, X, (i64d)ldx);
+        HIPCHK(hipGetLastError());
+    }
+
+    template <bool SMALL>
+    void run_kw(int kw, int kc, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
+    {
+        switch (kw) {
+        case 1: run<SMALL, 1>(kc, B, ldb, X, ldx, ok, s); break;
+        case 2: run<SMALL, 2>(kc, B, ldb, X, ldx, ok, s); break;
+        case 4: run<SMALL, 4>(kc, B, ldb, X, ldx, ok, s); break;
+        case 8: run<SMALL, 8>(kc, B, ldb, X, ldx, ok, s); break;
+        case 16: run<SMALL, 16>(kc, B, ldb, X, ldx, ok, s); break;
+        case 32: run<SMALL, 32>(kc, B, ldb, X, ldx, ok, s); break;
+        default: run<SMALL, 64>(kc, B, ldb, X, ldx, ok, s); break;
+        }
+    }
+
+    // X, residual in B and ok for k right-hand sides on device arrays, enqueued on s (k > 0)
+    void apply_dev(int k, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
+    {
+        HIPCHK(hipMemsetAsync(ok, 1, (size_t)k, s));
+        for (int k0 = 0; k0 < k; k0 += 64) {
+            const int rem = k - k0;
+            int kw = 1;
+            while (kw < rem && kw < 64) kw <<= 1;
+            const int kc = rem < kw ? rem : kw;
+            if (F.small) run_kw<true>(kw, kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
+            else run_kw<false>(kw, kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
+        }
+    }
+
+    // the same on host arrays, through device copies packed with leading dimension k; B, X and ok are written only once all went well
+    void apply_host(int k, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok)
+    {
+        if (k == 0) return;
+        hipStream_t s = nullptr;
+        const size_t kk = (size_t)k;
+        hb.ensure((size_t)m * kk);
+        hx.ensure((size_t)n * kk);
+        hok.ensure(kk);
+        if (m > 0) HIPCHK(hipMemcpy2DAsync(hb.p, kk * sizeof(int), B, (size_t)ldb * sizeof(int), kk * sizeof(int), (size_t)m, hipMemcpyHostToDevice, s));
+        apply_dev(k, hb.p, k, hx.p, k, hok.p, s);
+        std::vector<int> ob((size_t)m * kk), ox((size_t)n * kk);
+        std::vector<unsigned char> ook(kk);
+        if (m > 0) HIPCHK(hipMemcpyAsync(ob.data(), hb.p, ob.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (n > 0) HIPCHK(hipMemcpyAsync(ox.data(), hx.p, ox.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(ook.data(), hok.p, kk, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int i = 0; i < m; i++) memcpy(B + (size_t)i * (size_t)ldb, ob.data() + (size_t)i * kk, kk * sizeof(int));
+        for (int i = 0; i < n; i++) memcpy(X + (size_t)i * (size_t)ldx, ox.data() + (size_t)i * kk, kk * sizeof(int));
+        memcpy(ok, ook.data(), kk);
+    }
+};
+
+namespace {
+
+// All structural checks, the levels of the pivot graph, the panels and the gathered copies, on the host; then one upload.
+spasm_amd_trsolve *trsolve_create(const struct spasm_csr *T, const int *piv, int kind, const char *who)
+{
+    const std::string w(who);
+    if (!T) throw EngineError(w + ": NULL matrix");
+    if (kind != 0 && kind != 1) throw EngineError(w + ": kind must be 0 (forward, piv = q) or 1 (back, piv = p)");
+    require_device();
+    check_input(T, who);
+    const int n = T->n, m = T->m;
+    if (!piv && (kind == 0 ? n : m) > 0) throw EngineError(w + ": NULL pivot array");
+    std::unique_ptr<spasm_amd_trsolve> op(new spasm_amd_trsolve());
+    HIPCHK(hipGetDevice(&op->dev));
+    const ZpField F = zp_field_make(T->field->p);
+    op->F = F;
+    op->n = n;
+    op->m = m;
+    op->kind = kind;
+    const i64 *Tp = T->p;
+    const int *Tj = T->j;
+    const int *Tx = T->x;
+    char msg[256];
+
+    // pivots: c(i) and its inverse
+    std::vector<int> rowcol((size_t)n, -1), colrow((size_t)m, -1);
+    if (kind == 0) {
+        for (int i = 0; i < n; i++) {
+            const int j = piv[i];
+            if (j < 0) continue;
+            if (j >= m) { snprintf(msg, sizeof msg, "%s: q[%d] = %d is out of range (%d columns)", who, i, j, m); throw EngineError(msg); }
+            if (colrow[(size_t)j] >= 0) { snprintf(msg, sizeof msg, "%s: column %d is the pivot of rows %d and %d", who, j, colrow[(size_t)j], i); throw EngineError(msg); }
+            colrow[(size_t)j] = i;
+            rowcol[(size_t)i] = j;
+        }
+    } else {
+        for (int j = 0; j < m; j++) {
+            const int i = piv[j];
+            if (i < 0) continue;
+            if (i >= n) { snprintf(msg, sizeof msg, "%s: p[%d] = %d is out of range (%d rows)", who, j, i, n); throw EngineError(msg); }
+            if (rowcol[(size_t)i] >= 0) { snprintf(msg, sizeof msg, "%s: row %d holds the pivots of columns %d and %d", who, i, rowcol[(size_t)i], j); throw EngineError(msg); }
+            rowcol[(size_t)i] = j;
+            colrow[(size_t)j] = i;
+        }
+    }
+
+    // diagonals and in-degrees of the pivot graph (edge i -> k: row i has an entry on c(k), k != i)
+    std::vector<int> dg((size_t)n, 0), indeg((size_t)n, 0);
+    int badcol = -1;
+#pragma omp parallel for schedule(dynamic, 1024)
+    for (int i = 0; i < n; i++) {
+        if (rowcol[(size_t)i] < 0) continue;
+        int64_t d = 0;
+        for (i64 e = Tp[i]; e < Tp[i + 1]; e++) {
+            const int j = Tj[e];
+            if (j < 0 || j >= m) {
+#pragma omp atomic write
+                badcol = i;
+                continue;
+            }
+            const int k = colrow[(size_t)j];
+            if (k == i) d += Tx[e];
+            else if (k >= 0) {
+#pragma omp atomic
+                indeg[(size_t)k]++;
+            }
+        }
+        dg[(size_t)i] = zp_reduce(F, d);
+    }
+    if (badcol >= 0) { snprintf(msg, sizeof msg, "%s: row %d has a column index out of range", who, badcol); throw EngineError(msg); }
+    int npart = 0;
+    for (int i = 0; i < n; i++) {
+        if (rowcol[(size_t)i] < 0) continue;
+        npart++;
+        if (kind == 0 && dg[(size_t)i] != 1) {
+            snprintf(msg, sizeof msg, "%s: the pivot of row %d (column %d) is %d, not 1", who, i, rowcol[(size_t)i], dg[(size_t)i]);
+            throw EngineError(msg);
+        }
+        if (kind == 1 && dg[(size_t)i] == 0) {
+            snprintf(msg, sizeof msg, "%s: the diagonal entry of row %d (column %d) is zero", who, i, rowcol[(size_t)i]);
+            throw EngineError(msg);
+        }
+    }
+    op->npart = npart;
+
+    // levels, frontier by frontier (Kahn): the positions are the rows in level order, by row inside a level
+    std::vector<int> order, lvl_end;
+    order.reserve((size_t)npart);
+    for (int i = 0; i < n; i++)
+        if (rowcol[(size_t)i] >= 0 && indeg[(size_t)i] == 0) order.push_back(i);
+    size_t head = 0;
+    while (head < order.size()) {
+        const size_t end = order.size();
+        lvl_end.push_back((int)end);
+        for (size_t q = head; q < end; q++) {
+            const int i = order[q];
+            for (i64 e = Tp[i]; e < Tp[i + 1]; e++) {
+                const int k = colrow[(size_t)Tj[e]];
+                if (k >= 0 && k != i && --indeg[(size_t)k] == 0) order.push_back(k);
+            }
+        }
+        std::sort(order.begin() + (i64)end, order.end());
+        head = end;
+    }
+    if ((int)order.size() != npart) {
+        int on = -1;
+        for (int i = 0; i < n && on < 0; i++)
+            if (rowcol[(size_t)i] >= 0 && indeg[(size_t)i] > 0) on = i;
+        snprintf(msg, sizeof msg, "%s: the pivot graph has a cycle (row %d waits on itself through other rows)", who, on);
+        throw EngineError(msg);
+    }
+    op->nlevels = (int)lvl_end.size();
+
+    // panels: a wide level alone, narrower levels in chunks of at most TRS_CHUNK positions (a level may straddle two chunks)
+    std::vector<int> hsteps;
+    {
+        TrsPanel cur;
+        auto close = [&]() {
+            if (cur.cnt == 0) return;
+            cur.step_off = (i64)hsteps.size() - cur.nsteps;
+            op->panels.push_back(cur);
+            op->nchunk++;
+            cur = TrsPanel();
+        };
+        int lb = 0;
+        for (int le : lvl_end) {
+            if (le - lb >= TRS_WIDE) {
+                close();
+                TrsPanel P;
+                P.beg = lb;
+                P.cnt = le - lb;
+                P.wide = true;
+                op->panels.push_back(P);
+                op->nwide++;
+            } else {
+                for (int q = lb; q < le;) {
+                    if (cur.cnt == 0) cur.beg = q;
+                    const int take = std::min(le - q, TRS_CHUNK - cur.cnt);
+                    cur.cnt += take;
+                    cur.nsteps++;
+                    hsteps.push_back(cur.cnt);
+                    q += take;
+                    if (cur.cnt == TRS_CHUNK) close();
+                }
+            }
+            lb = le;
+        }
+        close();
+    }
+    const int npan = (int)op->panels.size();
+    std::vector<int> pos_of((size_t)n, -1), panel_of((size_t)npart, 0), hpcol((size_t)npart), hdinv((size_t)npart);
+    for (int a = 0; a < npart; a++) {
+        const int i = order[(size_t)a];
+        pos_of[(size_t)i] = a;
+        hpcol[(size_t)a] = rowcol[(size_t)i];
+        hdinv[(size_t)a] = kind == 0 ? 1 : zp_inverse(F, dg[(size_t)i]);
+    }
+    i64 ndiag = 0;
+    for (int P = 0; P < npan; P++) {
+        TrsPanel &Q = op->panels[(size_t)P];
+        for (int a = Q.beg; a < Q.beg + Q.cnt; a++) panel_of[(size_t)a] = P;
+        if (!Q.wide && Q.nsteps > 1) {
+            Q.diag_off = ndiag;
+            ndiag += (i64)Q.cnt * Q.cnt;
+        }
+    }
+
+    // gathered copies.  Entries of row pos a on column j: no pivot on j -> the residual's column j; the own pivot -> (the diagonal);
+    // the pivot of a position t of the same chunk -> its diagonal block; of a later panel -> the push of a's panel, target t.
+    std::vector<i64> rcnt((size_t)m + 1, 0);
+    std::vector<i64> pent((size_t)npan, 0);
+    std::vector<int> pdesc((size_t)npan, 0);
+#pragma omp parallel
+    {
+        std::vector<int> cnt((size_t)npart, 0), touched;
+#pragma omp for schedule(dynamic, 1)
+        for (int P = 0; P < npan; P++) {
+            const TrsPanel &Q = op->panels[(size_t)P];
+            i64 ne = 0;
+            touched.clear();
+            for (int a = Q.beg; a < Q.beg + Q.cnt; a++) {
+                const int i = order[(size_t)a];
+                for (i64 e = Tp[i]; e < Tp[i + 1]; e++) {
+                    const int j = Tj[e];
+                    const int k = colrow[(size_t)j];
+                    if (k < 0) {
+#pragma omp atomic
+                        rcnt[(size_t)j + 1]++;
+                    } else if (k != i) {
+                        const int t = pos_of[(size_t)k];
+                        if (panel_of[(size_t)t] == P) continue;
+                        ne++;
+                        if (cnt[(size_t)t]++ == 0) touched.push_back(t);
+                    }
+                }
+            }
+            for (int t : touched) cnt[(size_t)t] = 0;
+            pent[(size_t)P] = ne;
+            pdesc[(size_t)P] = (int)touched.size();
+        }
+    }
+    i64 nent = 0, ndesc = 0;
+    for (int P = 0; P < npan; P++) {
+        TrsPanel &Q = op->panels[(size_t)P];
+        Q.desc_off = ndesc;
+        Q.ndesc = pdesc[(size_t)P];
+        Q.nent = pent[(size_t)P];
+        Q.long_team = Q.ndesc > 0 && Q.nent > (i64)32 * Q.ndesc;
+        ndesc += Q.ndesc;
+        nent += Q.nent;
+    }
+    for (int j = 0; j < m; j++) rcnt[(size_t)j + 1] += rcnt[(size_t)j];
+    const i64 nres = m > 0 ? rcnt[(size_t)m] : 0;
+    op->res_long = m > 0 && nres > (i64)32 * m;
+    std::vector<int2> hgent((size_t)std::max<i64>(nent, 1)), hrent((size_t)std::max<i64>(nres, 1));
+    std::vector<int> hdtgt((size_t)std::max<i64>(ndesc, 1)), hdlen((size_t)std::max<i64>(ndesc, 1)), hdiag((size_t)std::max<i64>(ndiag, 1), 0);
+    std::vector<i64d> hdstart((size_t)std::max<i64>(ndesc, 1));
+    std::vector<i64> rcur(rcnt.begin(), rcnt.end());
+    i64 eoff = 0;
+    std::vector<i64> pent_off((size_t)npan, 0);
+    for (int P = 0; P < npan; P++) {
+        pent_off[(size_t)P] = eoff;
+        eoff += op->panels[(size_t)P].nent;
+    }
+#pragma omp parallel
+    {
+        std::vector<int> cnt((size_t)npart, 0), touched;
+        std::vector<i64> cur;
+#pragma omp for schedule(dynamic, 1)
+        for (int P = 0; P < npan; P++) {
+            const TrsPanel &Q = op->panels[(size_t)P];
+            touched.clear();
+            for (int a = Q.beg; a < Q.beg + Q.cnt; a++) {
+                const int i = order[(size_t)a];
+                for (i64 e = Tp[i]; e < Tp[i + 1]; e++) {
+                    const int k = colrow[(size_t)Tj[e]];
+                    if (k < 0 || k == i) continue;
+                    const int t = pos_of[(size_t)k];
+                    if (panel_of[(size_t)t] == P) continue;
+                    if (cnt[(size_t)t]++ == 0) touched.push_back(t);
+                }
+            }
+            std::sort(touched.begin(), touched.end());
+            // descriptors in target order; cnt[t] becomes the fill cursor of target t
+            i64 o = pent_off[(size_t)P];
+            for (size_t q = 0; q < touched.size(); q++) {
+                const int t = touched[q];
+                const size_t d = (size_t)(Q.desc_off + (i64)q);
+                hdtgt[d] = t;
+                hdstart[d] = o;
+                hdlen[d] = cnt[(size_t)t];
+                o += cnt[(size_t)t];
+                cnt[(size_t)t] = (int)q;
+            }
+            cur.assign(touched.size(), 0);
+            for (int a = Q.beg; a < Q.beg + Q.cnt; a++) {
+                const int i = order[(size_t)a];
+                for (i64 e = Tp[i]; e < Tp[i + 1]; e++) {
+                    const int j = Tj[e];
+                    const int k = colrow[(size_t)j];
+                    const int v = zp_reduce(F, (int64_t)Tx[e]);
+                    if (k < 0) {
+                        i64 slot;
+#pragma omp atomic capture
+                        slot = rcur[(size_t)j]++;
+                        hrent[(size_t)slot] = make_int2(a, v);
+                    } else if (k != i) {
+                        const int t = pos_of[(size_t)k];
+                        if (panel_of[(size_t)t] == P) {
+                            if (Q.nsteps > 1) {
+                                int &dd = hdiag[(size_t)(Q.diag_off + (i64)(a - Q.beg) * Q.cnt + (t - Q.beg))];
+                                dd = zp_add(F, dd, v);
+                            }
+                            continue;
+                        }
+                        const int q = cnt[(size_t)t];
+                        const size_t d = (size_t)(Q.desc_off + (i64)q);
+                        hgent[(size_t)(hdstart[d] + cur[(size_t)q]++)] = make_int2(a, v);
+                    }
+                }
+            }
+            for (int t : touched) cnt[(size_t)t] = 0;
+        }
+    }
+    op->stored = nent + nres + ndiag;
+
+    hipStream_t s = nullptr;
+    auto up = [&](auto &d, const auto &h) {
+        d.alloc(h.size());
+        if (!h.empty()) HIPCHK(hipMemcpyAsync(d.p, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice, s));
+    };
+    std::vector<int> hcolpos((size_t)m, -1);
+    for (int a = 0; a < npart; a++) hcolpos[(size_t)hpcol[(size_t)a]] = a;
+    std::vector<i64d> hrstart(rcnt.begin(), rcnt.end());
+    up(op->pcol, hpcol);
+    up(op->pdinv, hdinv);
+    up(op->rowpos, pos_of);
+    up(op->colpos, hcolpos);
+    up(op->steps, hsteps);
+    up(op->diag, hdiag);
+    up(op->dtgt, hdtgt);
+    up(op->dlen, hdlen);
+    up(op->dstart, hdstart);
+    up(op->rstart, hrstart);
+    up(op->gent, hgent);
+    up(op->rent, hrent);
+    HIPCHK(hipStreamSynchronize(s)); // the host vectors go out of scope
+    return op.release();
+}
+
+void trsolve_check(const spasm_amd_trsolve *op, int k, const void *B, i64 ldb, const void *X, i64 ldx, const void *ok, const char *who)
+{
+    if (!op) throw EngineError(std::string(who) + ": NULL operator");
+    if (k < 0 || ldb < k || ldx < k) throw EngineError(std::string(who) + ": bad arguments (k >= 0, ldb >= k, ldx >= k)");
+    if (k > 0 && ((op->m > 0 && !B) || (op->n > 0 && !X) || !ok)) throw EngineError(std::string(who) + ": NULL array");
+}
+
+// the error text names the entry point once
+void trsolve_error(const char *who, const std::exception &e)
+{
+    const size_t l = strlen(who);
+    if (strncmp(e.what(), who, l) == 0) spasm_set_error("%s", e.what());
+    else spasm_set_error("%s: %s", who, e.what());
+}
+
+// spasm_dense_forward_solve / spasm_dense_back_solve: a temporary operator, one right-hand side
+bool trsolve_once(const struct spasm_csr *T, spasm_ZZp *b, spasm_ZZp *x, const int *piv, int kind, const char *who)
+{
+    spasm_clear_error();
+    try {
+        std::unique_ptr<spasm_amd_trsolve> op(trsolve_create(T, piv, kind, who));
+        unsigned char ok = 0;
+        trsolve_check(op.get(), 1, b, 1, x, 1, &ok, who);
+        op->apply_host(1, b, 1, x, 1, &ok);
+        return ok != 0;
+    } catch (const std::exception &e) {
+        trsolve_error(who, e);
+        return false;
+    }
+}
+
+} // namespace
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -6699,6 +7171,75 @@ SPASM_API int spasm_amd_spmv_apply_dev(spasm_amd_spmv *op, int trans, int k, con
 }
 
 SPASM_API void spasm_amd_spmv_free(spasm_amd_spmv *op)
+{
+    if (!op) return;
+    DeviceGuard g;
+    (void)hipSetDevice(op->dev);
+    delete op;
+}
+
+// reference src/SpaSM.jl:663-692 (dense_back_solve, dense_forward_solve): host arrays; on an error b and x are left as they were
+SPASM_API bool spasm_dense_forward_solve(const struct spasm_csr *U, spasm_ZZp *b, spasm_ZZp *x, const int *q)
+{
+    return trsolve_once(U, b, x, q, 0, "spasm_dense_forward_solve");
+}
+
+SPASM_API bool spasm_dense_back_solve(const struct spasm_csr *L, spasm_ZZp *b, spasm_ZZp *x, const int *p)
+{
+    return trsolve_once(L, b, x, p, 1, "spasm_dense_back_solve");
+}
+
+SPASM_API spasm_amd_trsolve *spasm_amd_trsolve_create(const struct spasm_csr *T, const int *piv, int kind)
+{
+    spasm_clear_error();
+    try {
+        return trsolve_create(T, piv, kind, "spasm_amd_trsolve_create");
+    } catch (const std::exception &e) {
+        trsolve_error("spasm_amd_trsolve_create", e);
+        return nullptr;
+    }
+}
+
+SPASM_API int spasm_amd_trsolve_apply(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok)
+{
+    spasm_clear_error();
+    try {
+        trsolve_check(op, k, B, ldb, X, ldx, ok, "spasm_amd_trsolve_apply");
+        DeviceGuard g;
+        HIPCHK(hipSetDevice(op->dev));
+        op->apply_host(k, B, ldb, X, ldx, ok);
+        return 0;
+    } catch (const std::exception &e) {
+        trsolve_error("spasm_amd_trsolve_apply", e);
+        return -1;
+    }
+}
+
+SPASM_API int spasm_amd_trsolve_apply_dev(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream)
+{
+    spasm_clear_error();
+    try {
+        trsolve_check(op, k, B, ldb, X, ldx, ok, "spasm_amd_trsolve_apply_dev");
+        DeviceGuard g;
+        HIPCHK(hipSetDevice(op->dev));
+        hipStream_t s = (hipStream_t)stream;
+        if (k > 0) op->apply_dev(k, B, ldb, X, ldx, ok, s);
+        if (!stream) HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    } catch (const std::exception &e) {
+        trsolve_error("spasm_amd_trsolve_apply_dev", e);
+        return -1;
+    }
+}
+
+SPASM_API void spasm_amd_trsolve_stats(const spasm_amd_trsolve *op, i64 *out)
+{
+    if (!op || !out) return;
+    const i64 v[8] = {op->n, op->m, op->npart, op->nlevels, op->nwide, op->nchunk, op->launches(), op->stored};
+    memcpy(out, v, sizeof v);
+}
+
+SPASM_API void spasm_amd_trsolve_free(spasm_amd_trsolve *op)
 {
     if (!op) return;
     DeviceGuard g;
