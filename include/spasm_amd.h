@@ -258,6 +258,53 @@ void spasm_amd_trsolve_free(spasm_amd_trsolve *op);
 
 /* ---- spasm_transpose.c ---- */
 struct spasm_csr *spasm_transpose(const struct spasm_csr *A);        /* src/SpaSM.jl:589 (one-argument form) */
+/* src/SpaSM.jl:597 (submatrix, and the range forms of getindex at :594-603): rows [r0, r1), columns [c0, c1) of A as an
+ * (r1 - r0) x (c1 - c0) matrix over the same field, columns renumbered from c0, the entries of each row in their stored order (a
+ * copy, no sort); x == NULL when with_values is false.  Host-side, O(entries of the rows), needs no device.  A range that is
+ * inverted or leaves the matrix: NULL, spasm_amd_last_error() says why. */
+struct spasm_csr *spasm_submatrix(const struct spasm_csr *A, int r0, int r1, int c0, int c1, bool with_values);
+
+/* ---- Engine extension: sparse matrix algebra over GF(p) on the device (csrc/spgemm.hpp) ----
+ * What SpaSM.jl offers on CSR through SparseMatrixCSC on the host (src/SpaSM.jl:995-1004: a * b, a + b, a - b, -a, scalar * a) and
+ * submatrix, on matrices that stay on the device: spasm_amd_dcsr is an n x m matrix over GF(p) resident there, every operation
+ * returns a new handle and leaves its operands as they are, so chains of operations do not cross the host.
+ *   upload     A may be freed afterwards; A->x must not be NULL; rows need not be sorted and may hold duplicate columns (they
+ *              are summed), explicit zeros and any int32 as a value (reduced like the values of A elsewhere)
+ *   download   a host CSR the caller frees with spasm_csr_free
+ *   info       out[4] = n, m, stored entries, prime
+ *   mul        A (n x k) * B (k x m)
+ *   lincomb    a * A + b * B for any i64 a, b (reduced mod p); B == NULL: a * A.  lincomb(1, A, 0, NULL) is the canonical form of A
+ *   submatrix  rows [r0, r1), columns [c0, c1), columns renumbered from c0
+ *   equal      1 when A and B are the same matrix over the same field (canonical forms are compared; an upload is brought to
+ *              canonical form first), 0 when not, < 0 on error
+ *   stats      of the operation that made D (all 0 for an upload): out[12] = products (sum over the rows of their bound), entries
+ *              written, rows through the tiny / the LDS hash / the global-memory path, chunks of rows, device microseconds of the
+ *              size / numeric / compact steps (HIP events), peak scratch bytes, operation (1 mul, 2 lincomb, 3 submatrix),
+ *              largest bound of a row
+ * CONTRACT of every result (mul, lincomb, submatrix, and the one-shot forms below):
+ *   exact          every entry is the true value modulo p as a balanced residue in [mhalfp, halfp], for every prime the engine
+ *                  accepts (3 .. 0xFFFFFFFB) and any number of terms per entry
+ *   canonical      inside each row the columns ascend, no stored entry is zero (terms that cancel mod p are dropped), and after
+ *                  download nzmax == nnz == p[n]
+ *   deterministic  two runs give byte-identical p, j, x
+ *   errors         a NULL argument, inner dimensions or primes that differ, A->x == NULL, a column index or a range outside the
+ *                  matrix, no device ("no HIP device"), out of device memory: NULL (or < 0), operands untouched,
+ *                  spasm_amd_last_error() says why; after success the text is empty.
+ * One operation at a time per handle as a result; handles may be shared as operands. */
+typedef struct spasm_amd_dcsr spasm_amd_dcsr;
+spasm_amd_dcsr *spasm_amd_dcsr_upload(const struct spasm_csr *A);
+struct spasm_csr *spasm_amd_dcsr_download(const spasm_amd_dcsr *D);
+void spasm_amd_dcsr_info(const spasm_amd_dcsr *D, i64 *out);
+void spasm_amd_dcsr_free(spasm_amd_dcsr *D);
+spasm_amd_dcsr *spasm_amd_dcsr_mul(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B);
+spasm_amd_dcsr *spasm_amd_dcsr_lincomb(i64 a, const spasm_amd_dcsr *A, i64 b, const spasm_amd_dcsr *B);
+spasm_amd_dcsr *spasm_amd_dcsr_submatrix(const spasm_amd_dcsr *A, int r0, int r1, int c0, int c1);
+int spasm_amd_dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B);
+void spasm_amd_dcsr_stats(const spasm_amd_dcsr *D, i64 *out);
+/* one-shot forms on host matrices: upload, operate, download */
+struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B);
+struct spasm_csr *spasm_amd_csr_lincomb(i64 a, const struct spasm_csr *A, i64 b, const struct spasm_csr *B);
+
 
 /* ---- spasm_echelonize.c / spasm_kernel.c : THE hot path ---- */
 void spasm_echelonize_init_opts(struct echelonize_opts *opts);       /* src/SpaSM.jl:817 */

@@ -7,6 +7,7 @@ from . import _abi, blocks
 from .blocks import Block
 from .api import (
     CSR,
+    DeviceCSR,
     LU,
     EchelonizeOpts,
     Field,
@@ -41,6 +42,7 @@ from .api import (
     sparse,
     sparse_triangular_solve,
     sparse_triangular_solve_row,
+    submatrix,
     synth_csr,
     transpose,
     xapy,
@@ -50,4 +52,5 @@ __all__ = [
     "Block", "blocks", "CSR", "LU", "Triplet", "load", "save", "EchelonizeOpts", "Field", "SpasmError", "ZZp", "balanced", "RankCertificate", "certificate_rank_create", "certificate_rank_verify", "rank_certificate_save", "rank_certificate_load", "echelonize", "echelonize_multi", "factorization_verify", "gesv", "solve", "kernel",
     "last_rounds", "nnz", "prime0", "rank", "rref", "sparse", "sparse_triangular_solve", "sparse_triangular_solve_row", "scatter", "synth_csr", "transpose",
     "axpy", "xapy", "SpMV", "dense_forward_solve", "dense_back_solve", "TriangularSolver",
+    "DeviceCSR", "submatrix",
 ]

@@ -249,6 +249,18 @@ SIGNATURES = {
     "spasm_amd_spmv_apply": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]),
     "spasm_amd_spmv_apply_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_spmv_free": (None, [C.c_void_p]),
+    "spasm_submatrix": (_P(CsrStruct), [_P(CsrStruct), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_bool]),
+    "spasm_amd_dcsr_upload": (C.c_void_p, [_P(CsrStruct)]),
+    "spasm_amd_dcsr_download": (_P(CsrStruct), [C.c_void_p]),
+    "spasm_amd_dcsr_info": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_dcsr_free": (None, [C.c_void_p]),
+    "spasm_amd_dcsr_mul": (C.c_void_p, [C.c_void_p, C.c_void_p]),
+    "spasm_amd_dcsr_lincomb": (C.c_void_p, [C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_dcsr_submatrix": (C.c_void_p, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "spasm_amd_dcsr_equal": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "spasm_amd_dcsr_stats": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_csr_mul": (_P(CsrStruct), [_P(CsrStruct), _P(CsrStruct)]),
+    "spasm_amd_csr_lincomb": (_P(CsrStruct), [C.c_int64, _P(CsrStruct), C.c_int64, _P(CsrStruct)]),
     "spasm_dense_forward_solve": (C.c_bool, [_P(CsrStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spasm_dense_back_solve": (C.c_bool, [_P(CsrStruct), C.c_void_p, C.c_void_p, C.c_void_p]),
     "spasm_amd_trsolve_create": (C.c_void_p, [_P(CsrStruct), C.c_void_p, C.c_int32]),

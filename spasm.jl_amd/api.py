@@ -211,8 +211,40 @@ class CSR:
 
     def __matmul__(self, x):
         """A @ x (reference src/SpaSM.jl:658, A * x): x of shape (m,) or (m, k), integers (reduced mod p); a new int32 array of
-        shape (n,) or (n, k)."""
+        shape (n,) or (n, k).  A @ B with B a CSR (reference src/SpaSM.jl:995): the product as a new CSR in canonical form."""
+        if isinstance(x, CSR):
+            return _csr_mul(self, x)
         return _product(self, x, trans=False)
+
+    # Matrix algebra (reference src/SpaSM.jl:995-1004), on the device (csrc/spgemm.hpp); results are canonical: columns ascending
+    # inside each row, no zero stored.  `==` stays identity: equality as matrices is equals().
+    def __add__(self, other):
+        return _csr_lincomb(1, self, 1, other)
+
+    def __sub__(self, other):
+        return _csr_lincomb(1, self, -1, other)
+
+    def __neg__(self):
+        return _csr_lincomb(-1, self, 0, None)
+
+    def __mul__(self, a):
+        return _csr_lincomb(_int_scalar(a), self, 0, None)
+
+    __rmul__ = __mul__
+
+    def equals(self, other):
+        """True when both are the same matrix over the same field, whatever the order of the stored entries."""
+        if not isinstance(other, CSR):
+            raise TypeError("a CSR expected")
+        if self.shape != other.shape or self.prime != other.prime:
+            return False
+        with DeviceCSR(self) as a, DeviceCSR(other) as b:
+            return a.equals(b)
+
+    def __getitem__(self, key):
+        """A[r0:r1, c0:c1] (reference src/SpaSM.jl:594-603): spasm_submatrix on the host, stored order kept."""
+        rows, cols = _slice_pair(key, self.shape)
+        return submatrix(self, rows, cols)
 
     def __rmatmul__(self, x):
         """x @ A (reference src/SpaSM.jl:645, x * A): x of shape (n,) or (k, n), integers (reduced mod p); a new int32 array of
@@ -420,6 +452,201 @@ def _rows_view(a, name):
     if a.strides[1] != 4 or (a.shape[0] > 1 and a.strides[0] < 4 * a.shape[1]) or a.strides[0] % 4:
         raise ValueError(f"{name} must have unit stride along its rows")
     return a
+
+
+# ---------------------------------------------------------------------------------------------
+# Matrix algebra: A B, a A + b B, submatrix  (reference src/SpaSM.jl:594-603, :995-1004; csrc/spgemm.hpp)
+# ---------------------------------------------------------------------------------------------
+def _int_scalar(a):
+    if isinstance(a, (bool, np.bool_)) or not isinstance(a, (int, np.integer)):
+        raise TypeError("an integer scalar expected")
+    a = int(a)
+    if not -(2**63) <= a < 2**63:
+        raise ValueError("the scalar must fit 64 bits")
+    return a
+
+
+def _same_field(A, B):
+    if A.prime != B.prime:
+        raise ValueError(f"the matrices are over different primes: {A.prime} and {B.prime}")
+
+
+def _slice_pair(key, shape):
+    """(rows, cols) as ranges from A[r, c] with step-1 slices"""
+    if not isinstance(key, tuple) or len(key) != 2:
+        raise TypeError("two slices expected: A[r0:r1, c0:c1]")
+    out = []
+    for k, size in zip(key, shape):
+        if not isinstance(k, slice):
+            raise TypeError("slices expected: A[r0:r1, c0:c1]")
+        if k.step not in (None, 1):
+            raise ValueError("slices with a step are not supported")
+        lo, hi, _ = k.indices(size)
+        out.append(range(lo, max(hi, lo)))
+    return out[0], out[1]
+
+
+def _range_bounds(r, name):
+    if isinstance(r, slice):
+        raise TypeError(f"{name} must be a range")
+    r = range(*r) if isinstance(r, tuple) else r
+    if not isinstance(r, range):
+        raise TypeError(f"{name} must be a range")
+    if r.step != 1:
+        raise ValueError("ranges with a step are not supported")
+    return r.start, r.stop  # (an inverted or outside range is the library's to refuse)
+
+
+def submatrix(A, rows, cols, with_values=True):
+    """submatrix(A, r, c, with_values) (reference src/SpaSM.jl:594-597) with Python ranges: rows and columns of A as a new CSR,
+    columns renumbered from cols.start, the entries of each row in their stored order; without values x is NULL.  Host-side."""
+    r0, r1 = _range_bounds(rows, "rows")
+    c0, c1 = _range_bounds(cols, "cols")
+    ptr = _abi.lib().spasm_submatrix(A.data, r0, r1, c0, c1, bool(with_values))
+    if not ptr:
+        raise SpasmError(_abi.last_error() or "spasm_submatrix failed")
+    return CSR(ptr)
+
+
+def _csr_mul(A, B):
+    if A.m != B.n:
+        raise ValueError(f"dimension mismatch: {A.shape} times {B.shape}")
+    _same_field(A, B)
+    ptr = _abi.lib().spasm_amd_csr_mul(A.data, B.data)
+    if not ptr:
+        raise SpasmError(_abi.last_error() or "spasm_amd_csr_mul failed")
+    return CSR(ptr)
+
+
+def _csr_lincomb(a, A, b, B):
+    if B is not None:
+        if not isinstance(B, CSR):
+            raise TypeError("a CSR expected")
+        if A.shape != B.shape:
+            raise ValueError(f"dimension mismatch: {A.shape} and {B.shape}")
+        _same_field(A, B)
+    ptr = _abi.lib().spasm_amd_csr_lincomb(_int_scalar(a), A.data, _int_scalar(b), B.data if B is not None else None)
+    if not ptr:
+        raise SpasmError(_abi.last_error() or "spasm_amd_csr_lincomb failed")
+    return CSR(ptr)
+
+
+class DeviceCSR:
+    """An n x m matrix over GF(p) resident on the device (spasm_amd_dcsr_*; engine extension).  DeviceCSR(A) uploads the CSR A,
+    which may be dropped afterwards.  D1 @ D2, D1 + D2, D1 - D2, -D, a * D, D * a (Python int), D[r0:r1, c0:c1] make new resident
+    matrices in canonical form (columns ascending inside each row, no zero stored) without crossing the host; download() gives
+    a CSR; equals() compares as matrices; stats() describes the operation that made the matrix."""
+
+    STATS = ("flops", "entries", "rows_tiny", "rows_hash", "rows_global", "chunks", "ms_size", "ms_numeric", "ms_compact", "scratch_bytes", "op", "max_bound")
+
+    def __init__(self, A, _handle=None):
+        if _handle is not None:
+            self._h = _handle
+        else:
+            if not isinstance(A, CSR):
+                raise TypeError("a CSR expected")
+            self._h = _abi.lib().spasm_amd_dcsr_upload(A.data)
+            if not self._h:
+                raise SpasmError(_abi.last_error() or "spasm_amd_dcsr_upload failed")
+        out = (C.c_int64 * 4)()
+        _abi.lib().spasm_amd_dcsr_info(self._h, out)
+        self.shape = (int(out[0]), int(out[1]))
+        self.nnz = int(out[2])
+        self.prime = int(out[3])
+
+    @classmethod
+    def _wrap(cls, handle, who):
+        if not handle:
+            raise SpasmError(_abi.last_error() or f"{who} failed")
+        return cls(None, _handle=handle)
+
+    def _need(self):
+        if not getattr(self, "_h", None):
+            raise SpasmError("the matrix is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _abi.lib().spasm_amd_dcsr_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def download(self):
+        ptr = _abi.lib().spasm_amd_dcsr_download(self._need())
+        if not ptr:
+            raise SpasmError(_abi.last_error() or "spasm_amd_dcsr_download failed")
+        return CSR(ptr)
+
+    def stats(self):
+        out = (C.c_int64 * 12)()
+        _abi.lib().spasm_amd_dcsr_stats(self._need(), out)
+        d = {k: int(v) for k, v in zip(self.STATS, out)}
+        for k in ("ms_size", "ms_numeric", "ms_compact"):
+            d[k] = d[k] / 1000.0  # the library counts microseconds
+        return d
+
+    def _other(self, other):
+        if not isinstance(other, DeviceCSR):
+            raise TypeError("a DeviceCSR expected")
+        h = other._need()
+        _same_field(self, other)
+        return h
+
+    def __matmul__(self, other):
+        if not isinstance(other, DeviceCSR):
+            return NotImplemented
+        me, h = self._need(), self._other(other)
+        if self.shape[1] != other.shape[0]:
+            raise ValueError(f"dimension mismatch: {self.shape} times {other.shape}")
+        return DeviceCSR._wrap(_abi.lib().spasm_amd_dcsr_mul(me, h), "spasm_amd_dcsr_mul")
+
+    def lincomb(self, a, b=0, other=None):
+        """a * self + b * other (other None: a * self)"""
+        me, h = self._need(), None
+        if other is not None:
+            h = self._other(other)
+            if self.shape != other.shape:
+                raise ValueError(f"dimension mismatch: {self.shape} and {other.shape}")
+        return DeviceCSR._wrap(_abi.lib().spasm_amd_dcsr_lincomb(_int_scalar(a), me, _int_scalar(b), h), "spasm_amd_dcsr_lincomb")
+
+    def __add__(self, other):
+        return self.lincomb(1, 1, other) if isinstance(other, DeviceCSR) else NotImplemented
+
+    def __sub__(self, other):
+        return self.lincomb(1, -1, other) if isinstance(other, DeviceCSR) else NotImplemented
+
+    def __neg__(self):
+        return self.lincomb(-1)
+
+    def __mul__(self, a):
+        return self.lincomb(_int_scalar(a))
+
+    __rmul__ = __mul__
+
+    def __getitem__(self, key):
+        me = self._need()
+        rows, cols = _slice_pair(key, self.shape)
+        return DeviceCSR._wrap(_abi.lib().spasm_amd_dcsr_submatrix(me, rows.start, rows.stop, cols.start, cols.stop), "spasm_amd_dcsr_submatrix")
+
+    def equals(self, other):
+        if not isinstance(other, DeviceCSR):
+            raise TypeError("a DeviceCSR expected")
+        rc = _abi.lib().spasm_amd_dcsr_equal(self._need(), other._need())
+        if rc < 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_dcsr_equal failed")
+        return bool(rc)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -119,6 +119,36 @@ SPASM_API void spasm_csr_free(struct spasm_csr *A) // reference src/SpaSM.jl:451
     free(A->p); free(A->j); free(A->x); free(A);
 }
 
+// reference src/SpaSM.jl:597 (submatrix; getindex with ranges :594-603): a copy of the rows [r0, r1) restricted to the columns
+// [c0, c1), entries in their stored order
+SPASM_API struct spasm_csr *spasm_submatrix(const struct spasm_csr *A, int r0, int r1, int c0, int c1, bool with_values)
+{
+    spasm_clear_error();
+    if (!A) { spasm_set_error("spasm_submatrix: NULL matrix"); return nullptr; }
+    if (r0 < 0 || r1 < r0 || r1 > A->n || c0 < 0 || c1 < c0 || c1 > A->m) {
+        spasm_set_error("spasm_submatrix: range [%d, %d) x [%d, %d) outside the %d x %d matrix", r0, r1, c0, c1, A->n, A->m);
+        return nullptr;
+    }
+    if (with_values && !A->x) { spasm_set_error("spasm_submatrix: matrix without values (A->x == NULL)"); return nullptr; }
+    i64 nz = 0;
+    for (i64 k = A->p[r0]; k < A->p[r1]; k++) nz += (A->j[k] >= c0 && A->j[k] < c1) ? 1 : 0;
+    struct spasm_csr *B = spasm_csr_alloc(r1 - r0, c1 - c0, nz, A->field->p, with_values);
+    if (!B) return nullptr;
+    i64 at = 0;
+    for (int i = r0; i < r1; i++) {
+        B->p[i - r0] = at;
+        for (i64 k = A->p[i]; k < A->p[i + 1]; k++) {
+            const int j = A->j[k];
+            if (j < c0 || j >= c1) continue;
+            B->j[at] = j - c0;
+            if (with_values) B->x[at] = A->x[k];
+            at++;
+        }
+    }
+    B->p[r1 - r0] = at;
+    return B;
+}
+
 SPASM_API void spasm_lu_free(struct spasm_lu *N) // reference src/SpaSM.jl:463; U/L are wrapped own=false (:289,:292)
 {
     if (!N) return;

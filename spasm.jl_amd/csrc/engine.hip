@@ -12,6 +12,7 @@
 #include "greedy.hpp"
 #include "dense.hpp"
 #include "spmv.hpp"
+#include "spgemm.hpp"
 #include "trsolve.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
@@ -6035,6 +6036,462 @@ void spmv_once(const struct spasm_csr *A, int trans, const spasm_ZZp *x, spasm_Z
 } // namespace
 
 // ------------------------------------------------------------------------------------------------
+// Sparse matrix algebra on resident matrices (spgemm.hpp): products, linear combinations, submatrices.  A handle owns the row
+// pointers and the packed {column, value} entries of one matrix; every operation makes a new handle in canonical form.
+// ------------------------------------------------------------------------------------------------
+struct spasm_amd_dcsr {
+    int dev = 0;
+    int n = 0, m = 0;
+    i64 nnz = 0;
+    ZpField F;
+    bool canonical = false;  // rows sorted, no duplicate column, no zero: true for every result, unknown for an upload
+    DevBuf<i64d> p;          // n + 1
+    DevBuf<int2> ent;        // nnz
+    i64 stats[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+};
+
+namespace {
+
+template <int LOGT, int BS, bool SMALL> void spg_launch_hash(const SpgArgs &a, int nitems, const int *items, hipStream_t s)
+{
+    constexpr size_t lds = spg_hash_lds<SMALL>(LOGT, BS);
+    static bool attr_done[kMaxDev] = {false};
+    bool &done = attr_done[current_device()];
+    if (!done) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_spg_hash<LOGT, BS, SMALL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    hipLaunchKernelGGL((k_spg_hash<LOGT, BS, SMALL>), dim3(nitems), dim3(BS), lds, s, a, nitems, items);
+}
+
+template <bool SMALL> void spg_launch_class(int cls, const SpgArgs &a, int nitems, const int *items, hipStream_t s)
+{
+    switch (cls) {
+    case 0: hipLaunchKernelGGL((k_spg_tiny<SMALL>), dim3(cdiv(nitems, 256 / SPG_TINY_TEAM)), dim3(256), 0, s, a, nitems, items); break;
+    case 1: spg_launch_hash<7, 64, SMALL>(a, nitems, items, s); break;
+    case 2: spg_launch_hash<8, 64, SMALL>(a, nitems, items, s); break;
+    case 3: spg_launch_hash<9, 64, SMALL>(a, nitems, items, s); break;
+    case 4: spg_launch_hash<10, 64, SMALL>(a, nitems, items, s); break;
+    case 5: spg_launch_hash<11, 256, SMALL>(a, nitems, items, s); break;
+    case 6: spg_launch_hash<12, 256, SMALL>(a, nitems, items, s); break;
+    case 7: spg_launch_hash<13, 256, SMALL>(a, nitems, items, s); break;
+    default: break;
+    }
+    HIPCHK(hipGetLastError());
+}
+
+struct SpgEvents {
+    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    SpgEvents() { for (auto &x : e) HIPCHK(hipEventCreate(&x)); }
+    ~SpgEvents() { for (auto &x : e) if (x) (void)hipEventDestroy(x); }
+    double ms(int a, int b)
+    {
+        float t = 0;
+        HIPCHK(hipEventElapsedTime(&t, e[a], e[b]));
+        return (double)t;
+    }
+};
+
+// bytes of scratch one chunk of rows may use: a third of the free device memory (SPASM_AMD_SPGEMM_SCRATCH_MB: a smaller figure,
+// for the tests of the chunked path)
+size_t spg_budget()
+{
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    size_t b = fr / 3;
+    const char *e = getenv("SPASM_AMD_SPGEMM_SCRATCH_MB");
+    if (e && atof(e) > 0) b = std::min(b, (size_t)(atof(e) * 1048576.0));
+    return b;
+}
+
+// C = op(A, B): the driver of the three steps of spgemm.hpp.  mode SPG_MUL: A (n x k) * B (k x m); SPG_LINCOMB: sa * A + sb * B (B may
+// be null); SPG_SUBMATRIX: A[r0:r1, c0:c1].  The operands have been checked by the caller.
+std::unique_ptr<spasm_amd_dcsr> spg_run(int mode, const spasm_amd_dcsr &A, const spasm_amd_dcsr *B, int sa, int sb, int r0, int r1, int c0, int c1)
+{
+    hipStream_t s = nullptr;
+    std::unique_ptr<spasm_amd_dcsr> R(new spasm_amd_dcsr());
+    R->dev = A.dev;
+    R->F = A.F;
+    R->canonical = true;
+    const int n = mode == SPG_SUBMATRIX ? r1 - r0 : A.n;
+    const int m = mode == SPG_MUL ? B->m : (mode == SPG_SUBMATRIX ? c1 - c0 : A.m);
+    R->n = n;
+    R->m = m;
+    R->p.alloc((size_t)n + 1);
+    R->stats[10] = mode;
+    if (n == 0 || m == 0) { // nothing to compute (and no accumulator of zero columns)
+        HIPCHK(hipMemsetAsync(R->p.p, 0, ((size_t)n + 1) * sizeof(i64d), s));
+        R->ent.alloc(1);
+        HIPCHK(hipStreamSynchronize(s));
+        return R;
+    }
+    int num_cu = 256;
+    {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, A.dev) == hipSuccess) num_cu = prop.multiProcessorCount;
+    }
+    SpgArgs a;
+    memset(&a, 0, sizeof a);
+    a.mode = mode;
+    a.nrows = n;
+    a.ncols = m;
+    a.Ap = A.p.p;
+    a.Aent = A.ent.p;
+    a.Bp = B ? B->p.p : nullptr;
+    a.Bent = B ? B->ent.p : nullptr;
+    a.sa = sa;
+    a.sb = sb;
+    a.r0 = mode == SPG_SUBMATRIX ? r0 : 0;
+    a.c0 = mode == SPG_SUBMATRIX ? c0 : 0;
+    a.c1 = mode == SPG_SUBMATRIX ? c1 : m;
+    a.F = A.F;
+
+    SpgEvents ev;
+    Scanner scan;
+    DevBuf<i64d> bound, cap, off, cnt, tmp;
+    const size_t n1 = (size_t)n + 1;
+    bound.alloc(n1);
+    cap.alloc(n1);
+    off.alloc(n1);
+    cnt.alloc(n1);
+    tmp.alloc(n1);
+    bound.zero(s);
+    cap.zero(s);
+    cnt.zero(s);
+    // ---- size
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    if (mode == SPG_MUL && A.nnz > 8 * (i64)A.n) hipLaunchKernelGGL(k_spg_size_wave, dim3(cdiv((i64)n * 64, 256)), dim3(256), 0, s, a, bound.p, cap.p);
+    else hipLaunchKernelGGL(k_spg_size, dim3(cdiv(n, 256)), dim3(256), 0, s, a, bound.p, cap.p);
+    HIPCHK(hipGetLastError());
+    scan.exclusive(cap.p, off.p, n1, s);
+    scan.exclusive(bound.p, tmp.p, n1, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    i64d total_cap = 0, flops = 0;
+    HIPCHK(hipMemcpyAsync(&total_cap, off.p + n, sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&flops, tmp.p + n, sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    double ms_size = ev.ms(0, 1), ms_num = 0, ms_compact = 0;
+    a.off = off.p;
+    a.cnt = cnt.p;
+
+    // ---- chunks of rows whose scratch slices fit the budget
+    const size_t budget = spg_budget();
+    const i64 max_ent = (i64)(budget / sizeof(int2));
+    std::vector<int> cut; // chunk c = rows cut[c] .. cut[c + 1] - 1
+    std::vector<i64d> hoff;
+    cut.push_back(0);
+    if (total_cap <= max_ent) {
+        cut.push_back(n);
+    } else {
+        hoff.resize(n1);
+        HIPCHK(hipMemcpy(hoff.data(), off.p, n1 * sizeof(i64d), hipMemcpyDeviceToHost));
+        int lo = 0;
+        while (lo < n) {
+            int hi = lo;
+            while (hi < n && hoff[(size_t)hi + 1] - hoff[(size_t)lo] <= max_ent) hi++;
+            if (hi == lo) {
+                char b[256];
+                snprintf(b, sizeof b, "row %d alone needs %.2f GiB of scratch, %.2f GiB may be used", lo,
+                         (double)(hoff[(size_t)lo + 1] - hoff[(size_t)lo]) * 8.0 / 1073741824.0, (double)budget / 1073741824.0);
+                throw EngineError(b);
+            }
+            cut.push_back(hi);
+            lo = hi;
+        }
+    }
+    const int nchunks = (int)cut.size() - 1;
+
+    DevBuf<unsigned char> key, key2, sort_tmp;
+    DevBuf<int> rowid, rowid2, hist;
+    DevBuf<i64d> maxb, pos;
+    DevBuf<int2> scratch;
+    DevBuf<long long> dense;
+    size_t dense_rows = 0;
+    hist.alloc(16);
+    maxb.alloc(1);
+    maxb.zero(s);
+    std::vector<DevBuf<int2>> parts((size_t)nchunks);
+    std::vector<i64> part_nnz((size_t)nchunks, 0);
+    i64 rows_path[3] = {0, 0, 0};
+    size_t peak = 0;
+    for (int c = 0; c < nchunks; c++) {
+        const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1], nc = hi - lo;
+        const i64d off_lo = nchunks == 1 ? 0 : hoff[(size_t)lo];
+        const i64d chunk_cap = nchunks == 1 ? total_cap : hoff[(size_t)hi] - off_lo;
+        key.ensure((size_t)nc);
+        key2.ensure((size_t)nc);
+        rowid.ensure((size_t)nc);
+        rowid2.ensure((size_t)nc);
+        pos.ensure((size_t)nc + 1);
+        scratch.ensure((size_t)chunk_cap + 1);
+        hist.zero(s);
+        hipLaunchKernelGGL(k_spg_classify, dim3(cdiv(nc, 256)), dim3(256), 0, s, lo, nc, bound.p, key.p, rowid.p, hist.p, maxb.p);
+        HIPCHK(hipGetLastError());
+        {
+            size_t bytes = 0;
+            HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key2.p, rowid.p, rowid2.p, (size_t)nc, 0, 4, s));
+            sort_tmp.ensure(bytes);
+            HIPCHK(rocprim::radix_sort_pairs(sort_tmp.p, bytes, key.p, key2.p, rowid.p, rowid2.p, (size_t)nc, 0, 4, s));
+        }
+        int h[16];
+        HIPCHK(hipMemcpyAsync(h, hist.p, sizeof h, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        a.off_base = off_lo;
+        a.scratch = scratch.p;
+        // the global class: as many rows at a time as workgroups fit the device, and as accumulators fit the budget
+        int nglobal = h[SPG_CLS_GLOBAL], gblocks = 0;
+        if (nglobal > 0) {
+            const size_t per_row = (size_t)m * sizeof(long long);
+            const size_t fit = budget / per_row;
+            if (fit == 0) {
+                char b[256];
+                snprintf(b, sizeof b, "a row of more than %d products needs an accumulator of %.2f GiB, %.2f GiB may be used", 64 << (SPG_LOGT_MAX - SPG_LOGT_MIN),
+                         (double)per_row / 1073741824.0, (double)budget / 1073741824.0);
+                throw EngineError(b);
+            }
+            gblocks = (int)std::min<size_t>(std::min<size_t>((size_t)nglobal, (size_t)num_cu * 2), fit);
+            if ((size_t)gblocks > dense_rows) {
+                dense.alloc((size_t)gblocks * (size_t)m);
+                dense.zero(s); // (the kernel leaves it zero)
+                dense_rows = (size_t)gblocks;
+            }
+        }
+        peak = std::max(peak, scratch.n * sizeof(int2) + dense.n * sizeof(long long));
+        // ---- numeric
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        int first = 0;
+        for (int cls = 0; cls < SPG_NCLASS; cls++) {
+            const int cntc = h[cls];
+            if (cntc > 0 && cls < SPG_CLS_GLOBAL) {
+                if (A.F.small) spg_launch_class<true>(cls, a, cntc, rowid2.p + first, s);
+                else spg_launch_class<false>(cls, a, cntc, rowid2.p + first, s);
+                rows_path[cls == 0 ? 0 : 1] += cntc;
+            } else if (cntc > 0 && cls == SPG_CLS_GLOBAL) {
+                hipLaunchKernelGGL(k_spg_global, dim3(gblocks), dim3(256), 0, s, a, cntc, rowid2.p + first, dense.p);
+                HIPCHK(hipGetLastError());
+                rows_path[2] += cntc;
+            }
+            first += cntc;
+        }
+        // ---- compact
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        scan.exclusive(cnt.p + lo, pos.p, (size_t)nc + 1, s); // (cnt[hi] is still 0: the chunks go in ascending order)
+        i64d cn = 0;
+        HIPCHK(hipMemcpyAsync(&cn, pos.p + nc, sizeof(i64d), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        parts[(size_t)c].alloc((size_t)cn + 1);
+        part_nnz[(size_t)c] = cn;
+        if (cn > 0) {
+            if (chunk_cap <= 16 * (i64d)nc) hipLaunchKernelGGL((k_spg_pack<8>), dim3(cdiv((i64)nc * 8, 256)), dim3(256), 0, s, lo, nc, off.p, off_lo, scratch.p, cnt.p, pos.p, parts[(size_t)c].p);
+            else hipLaunchKernelGGL((k_spg_pack<64>), dim3(cdiv((i64)nc * 64, 256)), dim3(256), 0, s, lo, nc, off.p, off_lo, scratch.p, cnt.p, pos.p, parts[(size_t)c].p);
+            HIPCHK(hipGetLastError());
+        }
+        HIPCHK(hipEventRecord(ev.e[3], s));
+        HIPCHK(hipStreamSynchronize(s));
+        ms_num += ev.ms(1, 2);
+        ms_compact += ev.ms(2, 3);
+    }
+    scratch.release();
+    dense.release();
+    // ---- the row pointers, and the parts back to back
+    scan.exclusive(cnt.p, R->p.p, n1, s);
+    i64 nnz = 0;
+    for (i64 v : part_nnz) nnz += v;
+    R->nnz = nnz;
+    if (nchunks == 1) {
+        R->ent = std::move(parts[0]);
+    } else {
+        R->ent.alloc((size_t)nnz + 1);
+        i64 at = 0;
+        for (int c = 0; c < nchunks; c++) {
+            if (part_nnz[(size_t)c] > 0)
+                HIPCHK(hipMemcpyAsync(R->ent.p + at, parts[(size_t)c].p, (size_t)part_nnz[(size_t)c] * sizeof(int2), hipMemcpyDeviceToDevice, s));
+            at += part_nnz[(size_t)c];
+        }
+    }
+    i64d hmax = 0;
+    HIPCHK(hipMemcpyAsync(&hmax, maxb.p, sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = R->stats;
+    st[0] = flops;
+    st[1] = nnz;
+    st[2] = rows_path[0];
+    st[3] = rows_path[1];
+    st[4] = rows_path[2];
+    st[5] = nchunks;
+    st[6] = (i64)(ms_size * 1000.0);
+    st[7] = (i64)(ms_num * 1000.0);
+    st[8] = (i64)(ms_compact * 1000.0);
+    st[9] = (i64)peak;
+    st[11] = hmax;
+    return R;
+}
+
+spasm_amd_dcsr *dcsr_upload(const struct spasm_csr *A, const char *who)
+{
+    require_device();
+    check_input(A, who);
+    const std::string w(who);
+    if (!A->x) throw EngineError(w + ": matrix without values (A->x == NULL)");
+    const int n = A->n, m = A->m;
+    if (n < 0 || m < 0 || !A->p || A->p[0] != 0) throw EngineError(w + ": malformed matrix");
+    for (int i = 0; i < n; i++)
+        if (A->p[i + 1] < A->p[i]) throw EngineError(w + ": row pointers must not decrease");
+    const i64 nnz = A->p[n];
+    if (nnz > 0 && !A->j) throw EngineError(w + ": malformed matrix");
+    std::unique_ptr<spasm_amd_dcsr> D(new spasm_amd_dcsr());
+    HIPCHK(hipGetDevice(&D->dev));
+    D->F = zp_field_make(A->field->p);
+    D->n = n;
+    D->m = m;
+    D->nnz = nnz;
+    hipStream_t s = nullptr;
+    D->p.alloc((size_t)n + 1);
+    D->ent.alloc((size_t)nnz + 1);
+    static_assert(sizeof(i64d) == sizeof(i64), "row pointers are copied as they are");
+    HIPCHK(hipMemcpyAsync(D->p.p, A->p, ((size_t)n + 1) * sizeof(i64d), hipMemcpyHostToDevice, s));
+    if (nnz > 0) {
+        DevBuf<int> dj, dx, bad;
+        dj.alloc((size_t)nnz);
+        dx.alloc((size_t)nnz);
+        bad.alloc(1);
+        bad.zero(s);
+        HIPCHK(hipMemcpyAsync(dj.p, A->j, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dx.p, A->x, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        const int grid = (int)std::min<i64>(cdiv(nnz, 256), 65536);
+        hipLaunchKernelGGL(k_spg_check_cols, dim3(grid), dim3(256), 0, s, (i64d)nnz, m, dj.p, bad.p);
+        hipLaunchKernelGGL(k_pack_entries, dim3(grid), dim3(256), 0, s, (i64d)nnz, D->F, dj.p, dx.p, D->ent.p);
+        HIPCHK(hipGetLastError());
+        int hbad = 0;
+        HIPCHK(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hbad) throw EngineError(w + ": a column index lies outside the matrix");
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return D.release();
+}
+
+struct spasm_csr *dcsr_download(const spasm_amd_dcsr *D)
+{
+    hipStream_t s = nullptr;
+    struct spasm_csr *R = spasm_csr_alloc(D->n, D->m, D->nnz, D->F.p, true);
+    if (!R) throw EngineError("out of host memory");
+    try {
+        HIPCHK(hipMemcpyAsync(R->p, D->p.p, ((size_t)D->n + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+        if (D->nnz > 0) {
+            DevBuf<int> dj, dx;
+            dj.alloc((size_t)D->nnz);
+            dx.alloc((size_t)D->nnz);
+            hipLaunchKernelGGL(k_spg_unpack, dim3((int)std::min<i64>(cdiv(D->nnz, 256), 65536)), dim3(256), 0, s, (i64d)D->nnz, D->ent.p, dj.p, dx.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(R->j, dj.p, (size_t)D->nnz * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(R->x, dx.p, (size_t)D->nnz * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    } catch (...) {
+        spasm_csr_free(R);
+        throw;
+    }
+    return R;
+}
+
+int spg_scalar(const ZpField &F, i64 a)
+{
+    i64 r = a % F.p;
+    if (r < 0) r += F.p;
+    return zp_normalize(F, r);
+}
+
+void dcsr_need(const spasm_amd_dcsr *D, const char *who)
+{
+    if (!D) throw EngineError(std::string(who) + ": NULL matrix");
+}
+
+spasm_amd_dcsr *dcsr_mul(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B, const char *who)
+{
+    dcsr_need(A, who);
+    dcsr_need(B, who);
+    const std::string w(who);
+    if (A->F.p != B->F.p) throw EngineError(w + ": the matrices are over different primes");
+    if (A->m != B->n) throw EngineError(w + ": dimension mismatch (columns of A, rows of B)");
+    if (A->dev != B->dev) throw EngineError(w + ": the matrices live on different devices");
+    return spg_run(SPG_MUL, *A, B, 1, 1, 0, 0, 0, 0).release();
+}
+
+spasm_amd_dcsr *dcsr_lincomb(i64 a, const spasm_amd_dcsr *A, i64 b, const spasm_amd_dcsr *B, const char *who)
+{
+    dcsr_need(A, who);
+    const std::string w(who);
+    if (B) {
+        if (A->F.p != B->F.p) throw EngineError(w + ": the matrices are over different primes");
+        if (A->n != B->n || A->m != B->m) throw EngineError(w + ": dimension mismatch");
+        if (A->dev != B->dev) throw EngineError(w + ": the matrices live on different devices");
+    }
+    return spg_run(SPG_LINCOMB, *A, B, spg_scalar(A->F, a), spg_scalar(A->F, b), 0, 0, 0, 0).release();
+}
+
+spasm_amd_dcsr *dcsr_submatrix(const spasm_amd_dcsr *A, int r0, int r1, int c0, int c1, const char *who)
+{
+    dcsr_need(A, who);
+    if (r0 < 0 || r1 < r0 || r1 > A->n || c0 < 0 || c1 < c0 || c1 > A->m) throw EngineError(std::string(who) + ": range outside the matrix");
+    return spg_run(SPG_SUBMATRIX, *A, nullptr, 1, 1, r0, r1, c0, c1).release();
+}
+
+int dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B, const char *who)
+{
+    dcsr_need(A, who);
+    dcsr_need(B, who);
+    if (A->dev != B->dev) throw EngineError(std::string(who) + ": the matrices live on different devices");
+    if (A->n != B->n || A->m != B->m || A->F.p != B->F.p) return 0;
+    std::unique_ptr<spasm_amd_dcsr> ca, cb; // canonical forms of what is not canonical yet: 1 * A
+    if (!A->canonical) { ca.reset(dcsr_lincomb(1, A, 0, nullptr, who)); A = ca.get(); }
+    if (!B->canonical) { cb.reset(dcsr_lincomb(1, B, 0, nullptr, who)); B = cb.get(); }
+    if (A->nnz != B->nnz) return 0;
+    hipStream_t s = nullptr;
+    DevBuf<int> diff;
+    diff.alloc(1);
+    diff.zero(s);
+    const i64 work = std::max<i64>(A->nnz, (i64)A->n + 1);
+    hipLaunchKernelGGL(k_spg_diff, dim3((int)std::min<i64>(cdiv(work, 256), 65536)), dim3(256), 0, s, A->n, (i64d)A->nnz, A->p.p, B->p.p, A->ent.p, B->ent.p, diff.p);
+    HIPCHK(hipGetLastError());
+    int h = 0;
+    HIPCHK(hipMemcpyAsync(&h, diff.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return h ? 0 : 1;
+}
+
+struct spasm_csr *csr_mul_once(const struct spasm_csr *A, const struct spasm_csr *B)
+{
+    require_device();
+    if (!A || !B) throw EngineError("NULL matrix");
+    if (A->m != B->n) throw EngineError("dimension mismatch (columns of A, rows of B)");
+    if (A->field->p != B->field->p) throw EngineError("the matrices are over different primes");
+    std::unique_ptr<spasm_amd_dcsr> a(dcsr_upload(A, "A"));
+    std::unique_ptr<spasm_amd_dcsr> b(dcsr_upload(B, "B"));
+    std::unique_ptr<spasm_amd_dcsr> c(dcsr_mul(a.get(), b.get(), "product"));
+    a.reset();
+    b.reset();
+    return dcsr_download(c.get());
+}
+
+struct spasm_csr *csr_lincomb_once(i64 sa, const struct spasm_csr *A, i64 sb, const struct spasm_csr *B)
+{
+    require_device();
+    if (!A) throw EngineError("NULL matrix");
+    if (B && (A->n != B->n || A->m != B->m)) throw EngineError("dimension mismatch");
+    if (B && A->field->p != B->field->p) throw EngineError("the matrices are over different primes");
+    std::unique_ptr<spasm_amd_dcsr> a(dcsr_upload(A, "A"));
+    std::unique_ptr<spasm_amd_dcsr> b(B ? dcsr_upload(B, "B") : nullptr);
+    std::unique_ptr<spasm_amd_dcsr> c(dcsr_lincomb(sa, a.get(), sb, b.get(), "combination"));
+    a.reset();
+    b.reset();
+    return dcsr_download(c.get());
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
 // Dense triangular solves x T = b (trsolve.hpp): the operator keeps T on the device in the order of its pivot graph's levels,
 // cut into panels, with each panel's entries gathered by the later position they feed.
 // ------------------------------------------------------------------------------------------------
@@ -7176,6 +7633,65 @@ SPASM_API void spasm_amd_spmv_free(spasm_amd_spmv *op)
     DeviceGuard g;
     (void)hipSetDevice(op->dev);
     delete op;
+}
+
+// ---- sparse matrix algebra on resident matrices (spgemm.hpp; engine extension) ----
+#define DCSR_TRY(who, body, fail)                          \
+    spasm_clear_error();                                   \
+    try {                                                  \
+        body                                               \
+    } catch (const std::exception &e) {                    \
+        spasm_set_error("%s: %s", who, e.what());          \
+        return fail;                                       \
+    }
+#define DCSR_ON(D) DeviceGuard g; if (D) HIPCHK(hipSetDevice((D)->dev));
+
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_upload(const struct spasm_csr *A) { DCSR_TRY("spasm_amd_dcsr_upload", return dcsr_upload(A, "upload");, nullptr) }
+SPASM_API struct spasm_csr *spasm_amd_dcsr_download(const spasm_amd_dcsr *D)
+{
+    DCSR_TRY("spasm_amd_dcsr_download", dcsr_need(D, "download"); DCSR_ON(D) return dcsr_download(D);, nullptr)
+}
+SPASM_API void spasm_amd_dcsr_info(const spasm_amd_dcsr *D, i64 *out)
+{
+    if (!D || !out) return;
+    out[0] = D->n;
+    out[1] = D->m;
+    out[2] = D->nnz;
+    out[3] = D->F.p;
+}
+SPASM_API void spasm_amd_dcsr_stats(const spasm_amd_dcsr *D, i64 *out)
+{
+    if (!D || !out) return;
+    memcpy(out, D->stats, sizeof D->stats);
+}
+SPASM_API void spasm_amd_dcsr_free(spasm_amd_dcsr *D)
+{
+    if (!D) return;
+    DeviceGuard g;
+    (void)hipSetDevice(D->dev);
+    delete D;
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_mul(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B)
+{
+    DCSR_TRY("spasm_amd_dcsr_mul", DCSR_ON(A) return dcsr_mul(A, B, "product");, nullptr)
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_lincomb(i64 a, const spasm_amd_dcsr *A, i64 b, const spasm_amd_dcsr *B)
+{
+    DCSR_TRY("spasm_amd_dcsr_lincomb", DCSR_ON(A) return dcsr_lincomb(a, A, b, B, "combination");, nullptr)
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_submatrix(const spasm_amd_dcsr *A, int r0, int r1, int c0, int c1)
+{
+    DCSR_TRY("spasm_amd_dcsr_submatrix", DCSR_ON(A) return dcsr_submatrix(A, r0, r1, c0, c1, "submatrix");, nullptr)
+}
+SPASM_API int spasm_amd_dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B)
+{
+    DCSR_TRY("spasm_amd_dcsr_equal", DCSR_ON(A) return dcsr_equal(A, B, "comparison");, -1)
+}
+// one-shot forms on host matrices: upload, operate, download
+SPASM_API struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B) { DCSR_TRY("spasm_amd_csr_mul", return csr_mul_once(A, B);, nullptr) }
+SPASM_API struct spasm_csr *spasm_amd_csr_lincomb(i64 a, const struct spasm_csr *A, i64 b, const struct spasm_csr *B)
+{
+    DCSR_TRY("spasm_amd_csr_lincomb", return csr_lincomb_once(a, A, b, B);, nullptr)
 }
 
 // reference src/SpaSM.jl:663-692 (dense_back_solve, dense_forward_solve): host arrays; on an error b and x are left as they were
