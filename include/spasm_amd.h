@@ -358,10 +358,7 @@ struct spasm_amd_round_stats {
     i64 w_entries;
     i64 w_long_rows;
     i64 npiv_greedy;      /* of npiv: pivots the greedy cycle-free search added (reference README.md:23; csrc/greedy.hpp) */
-    /* the fused Schur kernel (csrc/fused.hpp: plan + stream of a row in one kernel; round 4): device time of its launch and of the
-     * fix-up launch behind it (plans with class timing on; 0 otherwise), rows it took, entries it streamed, row segments it visited
-     * (1 per row + 1 per run of W), rows it left to the general path (whose launches are the classes above), entries of S its waves
-     * took from the cursor */
+    /* reserved, always 0 (the seven fields of a removed Schur kernel; they keep the layout of the struct) */
     double ms_fused;
     double ms_fused_fix;
     i64 rows_fused;

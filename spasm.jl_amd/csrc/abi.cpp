@@ -431,7 +431,7 @@ extern "C" SPASM_API bool spasm_rank_certificate_load(void *file, struct spasm_r
     if (fscanf(f, "%d %lld", &r, &prime) != 2 || r < 0) return false;
     {
         // r comes from the file: every one of its r lines takes 8 bytes at least ("i j x y\n"), so a count the rest of the file
-        // cannot hold is refused before anything is allocated for it
+        // cannot hold is rejected before anything is allocated for it
         const long at = ftell(f);
         if (at >= 0 && fseek(f, 0, SEEK_END) == 0) {
             const long end = ftell(f);
