@@ -518,6 +518,42 @@ int spasm_amd_multi_last_finish(void);
  * options as spasm_echelonize (L excluded); -1 on error. */
 i64 spasm_amd_rank(const struct spasm_csr *A, struct echelonize_opts *opts);
 
+/* ---- Engine extension: many small matrices in one call (csrc/batch.hpp) ----
+ * spasm_echelonize pays a fixed cost per call (upload, planning of the rounds, dozens of launches, several synchronisations) that
+ * dwarfs the work on a matrix of a few dozen rows.  These entries take `count` matrices A[0 .. count) at once; the matrices of one
+ * batch may differ in shape and in prime.
+ *   LDS path      a matrix with values, n * m <= 32768 (and opts == NULL or opts->L == 0) is eliminated by ONE workgroup in a dense
+ *                 image held in LDS, all such matrices of the batch in a constant number of launches per chunk (a chunk = as many
+ *                 matrices as fit the scratch budget, a third of the free device memory; SPASM_AMD_BATCH_SCRATCH_MB lowers it);
+ *                 one upload per call; per chunk one download, preceded by the 8-byte read of its size
+ *   general path  every other matrix of the batch goes through spasm_echelonize / spasm_kernel as they are, one at a time;
+ *                 its result is what the per-matrix call returns under `opts`
+ *   echelonize    out[i] is an ordinary spasm_lu (free it with spasm_lu_free).  From the LDS path: r, U r x m with the pivot 1 as the
+ *                 leftmost entry of its row and the columns ascending inside each row, qinv, p (the elected rows in election order,
+ *                 then the others ascending), L == NULL, complete == false; U is the REDUCED row echelon form, and row k holds the
+ *                 k-th pivot column.  spasm_kernel, spasm_rref, spasm_gesv, spasm_solve, spasm_factorization_verify and
+ *                 spasm_certificate_rank_create take it like any other LU.
+ *   options       the LDS path always elects the canonical pivot columns (those leftmost-entry pivots give: the pivot of a column
+ *                 is the first row, not yet a pivot, that holds it), so the pivot-search options (enable_greedy_pivot_search,
+ *                 enable_tall_and_skinny, enable_dense, enable_GPLU, min_pivot_proportion, max_round, sparsity_threshold, ...)
+ *                 have NO EFFECT there; rank and row space are those of spasm_echelonize under any options
+ *   kernel        K[i] = the vectors spasm_kernel returns for that LU (vector of the free column f: -1 on f, R[a][f] on the pivot
+ *                 column of row a of the reduced form), in ascending order of their free column, columns ascending inside a vector
+ *   rank          rank[i] only; nothing but the ranks is downloaded
+ *   stats         of the last batch call of this thread: out[8] = matrices, matrices through the LDS path, matrices through the
+ *                 general path, chunks, kernel launches of the LDS path (eliminations, scans, packs), device microseconds of the LDS
+ *                 path (HIP events), entries written by the LDS path, largest image in 32-bit words
+ *   exact         for every prime the engine accepts (3 .. 0xFFFFFFFB); values of A may be any int32 (reduced on load); a row must
+ *                 not hold a column twice
+ *   deterministic two runs give byte-identical results
+ *   errors        count < 0, a NULL array, a NULL matrix, A[i]->x == NULL, a malformed matrix, a column index outside the matrix, no
+ *                 device ("no HIP device"), out of memory: -1, NO output slot is written, spasm_amd_last_error() names the cause and
+ *                 the index of the matrix.  count == 0 succeeds (and needs no device).  After success the error text is empty. */
+int spasm_amd_echelonize_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_lu **out);
+int spasm_amd_rank_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, i64 *rank);
+int spasm_amd_kernel_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_csr **K);
+void spasm_amd_batch_stats(i64 *out);   /* of the last batch call of this thread */
+
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 

@@ -19,6 +19,7 @@ from .api import (
     RankCertificate,
     axpy,
     balanced,
+    batch_stats,
     dense_back_solve,
     dense_forward_solve,
     certificate_rank_create,
@@ -26,15 +27,18 @@ from .api import (
     rank_certificate_load,
     rank_certificate_save,
     echelonize,
+    echelonize_batch,
     echelonize_multi,
     factorization_verify,
     gesv,
     kernel,
+    kernel_batch,
     last_rounds,
     load,
     nnz,
     prime0,
     rank,
+    rank_batch,
     rref,
     save,
     scatter,
@@ -53,4 +57,5 @@ __all__ = [
     "last_rounds", "nnz", "prime0", "rank", "rref", "sparse", "sparse_triangular_solve", "sparse_triangular_solve_row", "scatter", "synth_csr", "transpose",
     "axpy", "xapy", "SpMV", "dense_forward_solve", "dense_back_solve", "TriangularSolver",
     "DeviceCSR", "submatrix",
+    "echelonize_batch", "rank_batch", "kernel_batch", "batch_stats",
 ]

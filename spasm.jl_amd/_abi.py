@@ -268,6 +268,10 @@ SIGNATURES = {
     "spasm_amd_trsolve_apply_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "spasm_amd_trsolve_stats": (None, [C.c_void_p, _P(C.c_int64)]),
     "spasm_amd_trsolve_free": (None, [C.c_void_p]),
+    "spasm_amd_echelonize_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(EchelonizeOptsStruct), _P(_P(LuStruct))]),
+    "spasm_amd_rank_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(EchelonizeOptsStruct), _P(C.c_int64)]),
+    "spasm_amd_kernel_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(EchelonizeOptsStruct), _P(_P(CsrStruct))]),
+    "spasm_amd_batch_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

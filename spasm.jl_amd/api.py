@@ -1059,6 +1059,70 @@ def rank(A, rank_only=False, verbose=False, **kwargs):
     return int(r)
 
 
+# ---------------------------------------------------------------------------------------------
+# Many small matrices in one call  (spasm_amd_*_batch; csrc/batch.hpp; engine extension)
+# ---------------------------------------------------------------------------------------------
+BATCH_STATS = ("matrices", "lds_path", "general_path", "chunks", "launches", "device_us", "entries", "max_image_words")
+
+
+def _batch_args(mats, opts, kwargs):
+    mats = list(mats)
+    for A in mats:
+        if not isinstance(A, CSR):
+            raise TypeError("a list of CSR expected")
+    if opts is None:
+        opts = EchelonizeOpts()
+    for k, v in kwargs.items():
+        if not hasattr(opts.struct, k):
+            raise AttributeError(f"type EchelonizeOpts has no field {k}")
+        setattr(opts.struct, k, v)
+    arr = (C.POINTER(_abi.CsrStruct) * max(len(mats), 1))(*[A.data for A in mats])
+    return mats, opts, arr
+
+
+def echelonize_batch(mats, opts=None, verbose=False, **kwargs):
+    """echelonize_batch([A, ...]; kwargs...) -> [LU, ...] (spasm_amd_echelonize_batch): matrices with n * m <= 32768 are
+    eliminated inside LDS, one workgroup each, all in a few launches; the others, and every matrix when L=True, take the path of
+    echelonize one at a time.  The LDS path elects the canonical (leftmost) pivot columns whatever the pivot-search options say."""
+    mats, opts, arr = _batch_args(mats, opts, kwargs)
+    out = (C.POINTER(_abi.LuStruct) * max(len(mats), 1))()
+    with _quiet(not verbose):
+        rc = _abi.lib().spasm_amd_echelonize_batch(len(mats), arr, C.byref(opts.struct), out)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_echelonize_batch failed")
+    return [LU(out[i]) for i in range(len(mats))]
+
+
+def rank_batch(mats, opts=None, verbose=False, **kwargs):
+    """rank_batch([A, ...]; kwargs...) -> [rank, ...] (spasm_amd_rank_batch): only the ranks leave the device."""
+    mats, opts, arr = _batch_args(mats, opts, kwargs)
+    out = (C.c_int64 * max(len(mats), 1))()
+    with _quiet(not verbose):
+        rc = _abi.lib().spasm_amd_rank_batch(len(mats), arr, C.byref(opts.struct), out)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_rank_batch failed")
+    return [int(out[i]) for i in range(len(mats))]
+
+
+def kernel_batch(mats, opts=None, verbose=False, **kwargs):
+    """kernel_batch([A, ...]; kwargs...) -> [K, ...] (spasm_amd_kernel_batch): K[i] = kernel(echelonize_batch(...)[i]), its
+    vectors in ascending order of their free column, without the LUs ever reaching the host."""
+    mats, opts, arr = _batch_args(mats, opts, kwargs)
+    out = (C.POINTER(_abi.CsrStruct) * max(len(mats), 1))()
+    with _quiet(not verbose):
+        rc = _abi.lib().spasm_amd_kernel_batch(len(mats), arr, C.byref(opts.struct), out)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_kernel_batch failed")
+    return [CSR(out[i]) for i in range(len(mats))]
+
+
+def batch_stats():
+    """Counters of the last batch call of this thread (spasm_amd_batch_stats), as a dict keyed by BATCH_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_batch_stats(out)
+    return {k: int(v) for k, v in zip(BATCH_STATS, out)}
+
+
 def last_rounds(max_rounds=4096):
     """Per-round records of the most recent echelonize call on this thread (engine extension)."""
     buf = (_abi.RoundStats * max_rounds)()

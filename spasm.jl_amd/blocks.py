@@ -69,37 +69,64 @@ class Block:
     def to_csr(self):
         """CSR(block::Block{CSR}) (src/blocks.jl:142-170)."""
         n, m = self.shape
-        prime = self.blocks[0].prime if self.blocks else api.prime0
+        present = [b for b in self.blocks if b is not None]
+        prime = present[0].prime if present else api.prime0
         rows = []
-        cache = [b.rows() for b in self.blocks]
+        cache = [b.rows() if b is not None else [] for b in self.blocks]
         for i in range(n):
             b, sub = self.row2block[i]
             rows.append([(self.block2col[b][c], v) for c, v in cache[b][sub]])
         return api.CSR.from_rows(rows, m, prime=prime)
 
 
-def echelonize(block, owner=None, **kwargs):
-    """echelonize(block::Block{CSR}) (src/blocks.jl:107-115).  owner=(rank, world): only blocks b % world == rank."""
-    lus = []
-    for b, A in enumerate(block.blocks):
-        mine = owner is None or b % owner[1] == owner[0]
-        lus.append(api.echelonize(A, **kwargs) if mine else None)
+def _mine(block, owner):
+    """indices of the blocks of the caller's share (owner=(rank, world): b % world == rank) that are present"""
+    return [b for b, X in enumerate(block.blocks) if X is not None and (owner is None or b % owner[1] == owner[0])]
+
+
+def echelonize(block, owner=None, batched=False, **kwargs):
+    """echelonize(block::Block{CSR}) (src/blocks.jl:107-115).  owner=(rank, world): only blocks b % world == rank.
+    batched=True: the blocks of the share go through ONE api.echelonize_batch call instead of a loop over api.echelonize (small
+    blocks are then eliminated inside LDS with canonical pivot columns, whatever the pivot-search options say)."""
+    lus = [None] * len(block.blocks)
+    mine = _mine(block, owner)
+    if batched:
+        for b, lu in zip(mine, api.echelonize_batch([block.blocks[b] for b in mine], **kwargs)):
+            lus[b] = lu
+    else:
+        for b in mine:
+            lus[b] = api.echelonize(block.blocks[b], **kwargs)
     return Block(lus, block.row2block, block.col2block, block.block2row, block.block2col)
 
 
-def rank(block, **kwargs):
-    """rank(block) = sum of the ranks (src/blocks.jl:117)."""
-    return sum(api.rank(X, **kwargs) for X in block.blocks if X is not None)
+def rank(block, owner=None, batched=False, **kwargs):
+    """rank(block) = sum of the ranks (src/blocks.jl:117) over the blocks of the share.  batched=True: one api.rank_batch call
+    for the blocks that are still matrices."""
+    mine = _mine(block, owner)
+    if batched:
+        mats = [block.blocks[b] for b in mine if isinstance(block.blocks[b], api.CSR)]
+        rest = [block.blocks[b] for b in mine if not isinstance(block.blocks[b], api.CSR)]
+        return sum(api.rank_batch(mats, **kwargs)) + sum(api.rank(X) for X in rest)
+    return sum(api.rank(block.blocks[b], **kwargs) for b in mine)
 
 
-def kernel(block, **kwargs):
-    """kernel(block::Block{LU}) (src/blocks.jl:119-137): per-block kernels, rows numbered block after block."""
-    if block.blocks and isinstance(block.blocks[0], api.CSR):
-        block = echelonize(block, **kwargs)
-    ks = [api.kernel(X) for X in block.blocks]
+def kernel(block, owner=None, batched=False, **kwargs):
+    """kernel(block::Block{LU}) (src/blocks.jl:119-137): per-block kernels, rows numbered block after block; a block outside the
+    share (or absent) contributes no rows.  batched=True on a Block of matrices: one api.kernel_batch call for the share."""
+    ks = [None] * len(block.blocks)
+    mine = _mine(block, owner)
+    if batched and all(isinstance(block.blocks[b], api.CSR) for b in mine):
+        for b, k in zip(mine, api.kernel_batch([block.blocks[b] for b in mine], **kwargs)):
+            ks[b] = k
+    else:
+        if block.blocks and any(isinstance(block.blocks[b], api.CSR) for b in mine):
+            block = echelonize(block, owner=owner, batched=batched, **kwargs)
+        for b in mine:
+            ks[b] = api.kernel(block.blocks[b])
     block2row, row2block, r = [], [], 0
     for b, k in enumerate(ks):
-        block2row.append(list(range(r, r + k.n)))
-        row2block += [(b, i) for i in range(k.n)]
-        r += k.n
+        kn = k.n if k is not None else 0
+        block2row.append(list(range(r, r + kn)))
+        row2block += [(b, i) for i in range(kn)]
+        r += kn
     return Block(ks, row2block, block.col2block, block2row, block.block2col)

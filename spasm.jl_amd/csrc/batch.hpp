@@ -1,0 +1,244 @@
+// batch.hpp -- many small matrices echelonized in one launch: one workgroup per matrix, resident in LDS from first load to last store.
+//
+// The whole batch is one concatenated device CSR (row pointers P as global entry offsets, columns J, values X) plus one
+// descriptor per matrix.  A workgroup scatters its matrix into a dense n x m image of balanced residues (32-bit words, row
+// stride ld) and eliminates it column by column with the rule dense.hpp:5 states: the pivot of a column is the first row, not
+// yet a pivot, that holds a non-zero there.  The pivot row is subtracted from EVERY other row that holds the column (earlier
+// pivot rows too), so the image ends as the reduced row echelon form and the pivot columns are the canonical ones.
+//
+// Two shortcuts keep it to three barriers per column, both invisible in the result:
+//   - pivot rows are not normalised in place: row k stays a multiple of its normalised form and the inverse of its pivot is
+//     kept (pinv[k]); the factor of a row is f * pinv and the output multiplies by pinv once;
+//   - column c is not zeroed: the factors are written over it (each row its own word) and read from there by the update.
+//     Pivot columns of the final image therefore hold leftovers; the output never reads them (the pivot is written as 1).
+//
+// Row stride: the election and the factor pass walk DOWN a column, lane i at word i * ld + c.  ds_read_b32 / ds_write_b32 bank
+// on (word mod 32) per half wave, so an odd ld makes the walk conflict-free and an even one folds it onto 32 / gcd(ld, 32) banks.
+// ld = m for odd m, m + 1 for even m when the padded image still fits the largest class (BATCH_PAD_CAP), else m.
+//
+// Output of a workgroup, into its slices of the chunk's buffers (no atomics, no cross-workgroup traffic):
+//   BATCH_LU      rec[0] = rank, rec[2 .. 2 + m) = qinv, rec[2 + m .. 2 + m + n) = p (elected rows in election order, then the
+//                 others ascending); row k of U (k-th elected pivot = k-th pivot column) compacted in column order at
+//                 scratch[slice + k * (m - r + 1)], its length in cnt[slot0 + k]
+//   BATCH_KERNEL  rec[0] = rank; kernel vector t (t-th free column f) = {(pivcol(k), R[k][f])} in k order, then (f, -1), at
+//                 scratch[slice + t * (r + 1)], its length in cnt[slot0 + t]
+//   BATCH_RANK    rank[item] only (rows that are pivots already are not reduced further)
+// k_batch_pack then copies the rows back to back at the exclusive scan of cnt, in the manner of k_spg_pack.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "zp.hpp"
+
+#define BATCH_LIMIT 32768     // n * m <= this many words takes the LDS path (and n, m <= it)
+#define BATCH_PAD_CAP 34816   // words of image the largest class holds: the limit + room for the padding of the stride
+#define BATCH_NCLASS 4
+
+enum { BATCH_LU = 0, BATCH_KERNEL = 1, BATCH_RANK = 2 };
+
+struct BatchDesc {
+    i64d row0;    // P[row0 .. row0 + n]: the row pointers of the matrix (offsets into J / X)
+    i64d rec;     // its record in the chunk's output buffer (ints)
+    i64d slice;   // its slice of the entry scratch (int2)
+    i64d slot0;   // its first row slot in cnt
+    int n, m, ld;
+    int nslots;   // row slots: min(n, m) for BATCH_LU, m for BATCH_KERNEL
+    ZpField F;
+};
+
+struct BatchArgs {
+    const BatchDesc *desc;
+    const int *items;          // descriptors of this launch (one class of one chunk)
+    const i64d *P;
+    const int *J;
+    const int *X;
+    int mode;
+    int cap, bw, rmax;         // LDS layout of the class: image words, words per bitset, pivots
+    int *rec;
+    int2 *scratch;
+    int *cnt;
+    int *rank;                 // BATCH_RANK: indexed like desc
+};
+
+// words of LDS of a class besides the image: two bitsets (pivot rows, pivot columns), three pivot lists, the election's mailbox
+__host__ __device__ inline int batch_lds_words(int cap, int bw, int rmax) { return cap + 2 * bw + 3 * rmax + 16; }
+
+template <int BS>
+__global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
+{
+    extern __shared__ int s_batch[];
+    constexpr int NW = BS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int item = a.items[blockIdx.x];
+    const BatchDesc d = a.desc[item];
+    const ZpField F = d.F;
+    const int n = d.n, m = d.m, ld = d.ld, mode = a.mode;
+    int *img = s_batch;
+    unsigned *rowflag = (unsigned *)(img + a.cap);
+    unsigned *colflag = rowflag + a.bw;
+    int *pivrow = (int *)(colflag + a.bw);
+    int *pivcol = pivrow + a.rmax;
+    int *pinv = pivcol + a.rmax;
+    int *wmin = pinv + a.rmax;
+
+    for (int e = tid; e < n * ld; e += BS) img[e] = 0;
+    for (int w = tid; w < a.bw; w += BS) { rowflag[w] = 0; colflag[w] = 0; }
+    __syncthreads();
+    // TX lanes per row (a power of two, at most a wave), TY rows at a time
+    int lt = 0;
+    while ((1 << lt) < m && lt < 6) lt++;
+    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
+    for (int i = ty; i < n; i += TY) {
+        const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
+        for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
+    }
+    __syncthreads();
+
+    int r = 0, par = 0;
+    int *qinv = a.rec + d.rec + 2;
+    for (int c = 0; c < m; c++) {
+        // ---- election: the first row that is not a pivot yet and holds column c
+        int pr = 0x7fffffff;
+        for (int base = 0; base < n; base += BS) {
+            const int i = base + tid;
+            const bool hit = i < n && !((rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + c] != 0;
+            const unsigned long long b = __ballot(hit);
+            if (lane == 0) wmin[par * 8 + wave] = b ? base + wave * 64 + (__ffsll((long long)b) - 1) : 0x7fffffff;
+            __syncthreads();
+            int best = 0x7fffffff;
+#pragma unroll
+            for (int w = 0; w < NW; w++) best = min(best, wmin[par * 8 + w]);
+            par ^= 1; // (the mailbox of the step before last is free again: a barrier lies between)
+            if (best != 0x7fffffff) { pr = best; break; }
+        }
+        if (pr == 0x7fffffff) {
+            if (tid == 0 && mode == BATCH_LU) qinv[c] = -1;
+            continue;
+        }
+        const int inv = zp_inverse(F, img[pr * ld + c]);
+        // ---- factors, in place on column c
+        for (int i = tid; i < n; i += BS) {
+            if (i == pr) continue;
+            const int f = img[i * ld + c];
+            if (f == 0) continue;
+            const bool done = mode == BATCH_RANK && ((rowflag[i >> 5] >> (i & 31)) & 1u);
+            img[i * ld + c] = done ? 0 : zp_mul(F, f, inv);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            rowflag[pr >> 5] |= 1u << (pr & 31);
+            colflag[c >> 5] |= 1u << (c & 31);
+            pivrow[r] = pr;
+            pivcol[r] = c;
+            pinv[r] = inv;
+            if (mode == BATCH_LU) qinv[c] = r;
+        }
+        // ---- update: row i -= factor * pivot row, on the columns right of c
+        for (int i = ty; i < n; i += TY) {
+            if (i == pr) continue;
+            const int g = img[i * ld + c];
+            if (g == 0) continue;
+            for (int j = c + 1 + tx; j < m; j += TX) {
+                const int v = img[pr * ld + j];
+                if (v != 0) img[i * ld + j] = zp_axpy(F, -g, v, img[i * ld + j]);
+            }
+        }
+        __syncthreads();
+        r++;
+    }
+
+    if (mode == BATCH_RANK) {
+        if (tid == 0) a.rank[item] = r;
+        return;
+    }
+    int *rec = a.rec + d.rec;
+    int *cnt = a.cnt + d.slot0;
+    if (tid == 0) { rec[0] = r; rec[1] = 0; }
+    const unsigned long long lt_mask = (1ull << lane) - 1ull;
+    if (mode == BATCH_LU) {
+        const int stride = m - r + 1;
+        for (int k = wave; k < r; k += NW) {
+            const int pr = pivrow[k], pc = pivcol[k], inv = pinv[k];
+            int2 *dst = a.scratch + d.slice + (i64d)k * stride;
+            int count = 0;
+            for (int j0 = pc; j0 < m; j0 += 64) {
+                const int j = j0 + lane;
+                int v = 0;
+                if (j == pc) v = 1;
+                else if (j < m && !((colflag[j >> 5] >> (j & 31)) & 1u)) {
+                    const int x = img[pr * ld + j];
+                    if (x != 0) v = zp_mul(F, x, inv);
+                }
+                const unsigned long long b = __ballot(v != 0);
+                if (v != 0) dst[count + __popcll(b & lt_mask)] = make_int2(j, v);
+                count += __popcll(b);
+            }
+            if (lane == 0) cnt[k] = count;
+        }
+        for (int k = r + tid; k < d.nslots; k += BS) cnt[k] = 0;
+        __syncthreads();
+        // p: the elected rows, then the others ascending (their places from the popcounts of the words before them)
+        int *woff = (int *)colflag;
+        if (tid == 0) {
+            int off = 0;
+            for (int w = 0; w * 32 < n; w++) { woff[w] = off; off += __popc(~rowflag[w]); }
+        }
+        __syncthreads();
+        int *p = rec + 2 + m;
+        for (int k = tid; k < r; k += BS) p[k] = pivrow[k];
+        for (int i = tid; i < n; i += BS) {
+            const unsigned free_rows = ~rowflag[i >> 5];
+            if ((free_rows >> (i & 31)) & 1u) p[r + woff[i >> 5] + __popc(free_rows & ((1u << (i & 31)) - 1u))] = i;
+        }
+    } else {
+        const int stride = r + 1;
+        int *woff = (int *)rowflag;
+        __syncthreads();
+        if (tid == 0) {
+            int off = 0;
+            for (int w = 0; w * 32 < m; w++) { woff[w] = off; off += __popc(colflag[w]); }
+        }
+        __syncthreads();
+        for (int f = wave; f < m; f += NW) {
+            const unsigned word = colflag[f >> 5];
+            if ((word >> (f & 31)) & 1u) continue;
+            const int t = f - (woff[f >> 5] + __popc(word & ((1u << (f & 31)) - 1u)));
+            int2 *dst = a.scratch + d.slice + (i64d)t * stride;
+            int count = 0;
+            for (int k0 = 0; k0 < r; k0 += 64) {
+                const int k = k0 + lane;
+                int v = 0, pc = 0;
+                if (k < r) {
+                    pc = pivcol[k];
+                    if (pc < f) {
+                        const int x = img[pivrow[k] * ld + f];
+                        if (x != 0) v = zp_mul(F, x, pinv[k]);
+                    }
+                }
+                const unsigned long long b = __ballot(v != 0);
+                if (v != 0) dst[count + __popcll(b & lt_mask)] = make_int2(pc, v);
+                count += __popcll(b);
+            }
+            if (lane == 0) {
+                dst[count] = make_int2(f, -1);
+                cnt[t] = count + 1;
+            }
+        }
+        for (int t = m - r + tid; t < d.nslots; t += BS) cnt[t] = 0;
+    }
+}
+
+// the rows of a chunk back to back: one wave per matrix, row k of its slice to out[rowstart[slot0 + k] ..]
+__global__ __launch_bounds__(64) void k_batch_pack(const BatchDesc *__restrict__ desc, const int *__restrict__ items, int mode, const int *__restrict__ rec,
+                                                   const int *__restrict__ cnt, const i64d *__restrict__ rowstart, const int2 *__restrict__ scratch,
+                                                   int2 *__restrict__ out)
+{
+    const BatchDesc d = desc[items[blockIdx.x]];
+    const int r = rec[d.rec];
+    const int rows = mode == BATCH_LU ? r : d.m - r;
+    const int stride = mode == BATCH_LU ? d.m - r + 1 : r + 1;
+    for (int k = 0; k < rows; k++) {
+        const int c = cnt[d.slot0 + k];
+        const int2 *src = scratch + d.slice + (i64d)k * stride;
+        int2 *dst = out + rowstart[d.slot0 + k];
+        for (int e = threadIdx.x; e < c; e += 64) dst[e] = src[e];
+    }
+}

@@ -13,6 +13,7 @@
 #include "spmv.hpp"
 #include "spgemm.hpp"
 #include "trsolve.hpp"
+#include "batch.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -6483,6 +6484,390 @@ bool trsolve_once(const struct spasm_csr *T, spasm_ZZp *b, spasm_ZZp *x, const i
 
 } // namespace
 
+// ------------------------------------------------------------------------------------------------
+// Many small matrices in one call (batch.hpp): every matrix whose dense image fits LDS is eliminated by one workgroup; the others,
+// and every matrix of a call that asks for L, go through do_echelonize / do_kernel one at a time.  One upload for the whole
+// batch (descriptors, class-sorted items, row pointers, columns, values in one staging buffer); per chunk of matrices whose
+// scratch fits the budget: at most BATCH_NCLASS elimination launches, one scan, one pack, the 8-byte read of the chunk's
+// entry count and one download.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+thread_local i64 g_batch_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+struct BatchClass { int cap, bs; };
+// image words -> threads: small images get small workgroups and several of them per CU (LDS per workgroup: 5, 18, 53, 147 KiB)
+constexpr BatchClass kBatchClass[BATCH_NCLASS] = {{1024, 64}, {4096, 128}, {12288, 256}, {BATCH_PAD_CAP, 512}};
+
+void batch_layout(int cls, int &bw, int &rmax)
+{
+    const int lim = std::min(kBatchClass[cls].cap, BATCH_LIMIT);
+    bw = lim / 32;
+    rmax = 1; // min(n, m) <= sqrt(n * m) < rmax
+    while ((i64)rmax * rmax <= lim) rmax++;
+}
+
+template <int BS> void batch_launch(const BatchArgs &a, int nitems, size_t lds, hipStream_t s)
+{
+    static bool attr_done[kMaxDev] = {false};
+    bool &done = attr_done[current_device()];
+    if (!done) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_batch_elim<BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    hipLaunchKernelGGL((k_batch_elim<BS>), dim3(nitems), dim3(BS), lds, s, a);
+}
+
+void batch_launch_class(int cls, BatchArgs a, const int *items, int nitems, hipStream_t s)
+{
+    a.items = items;
+    a.cap = kBatchClass[cls].cap;
+    batch_layout(cls, a.bw, a.rmax);
+    const size_t lds = (size_t)batch_lds_words(a.cap, a.bw, a.rmax) * sizeof(int);
+    switch (cls) {
+    case 0: batch_launch<64>(a, nitems, lds, s); break;
+    case 1: batch_launch<128>(a, nitems, lds, s); break;
+    case 2: batch_launch<256>(a, nitems, lds, s); break;
+    default: batch_launch<512>(a, nitems, lds, s); break;
+    }
+    HIPCHK(hipGetLastError());
+}
+
+// bytes of device buffers one chunk may use: a third of the free device memory (SPASM_AMD_BATCH_SCRATCH_MB: a smaller figure, for
+// the tests of the chunked path; read once per call)
+size_t batch_budget()
+{
+    size_t fr = 0, tot = 0;
+    HIPCHK(hipMemGetInfo(&fr, &tot));
+    size_t b = fr / 3;
+    const char *e = getenv("SPASM_AMD_BATCH_SCRATCH_MB");
+    if (e && atof(e) > 0) b = std::min(b, (size_t)(atof(e) * 1048576.0));
+    return b;
+}
+
+// most entries of the output of an n x m matrix: U of rank r has r rows of at most m - r + 1 entries, K has m - r rows of at most
+// r + 1, r <= min(n, m); both products peak where the factors meet
+i64 batch_entry_cap(int mode, int n, int m)
+{
+    const i64 rm = std::min(n, m);
+    if (mode == BATCH_LU) {
+        const i64 r = std::min<i64>(rm, (m + 1) / 2);
+        return r * (m - r + 1);
+    }
+    const i64 r = std::min<i64>(rm, m / 2);
+    return (m - r) * (r + 1);
+}
+
+struct BatchResults {
+    std::vector<struct spasm_lu *> lu;
+    std::vector<struct spasm_csr *> K;
+    ~BatchResults()
+    {
+        for (auto *x : lu) spasm_lu_free(x);
+        for (auto *x : K) spasm_csr_free(x);
+    }
+};
+
+inline size_t batch_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// mode BATCH_LU: lu_out[count]; BATCH_KERNEL: k_out[count]; BATCH_RANK: rank_out[count].  Nothing is written before all is done.
+void batch_run(int mode, int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_lu **lu_out, struct spasm_csr **k_out, i64 *rank_out)
+{
+    memset(g_batch_stats, 0, sizeof g_batch_stats);
+    if (count < 0) throw EngineError("count < 0");
+    if (count == 0) return;
+    if (!A || (mode == BATCH_LU && !lu_out) || (mode == BATCH_KERNEL && !k_out) || (mode == BATCH_RANK && !rank_out)) throw EngineError("NULL array");
+    char msg[160];
+    for (int i = 0; i < count; i++) {
+        const struct spasm_csr *M = A[i];
+        const char *bad = nullptr;
+        if (!M) bad = "NULL matrix";
+        else if (M->field->p <= 2 || M->field->p > 0xfffffffbLL) bad = "prime out of range (2 < p <= 0xfffffffb)";
+        else if (M->n < 0 || M->m < 0 || !M->p || M->p[0] != 0) bad = "malformed matrix";
+        else if (!M->x) bad = "matrix without values (A[i]->x == NULL)";
+        else {
+            for (int t = 0; t < M->n && !bad; t++)
+                if (M->p[t + 1] < M->p[t]) bad = "row pointers must not decrease";
+            const i64 nz = bad ? 0 : M->p[M->n];
+            if (!bad && nz > 0 && !M->j) bad = "malformed matrix";
+            const unsigned um = (unsigned)M->m;
+            for (i64 k = 0; k < nz && !bad; k++)
+                if ((unsigned)M->j[k] >= um) bad = "a column index lies outside the matrix";
+        }
+        if (bad) {
+            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
+            throw EngineError(msg);
+        }
+    }
+    require_device();
+    const bool fast_ok = !opts || !opts->L;
+    std::vector<int> fast, slow;
+    for (int i = 0; i < count; i++) {
+        const struct spasm_csr *M = A[i];
+        if (fast_ok && M->n <= BATCH_LIMIT && M->m <= BATCH_LIMIT && (i64)M->n * M->m <= BATCH_LIMIT) fast.push_back(i);
+        else slow.push_back(i);
+    }
+    BatchResults res;
+    if (mode == BATCH_LU) res.lu.assign((size_t)count, nullptr);
+    if (mode == BATCH_KERNEL) res.K.assign((size_t)count, nullptr);
+    std::vector<i64> ranks((size_t)count, 0);
+    i64 *st = g_batch_stats;
+    st[0] = count;
+    st[1] = (i64)fast.size();
+    st[2] = (i64)slow.size();
+
+    const int nf = (int)fast.size();
+    if (nf > 0) {
+        hipStream_t s = nullptr;
+        const size_t budget = batch_budget();
+        // ---- descriptors, classes, chunks
+        std::vector<BatchDesc> desc((size_t)nf);
+        std::vector<unsigned char> cls((size_t)nf);
+        std::vector<i64> ecap((size_t)nf), recw((size_t)nf);
+        i64 rows_total = 0, nnz_total = 0;
+        for (int f = 0; f < nf; f++) {
+            const struct spasm_csr *M = A[fast[(size_t)f]];
+            BatchDesc &d = desc[(size_t)f];
+            memset(&d, 0, sizeof d);
+            d.n = M->n;
+            d.m = M->m;
+            d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
+            d.F = zp_field_make(M->field->p);
+            d.row0 = rows_total;
+            d.nslots = mode == BATCH_LU ? std::min(M->n, M->m) : M->m;
+            const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
+            int c = 0;
+            while (key > kBatchClass[c].cap) c++;
+            cls[(size_t)f] = (unsigned char)c;
+            ecap[(size_t)f] = mode == BATCH_RANK ? 0 : batch_entry_cap(mode, d.n, d.m);
+            recw[(size_t)f] = mode == BATCH_LU ? ((2 + (i64)d.m + d.n + 1) & ~(i64)1) : 2;
+            st[7] = std::max<i64>(st[7], (i64)d.n * d.ld);
+            rows_total += (i64)M->n + 1;
+            nnz_total += M->p[M->n];
+        }
+        std::vector<int> cut; // chunk c = fast matrices cut[c] .. cut[c + 1] - 1 (in batch order)
+        cut.push_back(0);
+        if (mode == BATCH_RANK) {
+            cut.push_back(nf);
+        } else {
+            size_t used = 0;
+            for (int f = 0; f < nf; f++) {
+                // scratch + packed entries, record, row counts and their scan
+                const size_t need = (size_t)ecap[(size_t)f] * 2 * sizeof(int2) + (size_t)recw[(size_t)f] * sizeof(int) + (size_t)desc[(size_t)f].nslots * (sizeof(int) + sizeof(i64d));
+                if (used > 0 && used + need > budget) { cut.push_back(f); used = 0; }
+                used += need;
+            }
+            cut.push_back(nf);
+        }
+        const int nchunks = (int)cut.size() - 1;
+        // inside a chunk the matrices go by class (a stable counting sort), and their slices are laid out in that order
+        std::vector<int> items((size_t)nf);
+        struct ChunkPlan { int hist[BATCH_NCLASS]; i64 slots, recs, ents; };
+        std::vector<ChunkPlan> plan((size_t)nchunks);
+        for (int c = 0; c < nchunks; c++) {
+            ChunkPlan &pl = plan[(size_t)c];
+            memset(&pl, 0, sizeof pl);
+            const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+            for (int f = lo; f < hi; f++) pl.hist[cls[(size_t)f]]++;
+            int at[BATCH_NCLASS], sum = lo;
+            for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += pl.hist[k]; }
+            for (int f = lo; f < hi; f++) items[(size_t)at[cls[(size_t)f]]++] = f;
+            for (int q = lo; q < hi; q++) {
+                BatchDesc &d = desc[(size_t)items[(size_t)q]];
+                d.slot0 = pl.slots;
+                d.rec = pl.recs;
+                d.slice = pl.ents;
+                pl.slots += d.nslots;
+                pl.recs += recw[(size_t)items[(size_t)q]];
+                pl.ents += ecap[(size_t)items[(size_t)q]];
+            }
+        }
+        // ---- one upload: descriptors | items | row pointers | columns | values
+        const size_t o_desc = 0;
+        const size_t o_items = batch_align(o_desc + (size_t)nf * sizeof(BatchDesc));
+        const size_t o_p = batch_align(o_items + (size_t)nf * sizeof(int));
+        const size_t o_j = batch_align(o_p + (size_t)rows_total * sizeof(i64d));
+        const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
+        const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
+        std::vector<unsigned char> stage(in_bytes);
+        memcpy(stage.data() + o_desc, desc.data(), (size_t)nf * sizeof(BatchDesc));
+        memcpy(stage.data() + o_items, items.data(), (size_t)nf * sizeof(int));
+        {
+            i64d *P = (i64d *)(stage.data() + o_p);
+            int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
+            i64 e0 = 0, r0 = 0;
+            for (int f = 0; f < nf; f++) {
+                const struct spasm_csr *M = A[fast[(size_t)f]];
+                const i64 nz = M->p[M->n];
+                for (int t = 0; t <= M->n; t++) P[r0 + t] = (i64d)(e0 + M->p[t]);
+                if (nz > 0) {
+                    memcpy(J + e0, M->j, (size_t)nz * sizeof(int));
+                    memcpy(X + e0, M->x, (size_t)nz * sizeof(int));
+                }
+                r0 += (i64)M->n + 1;
+                e0 += nz;
+            }
+        }
+        DevBuf<unsigned char> in;
+        in.alloc(in_bytes);
+        HIPCHK(hipMemcpyAsync(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, s));
+        BatchArgs a;
+        memset(&a, 0, sizeof a);
+        a.desc = (const BatchDesc *)(in.p + o_desc);
+        a.P = (const i64d *)(in.p + o_p);
+        a.J = (const int *)(in.p + o_j);
+        a.X = (const int *)(in.p + o_x);
+        a.mode = mode;
+        const int *d_items = (const int *)(in.p + o_items);
+        SpgEvents ev;
+        i64 launches = 0, entries = 0;
+        double ms = 0;
+
+        if (mode == BATCH_RANK) {
+            DevBuf<int> drank;
+            drank.alloc((size_t)nf);
+            a.rank = drank.p;
+            HIPCHK(hipEventRecord(ev.e[0], s));
+            int first = 0;
+            for (int k = 0; k < BATCH_NCLASS; k++) {
+                const int cn = plan[0].hist[k];
+                if (cn > 0) { batch_launch_class(k, a, d_items + first, cn, s); launches++; }
+                first += cn;
+            }
+            HIPCHK(hipEventRecord(ev.e[1], s));
+            std::vector<int> hr((size_t)nf);
+            HIPCHK(hipMemcpyAsync(hr.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            ms += ev.ms(0, 1);
+            for (int f = 0; f < nf; f++) ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
+        } else {
+            DevBuf<int2> scratch;
+            DevBuf<unsigned char> out;
+            DevBuf<i64d> rowstart;
+            DevBuf<unsigned char> scan_tmp;
+            std::vector<unsigned char> host;
+            for (int c = 0; c < nchunks; c++) {
+                const ChunkPlan &pl = plan[(size_t)c];
+                const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+                // the chunk's output buffer: row counts (+ 1 for the scan) | records | packed entries
+                const size_t o_rec = batch_align((size_t)(pl.slots + 1) * sizeof(int));
+                const size_t o_ent = batch_align(o_rec + (size_t)pl.recs * sizeof(int));
+                scratch.ensure((size_t)pl.ents + 1);
+                out.ensure(o_ent + (size_t)pl.ents * sizeof(int2) + 16);
+                rowstart.ensure((size_t)pl.slots + 1);
+                int *d_cnt = (int *)out.p;
+                a.cnt = d_cnt;
+                a.rec = (int *)(out.p + o_rec);
+                a.scratch = scratch.p;
+                HIPCHK(hipMemsetAsync(d_cnt + pl.slots, 0, sizeof(int), s));
+                HIPCHK(hipEventRecord(ev.e[0], s));
+                int first = lo;
+                for (int k = 0; k < BATCH_NCLASS; k++) {
+                    if (pl.hist[k] > 0) { batch_launch_class(k, a, d_items + first, pl.hist[k], s); launches++; }
+                    first += pl.hist[k];
+                }
+                {
+                    size_t bytes = 0;
+                    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
+                    scan_tmp.ensure(bytes);
+                    HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
+                    launches++;
+                }
+                i64d total = 0;
+                HIPCHK(hipMemcpyAsync(&total, rowstart.p + pl.slots, sizeof total, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                if (total < 0 || total > pl.ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+                if (total > 0) {
+                    hipLaunchKernelGGL(k_batch_pack, dim3(hi - lo), dim3(64), 0, s, a.desc, d_items + lo, mode, (const int *)a.rec, (const int *)d_cnt,
+                                       (const i64d *)rowstart.p, (const int2 *)scratch.p, (int2 *)(out.p + o_ent));
+                    HIPCHK(hipGetLastError());
+                    launches++;
+                }
+                HIPCHK(hipEventRecord(ev.e[1], s));
+                const size_t out_bytes = o_ent + (size_t)total * sizeof(int2);
+                if (host.size() < out_bytes) host.resize(out_bytes);
+                HIPCHK(hipMemcpyAsync(host.data(), out.p, out_bytes, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipStreamSynchronize(s));
+                ms += ev.ms(0, 1);
+                entries += total;
+                // ---- the chunk's results, in the order of its slices
+                const int *h_cnt = (const int *)host.data();
+                const int *h_rec = (const int *)(host.data() + o_rec);
+                const int2 *h_ent = (const int2 *)(host.data() + o_ent);
+                i64 at = 0;
+                for (int q = lo; q < hi; q++) {
+                    const int f = items[(size_t)q], i = fast[(size_t)f];
+                    const BatchDesc &d = desc[(size_t)f];
+                    const int *rec = h_rec + d.rec, *rc = h_cnt + d.slot0;
+                    const int r = rec[0], n = d.n, m = d.m;
+                    const int nrows = mode == BATCH_LU ? r : m - r;
+                    if (r < 0 || r > std::min(n, m)) throw EngineError("internal error: rank outside its bounds");
+                    i64 nz = 0;
+                    for (int k = 0; k < nrows; k++) nz += rc[k];
+                    if (at + nz > total) throw EngineError("internal error: row counts and entry count disagree");
+                    struct spasm_csr *R = spasm_csr_alloc(nrows, m, nz, d.F.p, true);
+                    if (!R) throw EngineError("out of host memory");
+                    for (int k = 0; k < nrows; k++) R->p[k + 1] = R->p[k] + rc[k];
+                    for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[at + e].x; R->x[e] = h_ent[at + e].y; }
+                    at += nz;
+                    ranks[(size_t)i] = r;
+                    if (mode == BATCH_KERNEL) { res.K[(size_t)i] = R; continue; }
+                    struct spasm_lu *N = (struct spasm_lu *)malloc(sizeof *N);
+                    const int plen = std::max(std::max(n, m), 1);
+                    int *qinv = (int *)malloc(sizeof(int) * (size_t)std::max(m, 1));
+                    int *p = (int *)malloc(sizeof(int) * (size_t)plen);
+                    if (!N || !qinv || !p) { free(N); free(qinv); free(p); spasm_csr_free(R); throw EngineError("out of host memory"); }
+                    if (m > 0) memcpy(qinv, rec + 2, sizeof(int) * (size_t)m);
+                    if (n > 0) memcpy(p, rec + 2 + m, sizeof(int) * (size_t)n);
+                    for (int w = n; w < plen; w++) p[w] = -1;
+                    N->r = r;
+                    N->complete = false;
+                    N->L = nullptr;
+                    N->U = R;
+                    N->qinv = qinv;
+                    N->p = p;
+                    N->Ltmp = nullptr;
+                    res.lu[(size_t)i] = N;
+                }
+            }
+        }
+        st[3] = nchunks;
+        st[4] = launches;
+        st[5] = (i64)(ms * 1000.0);
+        st[6] = entries;
+    }
+    // ---- the others through the general path, one at a time
+    for (int i : slow) {
+        if (mode == BATCH_RANK) {
+            i64 r = -1;
+            if (opts && opts->L) {
+                struct spasm_lu *N = do_echelonize(A[i], opts);
+                r = N->r;
+                spasm_lu_free(N);
+            } else {
+                (void)do_echelonize(A[i], opts, &r);
+            }
+            ranks[(size_t)i] = r;
+        } else if (mode == BATCH_LU) {
+            res.lu[(size_t)i] = do_echelonize(A[i], opts);
+        } else {
+            struct spasm_lu *N = do_echelonize(A[i], opts);
+            try {
+                res.K[(size_t)i] = do_kernel(N);
+            } catch (...) {
+                spasm_lu_free(N);
+                throw;
+            }
+            spasm_lu_free(N);
+        }
+    }
+    if (mode == BATCH_LU) { memcpy(lu_out, res.lu.data(), sizeof(struct spasm_lu *) * (size_t)count); res.lu.clear(); }
+    else if (mode == BATCH_KERNEL) { memcpy(k_out, res.K.data(), sizeof(struct spasm_csr *) * (size_t)count); res.K.clear(); }
+    else memcpy(rank_out, ranks.data(), sizeof(i64) * (size_t)count);
+}
+
+} // namespace
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -7282,6 +7667,38 @@ SPASM_API void spasm_amd_trsolve_free(spasm_amd_trsolve *op)
     DeviceGuard g;
     (void)hipSetDevice(op->dev);
     delete op;
+}
+
+// ---- many small matrices in one call (batch.hpp; engine extension) ----
+#define BATCH_TRY(who, body)                               \
+    spasm_clear_error();                                   \
+    try {                                                  \
+        DeviceGuard g;                                     \
+        body                                               \
+        return 0;                                          \
+    } catch (const std::exception &e) {                    \
+        spasm_set_error("%s: %s", who, e.what());          \
+        return -1;                                         \
+    }
+
+SPASM_API int spasm_amd_echelonize_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_lu **out)
+{
+    BATCH_TRY("spasm_amd_echelonize_batch", batch_run(BATCH_LU, count, A, opts, out, nullptr, nullptr);)
+}
+
+SPASM_API int spasm_amd_rank_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, i64 *rank)
+{
+    BATCH_TRY("spasm_amd_rank_batch", batch_run(BATCH_RANK, count, A, opts, nullptr, nullptr, rank);)
+}
+
+SPASM_API int spasm_amd_kernel_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_csr **K)
+{
+    BATCH_TRY("spasm_amd_kernel_batch", batch_run(BATCH_KERNEL, count, A, opts, nullptr, K, nullptr);)
+}
+
+SPASM_API void spasm_amd_batch_stats(i64 *out)
+{
+    if (out) memcpy(out, g_batch_stats, sizeof g_batch_stats);
 }
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
