@@ -559,9 +559,16 @@ int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 
 /* The device's field arithmetic (csrc/zp.hpp, the restatement of spasm_ZZp.c as SpaSM.jl gives it, src/SpaSM.jl:383-390) on n
  * test vectors: a, b, c are balanced residues; out receives 8 ints per vector: a*b, a*b+c, a+b, a-b, -a, a^-1 (0 for a = 0),
- * a*b through the scatter kernels' lazy product + short reduction, 64*a*b through a lazy accumulator + full reduction.
+ * a*b through the scatter kernels' lazy product + short reduction, 64*a*b through a lazy accumulator + the same reduction.
  * Returns 0 on success. */
 int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, const int *c, int *out);
+
+/* The lazy accumulators of the sparse kernels over their domain: for each of n triples, count[i] >= 0 copies of the lazy product
+ * a[i] * b[i] are summed in the accumulator type the kernels use for this prime (i32 for p < 2^16, i64 above) and reduced as the
+ * kernels reduce a table slot; out[i] receives the balanced residue of count[i] * a[i] * b[i] as long as
+ * count[i] * (p/2 + 256) < 2^31 and count[i] <= 2^20 (p < 2^16; no limit above).  Returns 0 on success; without a device
+ * ("no HIP device") or with bad arguments 1, and out is not written. */
+int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *b, const int *count, int *out);
 
 #ifdef __cplusplus
 }

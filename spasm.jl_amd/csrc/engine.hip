@@ -1475,6 +1475,7 @@ struct Round {
         b.Llen = Llen.p;
         for (int c = 0; c < NCLASS; c++) b.cap[c] = -1;
         for (int c = 0; c < nhash; c++) b.cap[c] = kClasses[c].cap;
+        b.lazy_terms = zp_lazy_terms(F);
         // classes nhash..NHASHMAX-2 are unused (cap -1 never matches); class NHASHMAX-1 collects what fits nowhere
         b.class_count = class_count.p;
         b.class_list = class_list.p;
@@ -7375,6 +7376,36 @@ SPASM_API int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, c
         return 0;
     } catch (const std::exception &e) {
         spasm_set_error("spasm_amd_zp_probe: %s", e.what());
+        return 1;
+    }
+}
+
+// count[i] lazy products a[i] * b[i] summed and reduced as the kernels do it (one result per triple): see k_zp_sum_probe
+SPASM_API int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *b, const int *count, int *out)
+{
+    spasm_clear_error();
+    try {
+        require_device();
+        if (prime <= 2 || prime > 0xfffffffbLL || n < 0) throw EngineError("bad arguments");
+        for (int i = 0; i < n; i++)
+            if (count[i] < 0) throw EngineError("bad arguments (negative count)");
+        const ZpField F = zp_field_make(prime);
+        DevBuf<int> da, db, dc, dout;
+        da.alloc((size_t)n + 1); db.alloc((size_t)n + 1); dc.alloc((size_t)n + 1); dout.alloc((size_t)n + 1);
+        hipStream_t s = nullptr;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(da.p, a, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(db.p, b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(dc.p, count, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            if (F.small) hipLaunchKernelGGL(k_zp_sum_probe<true>, dim3(cdiv(n, 64)), dim3(64), 0, s, F, n, da.p, db.p, dc.p, dout.p);
+            else hipLaunchKernelGGL(k_zp_sum_probe<false>, dim3(cdiv(n, 64)), dim3(64), 0, s, F, n, da.p, db.p, dc.p, dout.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    } catch (const std::exception &e) {
+        spasm_set_error("spasm_amd_zp_sum_probe: %s", e.what());
         return 1;
     }
 }

@@ -786,6 +786,8 @@ struct BinArgs {
     int *fixcnt;             // out: 0 for every row slot (duplicates the streaming kernels leave for k_stream_fix)
     RowDesc *desc;           // [NCLASS][nrows]
     i64d cap[NCLASS];        // class c takes rows with bound <= cap[c]; the last class takes the rest
+    int lazy_terms;          // zp_lazy_terms(F): a row with this many multiplier records (+ its own entry on the same slot) would
+                             // overrun an i32 slot of the LDS tables; it goes to the last class too (i64 slots)
     int *class_count;        // [NCLASS]
     int *class_list;         // [NCLASS][nrows]
 };
@@ -808,6 +810,9 @@ __global__ __launch_bounds__(256) void k_bin(BinArgs a)
             const i64d b = a.bound[t];
             int c = NHASHMAX - 1;
             for (int k = NHASHMAX - 2; k >= 0; k--) if (b <= a.cap[k]) c = k;
+            // the bound is capped by the free columns, the list is not: all its terms may fall on one slot (rows planned along W
+            // have bounds, hence lists, within the largest table and never get here)
+            if (a.Llen[t] >= a.lazy_terms) c = NHASHMAX - 1;
             if (c < a.stream_classes && a.sflag && a.sflag[t]) c += NSTREAM0;
             cls[i] = c;
             pos[i] = atomicAdd(&s_cnt[c], 1);
@@ -1051,22 +1056,24 @@ __device__ __forceinline__ void table_try_n(RowTable<LOGT, SMALL> &tab, RetryLis
     rl.cnt = pos;
 }
 
-// final reduction of a lazy accumulator to the balanced residue
-template <bool SMALL> __device__ __forceinline__ int acc_reduce(const ZpField &F, typename ZpAcc<SMALL>::type acc);
-template <> __device__ __forceinline__ int acc_reduce<true>(const ZpField &F, int acc)
-{
-    // |acc| < 2^31 and p < 2^16: the float quotient is within 1 of the exact one, two corrections finish
-    const int p = (int)F.p, hp = (int)F.halfp, mhp = (int)F.mhalfp;
-    int r = acc - __float2int_rn((float)acc * F.finvp) * p;
-    if (r > hp) r -= p; else if (r < mhp) r += p;
-    if (r > hp) r -= p; else if (r < mhp) r += p;
-    return r;
-}
-template <> __device__ __forceinline__ int acc_reduce<false>(const ZpField &F, long long acc) { return zp_reduce(F, acc); }
-
-// the same for an accumulator that summed at most 2^20 lazy terms (|term| <= 0.51 p): the quotient is then below 2^20,
-// a 24-bit operand, its float estimate is off by < 3 * 2^-24 * 2^20 < 0.2 before rounding, so |r| < 0.7 p and ONE
-// correction lands in the balanced range.  Every row of the LDS classes qualifies (their multiplier lists are far shorter).
+// Final reduction of a lazy accumulator to the balanced residue.
+// SMALL: the accumulator summed at most zp_lazy_terms(F) lazy terms (zp.hpp: |term| <= halfp + 256, so the i32 holds
+// floor((2^31 - 1) / (halfp + 256)) of them without wrapping -- 65043 for p = 65521 -- and never more than 2^20).  The quotient is
+// then below 2^20, a 24-bit operand, its float estimate is off by < 3 * 2^-24 * 2^20 < 0.2 before rounding, so |r| < 0.7 p and
+// ONE correction lands in the balanced range.
+// The reduction checks nothing: whoever fills the accumulator keeps the number of terms in that domain.  Who does, kernel by
+// kernel (DESIGN.md section 5 has the same list):
+//   k_scatter        a slot gets at most one term per multiplier record + the own entry: llen + 1.  k_bin sends a row of a small
+//                    field with llen >= zp_lazy_terms(F) to k_scatter_big (i64 slots, canonical zp_mul terms).  The table size does
+//                    NOT bound llen: bound[] is capped by the free columns, so a row with a long list can sit in the 256-slot class.
+//   retry lists      a retried term is added once, like any other: no extra terms.  A list word keeps 18 bits for the term
+//                    (|term| <= halfp + 256 < 2^15.1, own entries are canonical).
+//   k_combine        a slot (pivot index) gets at most one term per own entry on a pivot column (the indices of a row of Uinv are
+//                    distinct), every such entry brings its own pivot index as a new slot, and a row with more than
+//                    MAXD <= 2048 distinct indices is handed on (to k_solve / k_solve_big, which keep canonical values): <= 2048 + 4 (the check follows every batch of MAXP = 4 entries).
+//   k_wlevel_*       a slot (column) gets the own entry + at most one term per entry merged (columns of a row of W are distinct); rows
+//                    whose bound npn + sum len(W[c]) exceeds half the table (<= 8192 entries) are not built: <= 8192.
+//   streaming twins  no lazy sums: stream_mul returns canonical products, duplicates are merged with zp_add (k_stream_fix).
 template <bool SMALL> __device__ __forceinline__ int acc_reduce_short(const ZpField &F, typename ZpAcc<SMALL>::type acc);
 template <> __device__ __forceinline__ int acc_reduce_short<true>(const ZpField &F, int acc)
 {
@@ -1432,7 +1439,8 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_scatter(ScatterArgs a)
 // ------------------------------------------------------------------------------------------------
 // SCATTER, unbounded rows (last resort): one workgroup per row, a dense i64 accumulator over the
 // columns and a touched-bitmap in global memory (both all-zero between rows), the list of touched
-// columns beside them.  Only rows whose bound exceeds the largest LDS table come here.
+// columns beside them.  Only rows whose bound exceeds the largest LDS table come here, and for p < 2^16 rows whose
+// multiplier list is too long for an i32 slot (k_bin): the terms here are canonical products summed in i64.
 // ------------------------------------------------------------------------------------------------
 struct BigScatterArgs {
     ScatterArgs s;
@@ -2972,7 +2980,7 @@ __global__ __launch_bounds__(256) void k_dense_gemm(int c1, int R, int C, ZpFiel
 // ------------------------------------------------------------------------------------------------
 // Field arithmetic as the kernels use it, one lane per test vector (tests/test_gpu_zp.py compares with Python integers;
 // reference src/SpaSM.jl:383-390).  out[8 * i ..] = mul, axpy, add, sub, neg, inverse, lazy product reduced
-// (mul_lazy + acc_reduce_short: the scatter kernels' path), sum of 64 lazy products reduced (acc_reduce: the hash tables' path).
+// (mul_lazy + acc_reduce_short: the scatter kernels' path), sum of 64 lazy products reduced the same way (the hash tables' path).
 // ------------------------------------------------------------------------------------------------
 template <bool SMALL>
 __global__ void k_zp_probe(ZpField F, int n, const int *__restrict__ a, const int *__restrict__ b, const int *__restrict__ c, int *__restrict__ out)
@@ -2990,6 +2998,20 @@ __global__ void k_zp_probe(ZpField F, int n, const int *__restrict__ a, const in
     o[6] = acc_reduce_short<SMALL>(F, ZpAcc<SMALL>::mul_lazy(F, x, y));
     typename ZpAcc<SMALL>::type acc = 0;
     for (int k = 0; k < 64; k++) acc += ZpAcc<SMALL>::mul_lazy(F, x, y);
-    o[7] = acc_reduce<SMALL>(F, acc);
+    o[7] = acc_reduce_short<SMALL>(F, acc);
+}
+
+// count[i] copies of the lazy product a[i] * b[i] summed in the kernels' accumulator type, then reduced as the hash classes,
+// k_combine and the W build reduce (tests/test_gpu_accumulators.py: counts up to zp_lazy_terms(F), operands at the edges of the
+// balanced range).
+template <bool SMALL>
+__global__ void k_zp_sum_probe(ZpField F, int n, const int *__restrict__ a, const int *__restrict__ b, const int *__restrict__ count, int *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const typename ZpAcc<SMALL>::type term = ZpAcc<SMALL>::mul_lazy(F, a[i], b[i]);
+    typename ZpAcc<SMALL>::type acc = 0;
+    for (int k = count[i]; k > 0; k--) acc += term;
+    out[i] = acc_reduce_short<SMALL>(F, acc);
 }
 

@@ -36,6 +36,18 @@ inline ZpField zp_field_make(int64_t p)
     return F;
 }
 
+// Lazy terms one accumulator may sum before it is reduced (ZpAcc below).  For p < 2^16 a term is at most halfp + 256 in
+// magnitude (zp_small_lazy), so an i32 holds floor((2^31 - 1) / (halfp + 256)) of them without wrapping: 65043 for p = 65521,
+// 129 133 for p = 32749, more for smaller primes; acc_reduce_short is specified for at most 2^20.  An i64 accumulator
+// (|term| < 2^31.1) is not a limit for any list the engine can hold.  Nothing in the kernels counts terms: the number is kept
+// below this by structure (table sizes, list limits) or by routing (k_bin) -- see the list above acc_reduce_short.
+inline int zp_lazy_terms(const ZpField &F)
+{
+    if (!F.small) return 0x7fffffff;
+    const int64_t cap = (((int64_t)1 << 31) - 1) / (F.halfp + 256);
+    return (int)(cap < ((int64_t)1 << 20) ? cap : ((int64_t)1 << 20));
+}
+
 ZP_HD int zp_normalize(const ZpField &F, int64_t x)
 {
     if (x < F.mhalfp) x += F.p;
@@ -90,8 +102,8 @@ ZP_HD int zp_inverse(const ZpField &F, int a)
 
 #if defined(__HIPCC__)
 // Lazy product for accumulation: returns a value congruent to a*b mod p, NOT canonical.
-//   SMALL (p < 2^16): |a*b| < 2^30 fits i32; one float-quotient step leaves |r| <= 0.51 p < 2^15.1,
-//                     so an i32 accumulator absorbs > 60000 terms before the final zp_reduce.
+//   SMALL (p < 2^16): |a*b| < 2^30 fits i32; one float-quotient step leaves |r| <= halfp + 256 < 2^15.1,
+//                     so an i32 accumulator absorbs zp_lazy_terms(F) >= 65043 terms before the final reduction.
 //   general:          i64 product, double quotient, |r| <= 0.51 p < 2^31.1; accumulate in i64.
 template <bool SMALL> struct ZpAcc;
 // x - rn(x/p) * p for p < 2^16 and |x/p| < 2^22 in four full-rate instructions: the quotient is read off the mantissa of

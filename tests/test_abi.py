@@ -96,6 +96,31 @@ def test_hot_path_fails_loudly_without_gpu(S):
         S.transpose(A)
 
 
+def test_field_probes_fail_loudly_without_gpu(S):
+    """spasm_amd_zp_probe / spasm_amd_zp_sum_probe run the field arithmetic ON the device: without one they return an error,
+    name the cause and leave the output alone (there is no host fall-back that could stand in for the kernels)."""
+    lib = S._abi.lib()
+    P = C.POINTER(C.c_int32)
+    a = np.array([1, -1, 32760], dtype=np.int32)
+    b = np.array([32760, 32760, -32760], dtype=np.int32)
+    cnt = np.array([1, 64, 60000], dtype=np.int32)
+    out = np.full(3, 0x55555555, dtype=np.int32)
+    out8 = np.full(24, 0x55555555, dtype=np.int32)
+    ptr = lambda v: v.ctypes.data_as(P)  # noqa: E731
+    rc_sum = lib.spasm_amd_zp_sum_probe(65521, 3, ptr(a), ptr(b), ptr(cnt), ptr(out))
+    err_sum = S._abi.last_error()
+    rc = lib.spasm_amd_zp_probe(65521, 3, ptr(a), ptr(b), ptr(cnt), ptr(out8))
+    err = S._abi.last_error()
+    if lib.spasm_amd_device_count() > 0:
+        assert rc_sum == 0 and rc == 0, (err_sum, err)
+        bal = lambda v: (v + 32760) % 65521 - 32760  # noqa: E731
+        assert out.tolist() == [bal(32760), bal(-32760 * 64), bal(-32760 * 32760 * 60000)]
+        return
+    assert rc_sum != 0 and "spasm_amd_zp_sum_probe" in err_sum and "no HIP device" in err_sum, err_sum
+    assert rc != 0 and "no HIP device" in err, err
+    assert (out == 0x55555555).all() and (out8 == 0x55555555).all()
+
+
 def test_dense_shard_steps_out_of_order_are_errors_not_crashes():
     """The per-process steps of the dense finish over row shards (spasm_amd_dshard_*) without a handle: an error code and a message."""
     import ctypes as C
