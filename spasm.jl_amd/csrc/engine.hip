@@ -163,20 +163,20 @@ template <bool SMALL> void launch_scatter_class(int cls, const ScatterArgs &a, i
 
 // grid = min(rows, resident workgroups): the kernels walk their row list with a grid stride, and a workgroup that is not resident
 // from the start would do its share after everybody else (the LDS bound alone can be above what the registers admit)
-template <int LOGT, int TPR, int WPB, int B, bool SMALL, int MINW = 1, int EPL = 1, int QX = 0, bool BLOOM = false> void launch_wstream(const StreamArgs &a, int nrows, int num_cu, size_t lds, hipStream_t s)
+template <int LOGT, int TPR, int WPB, int B, bool SMALL, int MINW = 1, int EPL = 1, int QX = 0, bool BLOOM = false, bool SEG = false> void launch_wstream(const StreamArgs &a, int nrows, int num_cu, size_t lds, hipStream_t s)
 {
     static int per_cu_dev[kMaxDev] = {0};
     int &per_cu = per_cu_dev[current_device()];
     if (!per_cu) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        HIPCHK(hipFuncSetAttribute((const void *)k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM, SEG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         int nb = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM>, WPB * 64, lds));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM, SEG>, WPB * 64, lds));
         per_cu = std::max(nb, 1);
     }
     if (nrows <= 0) return; // (warm-up call: attributes and occupancy only)
     const int rows_per_block = TPR == 64 ? WPB : 1;
     const int grid = std::max(1, std::min((nrows + rows_per_block - 1) / rows_per_block, num_cu * per_cu));
-    hipLaunchKernelGGL((k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM>), dim3(grid), dim3(WPB * 64), lds, s, a);
+    hipLaunchKernelGGL((k_wstream<LOGT, TPR, WPB, B, SMALL, MINW, EPL, QX, BLOOM, SEG>), dim3(grid), dim3(WPB * 64), lds, s, a);
     HIPCHK(hipGetLastError());
 }
 
@@ -195,6 +195,19 @@ inline int stream_chunk_log()
     const char *e = getenv("SPASM_AMD_CHUNK"); // (read per launch: a test sets it for one case)
     return e && atoi(e) == 128 ? 7 : 6;
 }
+// What the plan along W writes and the streaming kernels read (fixed by the plan: the scatter of a solve takes what its plan cut).
+// Default: SEGMENT records, one per run, the stream cut by position (stream.hpp: k_wplan<.., true>, k_wstream<.., SEG>).  The two
+// measured alternatives keep the chunk records they were built on: SPASM_AMD_CHUNK=128 (two entries per lane) and
+// SPASM_AMD_BLOOM=1 (the filter; chunks of 64).  The streaming kernels of the segment route address the U_PN + own + W buffer by
+// 32-bit BYTE offsets from its base: a buffer of 2^29 entries or more (the engine's own limit is 2^32 entries, prepare_w) also
+// takes chunk records of 64 and the kernels with 64-bit addresses.
+enum StreamMode { STREAM_SEG = 0, STREAM_CHUNK64 = 1, STREAM_BLOOM = 2, STREAM_CHUNK128 = 3 };
+inline StreamMode stream_mode(i64 buffer_entries)
+{
+    if (stream_chunk_log() == 7) return STREAM_CHUNK128;
+    if (stream_bloom()) return STREAM_BLOOM;
+    return buffer_entries < ((i64)1 << 29) ? STREAM_SEG : STREAM_CHUNK64;
+}
 
 // the streaming twins of the hash-table classes (row bounds up to 160 << c): first table of 256 << c words (at most 5/8 full); a
 // wave per row up to 640 entries, then 2 and 4 waves
@@ -202,9 +215,22 @@ const int kNumStreamClasses = 7;
 inline int stream_logt(int c) { return 8 + c; }
 inline int stream_tpr(int c) { return c <= 2 ? 64 : (c == 3 ? 128 : 256); }
 inline int stream_wpb(int c) { return c == 3 ? 2 : 4; }
-template <bool SMALL> void launch_stream_class(int cls, const StreamArgs &a, int nrows, int num_cu, size_t lds, hipStream_t s, int chunk_log = 6)
+template <bool SMALL> void launch_stream_class(int cls, const StreamArgs &a, int nrows, int num_cu, size_t lds, hipStream_t s, StreamMode mode)
 {
-    if (chunk_log == 7) {
+    if (mode == STREAM_SEG) { // (ring slots as for the chunk records: a slot is 64 positions now)
+        switch (cls) {
+        case 0: launch_wstream<8, 64, 4, 4, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 1: launch_wstream<9, 64, 4, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 2: launch_wstream<10, 64, 4, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 3: launch_wstream<11, 128, 2, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 4: launch_wstream<12, 256, 4, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 5: launch_wstream<13, 256, 4, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        case 6: launch_wstream<14, 256, 4, 8, SMALL, 1, 1, 0, false, true>(a, nrows, num_cu, lds, s); break;
+        default: break;
+        }
+        return;
+    }
+    if (mode == STREAM_CHUNK128) {
         switch (cls) { // (ring slots D: chunks of 128 in flight per wave)
         case 0: launch_wstream<8, 64, 4, 2, SMALL, 1, 2>(a, nrows, num_cu, lds, s); break;
         case 1: launch_wstream<9, 64, 4, 4, SMALL, 1, 2>(a, nrows, num_cu, lds, s); break;
@@ -217,7 +243,7 @@ template <bool SMALL> void launch_stream_class(int cls, const StreamArgs &a, int
         }
         return;
     }
-    if (stream_bloom()) { // the duplicate check as a filter (stream.hpp: BLOOM)
+    if (mode == STREAM_BLOOM) { // the duplicate check as a filter (stream.hpp: BLOOM)
         switch (cls) {
         case 0: launch_wstream<8, 64, 4, 4, SMALL, 1, 1, 0, true>(a, nrows, num_cu, lds, s); break;
         case 1: launch_wstream<9, 64, 4, 8, SMALL, 1, 1, 0, true>(a, nrows, num_cu, lds, s); break;
@@ -282,7 +308,7 @@ struct Round {
     DevBuf<int2> fixbuf;            // per row slot: SFIX duplicates found by the streaming kernels, merged by k_stream_fix
     DevBuf<int> fixcnt;
     bool use_stream = true;         // SPASM_AMD_STREAM=0 turns W and the streaming scatter off
-    int chunk_log = 6;              // entries per chunk record of the last plan along W (2^6 or 2^7: stream_chunk_log)
+    StreamMode smode = STREAM_SEG;  // records of the last plan along W: segments, or chunks of 2^6 / 2^7 entries (stream_mode)
     // W = -(I + U_PP)^-1 U_PN (stream.hpp), built level by level of the pivot graph (wlevel.hpp).  One buffer, addressed by 32-bit
     // offsets: [U_PN | the own non-pivot entries of the rows the plan kernel takes | the rows of W]
     bool use_w = false;
@@ -1258,10 +1284,12 @@ struct Round {
             wp.overflow_count = &ctr.p->wplan_reject;
             wp.ctr = ctr.p;
             wp.F = F;
-            chunk_log = stream_chunk_log(); // (the streaming kernels of this solve's scatter take what the plan cut)
-            wp.chunk_log = chunk_log;
+            smode = stream_mode(wbase + wcap); // (the streaming kernels of this solve's scatter take what the plan cut)
+            wp.chunk_log = smode == STREAM_CHUNK128 ? 7 : 6;
             constexpr int TEAM = 16, TPB = 256;
-            hipLaunchKernelGGL((k_wplan<TEAM, TPB>), dim3(std::min(cdiv((i64)nrows * TEAM, TPB), num_cu * 16)), dim3(TPB), 0, stream, wp);
+            const dim3 grid(std::min(cdiv((i64)nrows * TEAM, TPB), num_cu * 16));
+            if (smode == STREAM_SEG) hipLaunchKernelGGL((k_wplan<TEAM, TPB, true>), grid, dim3(TPB), 0, stream, wp);
+            else hipLaunchKernelGGL((k_wplan<TEAM, TPB, false>), grid, dim3(TPB), 0, stream, wp);
             HIPCHK(hipGetLastError());
             if (!use_uinv) {
                 // no Uinv beside W: the rows the plan kernel left are solved by elimination chains
@@ -1453,8 +1481,9 @@ struct Round {
         }
         for (int c = 0; c < std::min(nhash, kNumStreamClasses); c++) {
             const size_t lds = stream_lds_bytes(stream_logt(c), stream_tpr(c), stream_wpb(c));
-            if (F.small) launch_stream_class<true>(c, sa, 0, num_cu, lds, stream, stream_chunk_log());
-            else launch_stream_class<false>(c, sa, 0, num_cu, lds, stream, stream_chunk_log());
+            const StreamMode mode = stream_mode(use_w ? wbase + wcap : 0);
+            if (F.small) launch_stream_class<true>(c, sa, 0, num_cu, lds, stream, mode);
+            else launch_stream_class<false>(c, sa, 0, num_cu, lds, stream, mode);
         }
     }
 
@@ -1568,8 +1597,8 @@ struct Round {
             sa.redo_count = class_count.p + c;
             sa.redo_desc = class_desc.p + (size_t)c * nrows;
             const size_t lds = stream_lds_bytes(stream_logt(c), stream_tpr(c), stream_wpb(c));
-            if (F.small) launch_stream_class<true>(c, sa, nrows, num_cu, lds, s, chunk_log);
-            else launch_stream_class<false>(c, sa, nrows, num_cu, lds, s, chunk_log);
+            if (F.small) launch_stream_class<true>(c, sa, nrows, num_cu, lds, s, smode);
+            else launch_stream_class<false>(c, sa, nrows, num_cu, lds, s, smode);
         };
         // the duplicates the streaming kernels found are merged afterwards, a wave per row that has any
         auto launch_stream_fix = [&](hipStream_t s) {

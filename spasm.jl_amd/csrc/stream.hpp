@@ -319,7 +319,7 @@ struct WPlanArgs {
     int *overflow_count;
     RoundCounters *ctr;
     ZpField F;
-    int chunk_log;             // 6: chunks of 64 entries (a lane of the streaming kernel takes one), 7: of 128 (a lane takes two)
+    int chunk_log;             // chunk records only (k_wplan<.., false>): 6: chunks of 64 entries (a lane of the streaming kernel takes one), 7: of 128 (a lane takes two)
 };
 
 // The plan of a row's Schur row under W: its stream = the row's own entries on non-pivot columns (copied, compacted, behind W: they
@@ -328,7 +328,11 @@ struct WPlanArgs {
 // headers to gather.  TEAM lanes per row; rows of up to 2 TEAM entries (all of config 3) stay in registers between the
 // counting and the writing pass, longer ones are read twice.  Records and own entries are carved from blocks a team takes from
 // the pools now and then (one returning atomic per ~16 rows instead of two per row).
-template <int TEAM, int TPB>
+// SEGP: SEGMENT records -- one per run whatever its length, {start position << 16 | min(len, 0xffff), -multiplier, offset, len}, the
+// shape of a multiplier record, and one for the own entries; a row has 1 + (entries on pivot columns) of them, and up to 64 (a lane
+// of the streaming kernel holds one: k_wstream<.., SEG> cuts the stream by position).  Else one record per chunk of 2^chunk_log
+// entries of a run (the chunks of 128 and the filter kernels read those).
+template <int TEAM, int TPB, bool SEGP>
 __global__ __launch_bounds__(TPB) void k_wplan(WPlanArgs a)
 {
     constexpr int TEAMS = TPB / TEAM;
@@ -396,21 +400,26 @@ __global__ __launch_bounds__(TPB) void k_wplan(WPlanArgs a)
             zero_own |= valid && (e.y == 0 || (isP && ci.y < 0)); // (a row of W that could not be built: the lists take the row)
             const u64d mP = team_ballot<TEAM>(isP);
             if (k0 < 64) pm |= mP << (k0 & 63);
-            int tot;
-            (void)team_incl_scan<TEAM>(isP ? (ci.y + CH - 1) >> CL : 0, tot);
-            C += tot;
+            if constexpr (SEGP) C += __popcll(mP);
+            else {
+                int tot;
+                (void)team_incl_scan<TEAM>(isP ? (ci.y + CH - 1) >> CL : 0, tot);
+                C += tot;
+            }
             nN += __popcll(team_ballot<TEAM>(valid && !isP));
         }
         const bool anyzero = team_ballot<TEAM>(zero_own) != 0;
-        const int own_chunks = (nN + CH - 1) >> CL;
+        const int own_chunks = SEGP ? (nN > 0 ? 1 : 0) : (nN + CH - 1) >> CL;
         const int R = C + own_chunks;
-        const u64d base = take(rpos, rend, (u64d)R, RBLK, a.pool_ctr, a.lpool_cap);
-        const u64d obase = base == ~0ull ? ~0ull : take(opos, oend, (u64d)nN, OBLK, a.own_ctr, a.own_cap);
+        // (segments: a row with more than 64 records goes to the lists; nothing is written for it)
+        const bool fits = !SEGP || R <= 64;
+        const u64d base = take(rpos, rend, fits ? (u64d)R : 0, RBLK, a.pool_ctr, a.lpool_cap);
+        const u64d obase = base == ~0ull ? ~0ull : take(opos, oend, fits ? (u64d)nN : 0, OBLK, a.own_ctr, a.own_cap);
         // ---- pass 2: write.  The stream: own entries first (positions 0 .. nN-1), then the runs in entry order
         i64d run = nN;
         int w = own_chunks, no = 0;
         const bool room = base != ~0ull && obase != ~0ull;
-        for (int k0 = 0; k0 < ln && room; k0 += TEAM) {
+        for (int k0 = 0; k0 < ln && room && fits; k0 += TEAM) {
             const int k = k0 + tl;
             const bool valid = k < ln;
             int2 e = k0 == 0 ? ea : (k0 == TEAM ? eb : make_int2(0, 0));
@@ -427,36 +436,51 @@ __global__ __launch_bounds__(TPB) void k_wplan(WPlanArgs a)
             no += __popcll(mN);
             // its run, when it sits on a pivot column
             const int len = isP ? ci.y : 0;
-            const int nch = (len + CH - 1) >> CL;
-            int tot, ctot;
+            int tot;
             const int incl = team_incl_scan<TEAM>(len, tot);
-            const int cincl = team_incl_scan<TEAM>(nch, ctot);
             const int nm = zp_neg(F, e.y);
             i64d pre = run + incl - len;
-            int4 *out = a.Lpool + base + w + (cincl - nch);
-            for (int q = 0; q < nch; q++) { // (the lanes of a team have runs of different lengths)
-                const int clen = min(CH, len - CH * q);
-                const unsigned px = (pre < 0x8000 ? (unsigned)pre : 0x7fffu) << 16 | (unsigned)clen;
-                out[q] = make_int4((int)px, nm, (int)((unsigned)ci.z + (unsigned)CH * (unsigned)q), clen);
-                pre += clen;
+            if constexpr (SEGP) {
+                // one record per run, empty runs included (they hold no position: nobody selects them)
+                const u64d mP = team_ballot<TEAM>(isP);
+                const unsigned px = (pre < 0x8000 ? (unsigned)pre : 0x7fffu) << 16 | (unsigned)min(len, 0xffff);
+                if (isP) a.Lpool[base + w + __popcll(mP & ((1ull << tl) - 1ull))] = make_int4((int)px, nm, ci.z, len);
+                w += __popcll(mP);
+            } else {
+                const int nch = (len + CH - 1) >> CL;
+                int ctot;
+                const int cincl = team_incl_scan<TEAM>(nch, ctot);
+                int4 *out = a.Lpool + base + w + (cincl - nch);
+                for (int q = 0; q < nch; q++) { // (the lanes of a team have runs of different lengths)
+                    const int clen = min(CH, len - CH * q);
+                    const unsigned px = (pre < 0x8000 ? (unsigned)pre : 0x7fffu) << 16 | (unsigned)clen;
+                    out[q] = make_int4((int)px, nm, (int)((unsigned)ci.z + (unsigned)CH * (unsigned)q), clen);
+                    pre += clen;
+                }
+                w += ctot;
             }
-            w += ctot;
             run += tot;
         }
-        if (room) // the own entries as chunks with multiplier 1 (the scatter kernels subtract record.y times the entry)
-            for (int q = tl; q < own_chunks; q += TEAM) {
-                const int clen = min(CH, nN - CH * q);
-                a.Lpool[base + q] = make_int4((int)(((unsigned)(CH * q) << 16) | (unsigned)clen), -1, (int)(a.own_base + (unsigned)obase + (unsigned)CH * (unsigned)q), clen);
+        if (room && fits) { // the own entries with multiplier 1 (the scatter kernels subtract record.y times the entry)
+            if constexpr (SEGP) {
+                if (tl == 0 && nN > 0) a.Lpool[base] = make_int4(min(nN, 0xffff), -1, (int)(a.own_base + (unsigned)obase), nN);
+            } else {
+                for (int q = tl; q < own_chunks; q += TEAM) {
+                    const int clen = min(CH, nN - CH * q);
+                    a.Lpool[base + q] = make_int4((int)(((unsigned)(CH * q) << 16) | (unsigned)clen), -1, (int)(a.own_base + (unsigned)obase + (unsigned)CH * (unsigned)q), clen);
+                }
             }
+        }
         if (tl == 0) {
             if (base == ~0ull) { // the record pool is full: the host grows it and runs the plan again
                 atomicAdd(&ctr_shard(a.ctr)->lpool_overflow, 1);
                 a.Llen[t] = 0; a.Lstart[t] = 0; a.bound[t] = 0;
             } else {
                 const i64d bound = run;
-                // a wave holds 64 chunk records: one wave per row up to wave_row_bound entries, four beyond.  (No room for the own
-                // entries -- the regions of that buffer fill unevenly -- also sends the row to the lists.)
-                const bool ok = room && bound <= (i64d)a.free_cols && bound <= (i64d)a.max_bound && !anyzero && R <= (bound <= (i64d)a.wave_row_bound ? 64 : 256);
+                // a wave holds 64 records: with chunk records one wave per row up to wave_row_bound entries, four beyond; 64 segments
+                // whatever the length.  (No room for the own entries -- the regions of that buffer fill unevenly -- also sends the
+                // row to the lists.)
+                const bool ok = room && fits && bound <= (i64d)a.free_cols && bound <= (i64d)a.max_bound && !anyzero && R <= (SEGP || bound <= (i64d)a.wave_row_bound ? 64 : 256);
                 if (ok) {
                     a.Lstart[t] = (i64d)base;
                     a.Llen[t] = R;
@@ -491,11 +515,19 @@ typedef int v4i32s __attribute__((ext_vector_type(4)));
 // 2^LOGT-word bitmap with one returning ds_or (one word: the later of two equal columns sees both bits set whatever the interleaving
 // of lanes and waves); an entry whose bits were set already is a SUSPECT (a duplicate, or ~0.1 % of the entries by chance), goes on
 // the row's list, and is resolved at the end of the row against the row itself, read back from where it was just stored.
-template <int LOGT, int TPR, int WPB, int D, bool SMALL, int MINW, int EPL = 1, int QX = 0, bool BLOOM = false>
+// SEG: the records are SEGMENTS (k_wplan<.., true>: one per run, one for the own entries; lane s of `rec` holds segment s) and the
+// stream is cut BY POSITION: chunk g of wave rw is the positions 64 (rw + g NW) .. + 63 of [0, bound), whatever segments they fall
+// into.  Every chunk but a row's last is full.  A lane's segment is the last one that starts at or before its position: the one
+// that holds the chunk's first position is found with one compare and a population count (the starts ascend), every further start
+// inside the chunk costs one compare and two selects; its source is offset[s] + (position - start[s]) as a 32-bit BYTE offset
+// from the buffer's base (the host takes this route only while the buffer is below 2^32 bytes), its multiplier travels in a register
+// beside the ring slot.
+template <int LOGT, int TPR, int WPB, int D, bool SMALL, int MINW, int EPL = 1, int QX = 0, bool BLOOM = false, bool SEG = false>
 __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
 {
     static_assert(EPL == 1 || EPL == 2, "one or two entries per lane");
     static_assert(!(BLOOM && EPL == 2), "the filter is built for one entry per lane");
+    static_assert(!SEG || (EPL == 1 && !BLOOM), "the cut by position is built for one entry per lane and the exact tables");
     constexpr bool WAVE_ROW = (TPR == 64);
     static_assert(WAVE_ROW || TPR == WPB * 64, "a row is owned by one wave or by the whole workgroup");
     constexpr int NW = WAVE_ROW ? 1 : WPB; // waves sharing a row
@@ -532,7 +564,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
     // next.  Unconditional loads with clamped indices (beyond the last row: the last descriptor again).
     RowDesc d, dn, dnn;
     int4 rec, rec_n;
-    auto load_rec = [&](const RowDesc &dd) { return a.Lpool[dd.l_start + min(rw + lane * NW, max(dd.llen - 1, 0))]; };
+    auto load_rec = [&](const RowDesc &dd) { return a.Lpool[dd.l_start + min(SEG ? lane : rw + lane * NW, max(dd.llen - 1, 0))]; };
     d = stream_desc_unpack(stream_desc_load(a.desc + min(first, count - 1)));
     dn = stream_desc_unpack(stream_desc_load(a.desc + min(first + stride, count - 1)));
     dnn = stream_desc_unpack(stream_desc_load(a.desc + min(first + 2 * stride, count - 1)));
@@ -545,6 +577,35 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
     // behind that one belongs to somebody else and is replaced by a copy of the first where it is used)
     typedef typename std::conditional<EPL == 2, int4, int2>::type ring_t;
     ring_t ring[D];
+    int rmul[D]; // SEG: the multiplier of the lane's entry in that slot
+    // SEG: a row's segments as the lookup wants them, lane s for segment s: start (lanes past the last segment: never reached),
+    // offset - start, multiplier
+    struct SegRegs { int st, dl, nm; };
+    auto seg_regs = [&](const int4 &rc, int nseg) {
+        SegRegs r;
+        const int st = (int)((unsigned)rc.x >> 16);
+        r.st = lane < nseg ? st : INT_MAX;
+        r.dl = rc.z - st;
+        r.nm = -rc.y;
+        return r;
+    };
+    // chunk g of this wave in a row of E > 0 entries: the byte offset of the lane's entry in the buffer, and its multiplier
+    auto seg_locate = [&](const SegRegs &r, int E, int g, unsigned &boff, int &mu) {
+        const int p0 = (rw + g * NW) << 6;
+        const int pos = min(p0 + lane, E - 1);
+        const int n1 = __popcll(__ballot(r.st <= p0));      // segments that start at or before the chunk: the last of them holds p0
+        const int n2 = __popcll(__ballot(r.st <= p0 + 63)); // ... or inside it
+        const int cur = max(n1 - 1, 0);
+        int dl = __builtin_amdgcn_readlane(r.dl, cur);
+        mu = __builtin_amdgcn_readlane(r.nm, cur);
+        for (int s = n1; s < n2; s++) { // (wave-uniform; 0.45 rounds per chunk on config 3)
+            const bool in = pos >= __builtin_amdgcn_readlane(r.st, s);
+            dl = in ? __builtin_amdgcn_readlane(r.dl, s) : dl;
+            mu = in ? __builtin_amdgcn_readlane(r.nm, s) : mu;
+        }
+        boff = (unsigned)(pos + dl) << 3;
+    };
+    auto seg_load = [&](unsigned boff) { return *(const int2 *)((const unsigned char *)a.UPN + boff); };
     auto ring_load = [&](unsigned off, int clen) -> ring_t {
         if constexpr (EPL == 2) {
             const v4i32s v = *(const v4i32s *)(a.UPN + (size_t)off + (unsigned)min(2 * lane, clen - 1));
@@ -556,7 +617,23 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
     // (Refilling a group's slots with the next row's chunks as soon as the group has used them -- in front of most of the row's stores
     // instead of behind all of them; the stamps put 15 - 20 % of a row's cycles into the issue of these loads -- was tried in r04:
     // class 1 0.186 ms against 0.200, classes 3 and 4 0.82 - 0.86 / 0.45 - 0.48 against 0.80 / 0.44: 3.41 ms per step against 3.31.)
-    auto request = [&](const int4 &rc, int nmine, bool live) {
+    auto request = [&](const int4 &rc, int nmine, bool live, int nseg, int E) {
+        if constexpr (SEG) {
+            // (the branch only computes addresses: D loads whatever the row.  Slots past the wave's last chunk repeat it.)
+            const SegRegs r = seg_regs(rc, nseg);
+            unsigned boff = 0;
+            int mu = 0;
+#pragma unroll
+            for (int j = 0; j < D; j++) {
+                if (live && j < nmine) seg_locate(r, E, j, boff, mu);
+                // (opaque: a slot that repeats the offset before it would otherwise become a COPY of that slot's registers, which
+                // waits for the load -- lesson (5))
+                asm volatile("" : "+v"(boff));
+                ring[j] = seg_load(boff);
+                rmul[j] = mu;
+            }
+            return;
+        }
 #pragma unroll
         for (int j = 0; j < D; j++) {
             const int g = min(j, max(nmine - 1, 0));
@@ -570,7 +647,9 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
         }
     };
     auto chunks_of = [&](int ll) { return ll > rw ? (ll - rw + NW - 1) / NW : 0; };
-    request(rec, chunks_of(d.llen), first < count);
+    // chunks of a row, all waves together: its records, or its positions in sixty-fours
+    auto row_chunks = [&](const RowDesc &dd) { return SEG ? (dd.bound + 63) >> 6 : dd.llen; };
+    request(rec, chunks_of(row_chunks(d)), first < count, d.llen, d.bound);
 
 #ifdef SPASM_STAMPS
     u64d st_sum[NSTAMP] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -583,7 +662,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
         int *const mrow = misc + par * 8;
         unsigned char *const rowp = (unsigned char *)(a.Sent + d.s_start);
         int mylead = INT_MAX;
-        const int my_chunks = chunks_of(ll);
+        const int my_chunks = chunks_of(row_chunks(d));
         STAMP(0); // requests for the rows ahead
         // ---- the chunks, Q at a time: the first-table CAS of all Q are in flight together, then the second- and third-table ones.
         // The first D come from the ring, in straight-line code (a loop header would cost a vmcnt(0)); what a wave has beyond them
@@ -592,13 +671,22 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
         constexpr int Q = QX ? QX : (EPL == 2 ? (D >= 2 ? 2 : 1) : (D >= 4 ? 4 : D)); // (QX: chunks per group chosen by the caller)
         constexpr int NE = Q * EPL;
         static_assert(D % Q == 0, "whole groups of slots");
-        auto do_group = [&](const ring_t (&e)[Q], int g0, int nthere) {
+        auto do_group = [&](const ring_t (&e)[Q], const int (&emul)[Q], int g0, int nthere) {
             int cc[NE], vv[NE], pp[NE], cl[Q];
             bool there[NE]; // the entry is the lane's own (not a clamped copy)
             unsigned oo[NE], left[NE];
 #pragma unroll
             for (int q = 0; q < Q; q++) {
                 const int g = min(g0 + q, max(my_chunks - 1, 0));
+                if constexpr (SEG) {
+                    const int p0 = (rw + g * NW) << 6;
+                    cl[q] = 64;
+                    cc[q] = e[q].x;
+                    vv[q] = stream_mul<SMALL>(F, emul[q], e[q].y);
+                    pp[q] = min(p0 + lane, E - 1) + 1;
+                    there[q] = p0 + lane < E;
+                    continue;
+                }
                 const int rx = __builtin_amdgcn_readlane(rec.x, g);
                 const int nmul = -__builtin_amdgcn_readlane(rec.y, g);
                 cl[q] = rx & 0xffff;
@@ -697,32 +785,43 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
                     stream_report(stream_outcome(left[k]), oo[k], k / EPL < nthere && there[k], cc[k], vv[k], pp[k], mrow, fix, FCAP, lst);
             }
         };
-        const int next_chunks = chunks_of(dn.llen);
+        const int next_chunks = chunks_of(row_chunks(dn));
         const bool next_live = w + stride < count;
 #pragma unroll
         for (int j0 = 0; j0 < D; j0 += Q) {
             if (j0 < my_chunks) { // (wave-uniform)
                 ring_t e[Q];
+                int em[Q];
 #pragma unroll
-                for (int q = 0; q < Q; q++) e[q] = ring[j0 + q];
-                do_group(e, j0, my_chunks - j0);
+                for (int q = 0; q < Q; q++) { e[q] = ring[j0 + q]; em[q] = SEG ? rmul[j0 + q] : 0; }
+                do_group(e, em, j0, my_chunks - j0);
             }
         }
         if (my_chunks > D) {
+            SegRegs sr = {0, 0, 0};
+            if constexpr (SEG) sr = seg_regs(rec, ll);
             for (int g0 = D; g0 < my_chunks; g0 += Q) {
-                // (more than 64 chunks per wave do not occur: the plan kernel leaves such rows to the lists)
+                // (chunk records: more than 64 chunks per wave do not occur, the plan kernel leaves such rows to the lists)
                 ring_t e[Q];
+                int em[Q];
 #pragma unroll
                 for (int q = 0; q < Q; q++) {
                     const int g = min(g0 + q, my_chunks - 1);
-                    e[q] = ring_load((unsigned)__builtin_amdgcn_readlane(rec.z, g), __builtin_amdgcn_readlane(rec.w, g));
+                    em[q] = 0;
+                    if constexpr (SEG) {
+                        unsigned boff;
+                        seg_locate(sr, E, g, boff, em[q]);
+                        e[q] = seg_load(boff);
+                    } else {
+                        e[q] = ring_load((unsigned)__builtin_amdgcn_readlane(rec.z, g), __builtin_amdgcn_readlane(rec.w, g));
+                    }
                 }
-                do_group(e, g0, my_chunks - g0);
+                do_group(e, em, g0, my_chunks - g0);
             }
         }
         STAMP(1); // the chunks
         // ---- the first D chunks of the NEXT row are requested now: they fly while this row is finished
-        request(rec_n, next_chunks, next_live);
+        request(rec_n, next_chunks, next_live, dn.llen, dn.bound);
         STAMP(2); // requests for the next row
         // ---- end of the row: leftmost column, losers of all tables, duplicates
         mylead = wave_min_i32(mylead);
@@ -826,7 +925,7 @@ __global__ __launch_bounds__(WPB * 64, MINW) void k_wstream(StreamArgs a)
                 c_nnz += (u64d)E;
                 c_rows += E > 0;
                 c_ent += (u64d)E; // entries streamed: the own entries and the runs
-                c_seg += 1 + (u64d)ll;
+                c_seg += 1 + (u64d)row_chunks(d); // rows + chunks processed
             }
         }
         STAMP(3); // end of the row
