@@ -525,7 +525,8 @@ i64 spasm_amd_rank(const struct spasm_csr *A, struct echelonize_opts *opts);
  *   LDS path      a matrix with values, n * m <= 32768 (and opts == NULL or opts->L == 0) is eliminated by ONE workgroup in a dense
  *                 image held in LDS, all such matrices of the batch in a constant number of launches per chunk (a chunk = as many
  *                 matrices as fit the scratch budget, a third of the free device memory; SPASM_AMD_BATCH_SCRATCH_MB lowers it);
- *                 one upload per call; per chunk one download, preceded by the 8-byte read of its size
+ *                 one upload of the matrices and one of their descriptors per call; per chunk one download, preceded by the
+ *                 8-byte read of its size
  *   general path  every other matrix of the batch goes through spasm_echelonize / spasm_kernel as they are, one at a time;
  *                 its result is what the per-matrix call returns under `opts`
  *   echelonize    out[i] is an ordinary spasm_lu (free it with spasm_lu_free).  From the LDS path: r, U r x m with the pivot 1 as the
@@ -553,6 +554,48 @@ int spasm_amd_echelonize_batch(int count, const struct spasm_csr *const *A, stru
 int spasm_amd_rank_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, i64 *rank);
 int spasm_amd_kernel_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_csr **K);
 void spasm_amd_batch_stats(i64 *out);   /* of the last batch call of this thread */
+
+/* ---- Engine extension: a matrix split into its blocks on the device (csrc/blocks.hpp) ----
+ * The blocks of A are the connected components of its row/column graph: vertices are the rows and the columns, every STORED entry
+ * (i, j) joins row i and column j whatever its value (an explicit zero joins; a repeated (i, j) is harmless for the split).  This is
+ * Block(A) of the reference (src/blocks.jl:35-105), computed on the device: a union-find forest with the rule "the larger root goes
+ * under the smaller" gives the components, a stable sort by block number the maps, one copy the blocks.  The handle keeps them as one
+ * concatenated device CSR in the layout the batch entries above read, so the three consumers below start from the descriptors.
+ *   numbering     blocks in ascending order of their smallest vertex, rows before columns; an empty row is a 1 x 0 block, an empty
+ *                 column a 0 x 1 block.  Inside a block the rows and the columns keep their ascending order in A, and the entries of
+ *                 a row keep A's order.  row_pos / col_pos are 0-based positions inside the block.
+ *   create        uploads A (values as they are: any int32) and splits it.  create_dcsr does the same from a resident matrix without
+ *                 an upload, on that matrix's device; the values are the balanced residues the resident matrix holds.
+ *   info          out[11] = blocks, n, m, entries, rows / columns / entries of the block with most entries, blocks without entries,
+ *                 device microseconds of the components, of the numbering, of the split (HIP events)
+ *   shapes        rows[b], cols[b], nnz[b] for the nblocks blocks; any pointer may be NULL
+ *   maps          row_block[n], row_pos[n], col_block[m], col_pos[m], block_rows[n] (the rows of A block after block; those of block b
+ *                 at row_start[b] .. row_start[b + 1]), row_start[nblocks + 1], block_cols[m], col_start[nblocks + 1]; any may be NULL
+ *   fetch         block b as an ordinary spasm_csr over A's prime (free it with spasm_csr_free)
+ *   rank, echelonize, kernel
+ *                 rank[b], out[b], K[b] for the nblocks blocks: exactly what spasm_amd_rank_batch / _echelonize_batch / _kernel_batch
+ *                 return for the list of fetched blocks under the same opts -- the same kernel on the same input -- except that no
+ *                 entry of a block inside the LDS limit is downloaded or uploaded on the way.  Blocks over the limit, and every block
+ *                 when opts->L is set, are fetched and take the general path.  A block without entries needs no launch.
+ *                 spasm_amd_batch_stats describes the call (such a block counts with the LDS path).
+ *   deterministic the components do not depend on how the races of the union-find resolve (csrc/blocks.hpp gives the argument): two
+ *                 handles of one matrix hold byte-identical maps and blocks
+ *   errors        a NULL argument, A->x == NULL, a prime outside 3 .. 0xFFFFFFFB, malformed row pointers ("row pointers must not
+ *                 decrease"), a column index outside the matrix, n + m >= 2^31, a working set that does not fit the free device memory,
+ *                 no device, a block index out of range: NULL / -1, nothing is written to the output arrays, spasm_amd_last_error()
+ *                 names the cause.  spasm_amd_blocks_free(NULL) is a no-op.  A handle belongs to one process. */
+typedef struct spasm_amd_blocks spasm_amd_blocks;
+spasm_amd_blocks *spasm_amd_blocks_create(const struct spasm_csr *A);
+spasm_amd_blocks *spasm_amd_blocks_create_dcsr(const spasm_amd_dcsr *D);
+void spasm_amd_blocks_info(const spasm_amd_blocks *B, i64 *out);
+int spasm_amd_blocks_shapes(const spasm_amd_blocks *B, int *rows, int *cols, i64 *nnz);
+int spasm_amd_blocks_maps(const spasm_amd_blocks *B, int *row_block, int *row_pos, int *col_block, int *col_pos, int *block_rows, i64 *row_start,
+                          int *block_cols, i64 *col_start);
+struct spasm_csr *spasm_amd_blocks_fetch(const spasm_amd_blocks *B, int b);
+int spasm_amd_blocks_rank(spasm_amd_blocks *B, struct echelonize_opts *opts, i64 *rank);
+int spasm_amd_blocks_echelonize(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_lu **out);
+int spasm_amd_blocks_kernel(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_csr **K);
+void spasm_amd_blocks_free(spasm_amd_blocks *B);
 
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);

@@ -7,6 +7,7 @@ from . import _abi, blocks
 from .blocks import Block
 from .api import (
     CSR,
+    DeviceBlocks,
     DeviceCSR,
     LU,
     EchelonizeOpts,
@@ -58,4 +59,5 @@ __all__ = [
     "axpy", "xapy", "SpMV", "dense_forward_solve", "dense_back_solve", "TriangularSolver",
     "DeviceCSR", "submatrix",
     "echelonize_batch", "rank_batch", "kernel_batch", "batch_stats",
+    "DeviceBlocks",
 ]

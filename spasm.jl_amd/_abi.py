@@ -273,6 +273,16 @@ SIGNATURES = {
     "spasm_amd_rank_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(EchelonizeOptsStruct), _P(C.c_int64)]),
     "spasm_amd_kernel_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(EchelonizeOptsStruct), _P(_P(CsrStruct))]),
     "spasm_amd_batch_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_blocks_create": (C.c_void_p, [_P(CsrStruct)]),
+    "spasm_amd_blocks_create_dcsr": (C.c_void_p, [C.c_void_p]),
+    "spasm_amd_blocks_info": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_blocks_shapes": (C.c_int32, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
+    "spasm_amd_blocks_maps": (C.c_int32, [C.c_void_p, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int64), _P(C.c_int32), _P(C.c_int64)]),
+    "spasm_amd_blocks_fetch": (_P(CsrStruct), [C.c_void_p, C.c_int32]),
+    "spasm_amd_blocks_rank": (C.c_int32, [C.c_void_p, _P(EchelonizeOptsStruct), _P(C.c_int64)]),
+    "spasm_amd_blocks_echelonize": (C.c_int32, [C.c_void_p, _P(EchelonizeOptsStruct), _P(_P(LuStruct))]),
+    "spasm_amd_blocks_kernel": (C.c_int32, [C.c_void_p, _P(EchelonizeOptsStruct), _P(_P(CsrStruct))]),
+    "spasm_amd_blocks_free": (None, [C.c_void_p]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -1123,6 +1123,153 @@ def batch_stats():
     return {k: int(v) for k, v in zip(BATCH_STATS, out)}
 
 
+# ---------------------------------------------------------------------------------------------
+# A matrix split into its blocks on the device  (spasm_amd_blocks_*; csrc/blocks.hpp; engine extension)
+# ---------------------------------------------------------------------------------------------
+BLOCKS_INFO = ("blocks", "n", "m", "nnz", "largest_rows", "largest_cols", "largest_nnz", "blocks_without_entries", "components_us", "numbering_us", "split_us")
+
+
+class DeviceBlocks:
+    """The connected components of the row/column graph of A, found and split off on the device (spasm_amd_blocks_*).
+    DeviceBlocks(A) takes a CSR (uploaded; it may be dropped afterwards) or a DeviceCSR (no upload).  The blocks stay on the device
+    as one concatenated CSR in the batch's layout: rank(), echelonize(), kernel() give what rank_batch, echelonize_batch,
+    kernel_batch give for the list of blocks, without the entries crossing the host.  to_block() builds the Block that
+    Block.from_csr(A) builds; maps(), shapes(), fetch(b), info() read the handle."""
+
+    def __init__(self, A):
+        lib = _abi.lib()
+        if isinstance(A, CSR):
+            self._h = lib.spasm_amd_blocks_create(A.data)
+        elif isinstance(A, DeviceCSR):
+            self._h = lib.spasm_amd_blocks_create_dcsr(A._need())
+        else:
+            raise TypeError("a CSR or a DeviceCSR expected")
+        if not self._h:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_create failed")
+        i = self.info()
+        self._nb = i["blocks"]
+        self.shape = (i["n"], i["m"])
+        self.nnz = i["nnz"]
+        self.prime = A.prime
+
+    def _need(self):
+        if not getattr(self, "_h", None):
+            raise SpasmError("the blocks are closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _abi.lib().spasm_amd_blocks_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self._nb
+
+    def info(self):
+        out = (C.c_int64 * 11)()
+        _abi.lib().spasm_amd_blocks_info(self._need(), out)
+        return {k: int(v) for k, v in zip(BLOCKS_INFO, out)}
+
+    def shapes(self):
+        """(rows, cols, nnz): one int32 / int32 / int64 array entry per block"""
+        nb = self._nb
+        rows, cols, nz = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int64)
+        i32, i64 = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+        if _abi.lib().spasm_amd_blocks_shapes(self._need(), rows.ctypes.data_as(i32), cols.ctypes.data_as(i32), nz.ctypes.data_as(i64)) != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_shapes failed")
+        return rows[:nb], cols[:nb], nz[:nb]
+
+    def maps(self):
+        """dict of row_block, row_pos, col_block, col_pos, block_rows, row_start, block_cols, col_start (numpy arrays)"""
+        (n, m), nb = self.shape, self._nb
+        d = {
+            "row_block": np.zeros(max(n, 1), dtype=np.int32), "row_pos": np.zeros(max(n, 1), dtype=np.int32),
+            "col_block": np.zeros(max(m, 1), dtype=np.int32), "col_pos": np.zeros(max(m, 1), dtype=np.int32),
+            "block_rows": np.zeros(max(n, 1), dtype=np.int32), "row_start": np.zeros(nb + 1, dtype=np.int64),
+            "block_cols": np.zeros(max(m, 1), dtype=np.int32), "col_start": np.zeros(nb + 1, dtype=np.int64),
+        }
+        args = [d[k].ctypes.data_as(C.POINTER(C.c_int64 if d[k].dtype == np.int64 else C.c_int32)) for k in d]
+        if _abi.lib().spasm_amd_blocks_maps(self._need(), *args) != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_maps failed")
+        size = {"row_block": n, "row_pos": n, "block_rows": n, "col_block": m, "col_pos": m, "block_cols": m, "row_start": nb + 1, "col_start": nb + 1}
+        return {k: v[: size[k]] for k, v in d.items()}
+
+    def fetch(self, b):
+        ptr = _abi.lib().spasm_amd_blocks_fetch(self._need(), int(b))
+        if not ptr:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_fetch failed")
+        return CSR(ptr)
+
+    def block_maps(self):
+        """(row2block, col2block, block2row, block2col) as a Block holds them"""
+        mp = self.maps()
+        row2block = list(zip(mp["row_block"].tolist(), mp["row_pos"].tolist()))
+        col2block = list(zip(mp["col_block"].tolist(), mp["col_pos"].tolist()))
+        rs, cs = mp["row_start"].tolist(), mp["col_start"].tolist()
+        br, bc = mp["block_rows"].tolist(), mp["block_cols"].tolist()
+        block2row = [br[rs[b]:rs[b + 1]] for b in range(self._nb)]
+        block2col = [bc[cs[b]:cs[b + 1]] for b in range(self._nb)]
+        return row2block, col2block, block2row, block2col
+
+    def to_block(self):
+        """The Block of Block.from_csr(A): the blocks as host matrices and the four maps."""
+        from .blocks import Block
+
+        return Block([self.fetch(b) for b in range(self._nb)], *self.block_maps())
+
+    def _opts(self, opts, kwargs):
+        if opts is None:
+            opts = EchelonizeOpts()
+        for k, v in kwargs.items():
+            if not hasattr(opts.struct, k):
+                raise AttributeError(f"type EchelonizeOpts has no field {k}")
+            setattr(opts.struct, k, v)
+        return opts
+
+    def rank(self, opts=None, verbose=False, **kwargs):
+        """[rank of block b, ...] (spasm_amd_blocks_rank): only the ranks leave the device."""
+        opts = self._opts(opts, kwargs)
+        out = (C.c_int64 * max(self._nb, 1))()
+        with _quiet(not verbose):
+            rc = _abi.lib().spasm_amd_blocks_rank(self._need(), C.byref(opts.struct), out)
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_rank failed")
+        return [int(out[i]) for i in range(self._nb)]
+
+    def echelonize(self, opts=None, verbose=False, **kwargs):
+        """[LU of block b, ...] (spasm_amd_blocks_echelonize)"""
+        opts = self._opts(opts, kwargs)
+        out = (C.POINTER(_abi.LuStruct) * max(self._nb, 1))()
+        with _quiet(not verbose):
+            rc = _abi.lib().spasm_amd_blocks_echelonize(self._need(), C.byref(opts.struct), out)
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_echelonize failed")
+        return [LU(out[i]) for i in range(self._nb)]
+
+    def kernel(self, opts=None, verbose=False, **kwargs):
+        """[kernel of block b, ...] (spasm_amd_blocks_kernel)"""
+        opts = self._opts(opts, kwargs)
+        out = (C.POINTER(_abi.CsrStruct) * max(self._nb, 1))()
+        with _quiet(not verbose):
+            rc = _abi.lib().spasm_amd_blocks_kernel(self._need(), C.byref(opts.struct), out)
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_kernel failed")
+        return [CSR(out[i]) for i in range(self._nb)]
+
+
 def last_rounds(max_rounds=4096):
     """Per-round records of the most recent echelonize call on this thread (engine extension)."""
     buf = (_abi.RoundStats * max_rounds)()

@@ -4,6 +4,9 @@
 src/blocks.jl:35-105); `echelonize`, `rank`, `kernel` then run block by block (:107-139) and
 `to_csr` stitches a block matrix back together (:142-170).  Blocks are independent units: with one
 process per GPU, `owner=(rank, world)` makes a process work only on its share (zero communication).
+
+`api.DeviceBlocks(A)` is the same split done on the device (csrc/blocks.hpp); `echelonize`, `rank`, `kernel` take it in place of
+a Block and run all blocks as one batch whose input never leaves the device.
 """
 import numpy as np
 
@@ -28,9 +31,14 @@ class Block:
         return (len(self.row2block), len(self.col2block))
 
     @classmethod
-    def from_csr(cls, A):
+    def from_csr(cls, A, device=False):
         """Block(A::CSR): union-find over rows and columns joined by the non-zeros (src/blocks.jl:35-105).
-        Blocks are numbered by their smallest member in (rows, then columns) order."""
+        Blocks are numbered by their smallest member in (rows, then columns) order.  device=True: the same Block, found and
+        split on the device (api.DeviceBlocks)."""
+        if device:
+            with api.DeviceBlocks(A) as D:
+                B = D.to_block()
+            return cls(B.blocks, B.row2block, B.col2block, B.block2row, B.block2col)
         n, m = A.shape
         nz = api.nnz(A)
         p, j, x = A.p, A.j[:nz], A.x[:nz]
@@ -79,6 +87,15 @@ class Block:
         return api.CSR.from_rows(rows, m, prime=prime)
 
 
+def _device(block, owner):
+    """True for an api.DeviceBlocks (one handle, one process: no share of it can be given away)"""
+    if not isinstance(block, api.DeviceBlocks):
+        return False
+    if owner is not None:
+        raise ValueError("owner= cannot be combined with DeviceBlocks: a handle belongs to one process")
+    return True
+
+
 def _mine(block, owner):
     """indices of the blocks of the caller's share (owner=(rank, world): b % world == rank) that are present"""
     return [b for b, X in enumerate(block.blocks) if X is not None and (owner is None or b % owner[1] == owner[0])]
@@ -87,7 +104,10 @@ def _mine(block, owner):
 def echelonize(block, owner=None, batched=False, **kwargs):
     """echelonize(block::Block{CSR}) (src/blocks.jl:107-115).  owner=(rank, world): only blocks b % world == rank.
     batched=True: the blocks of the share go through ONE api.echelonize_batch call instead of a loop over api.echelonize (small
-    blocks are then eliminated inside LDS with canonical pivot columns, whatever the pivot-search options say)."""
+    blocks are then eliminated inside LDS with canonical pivot columns, whatever the pivot-search options say).
+    A DeviceBlocks in place of the Block: what Block.from_csr(A) gives with batched=True, from the blocks on the device."""
+    if _device(block, owner):
+        return Block(block.echelonize(**kwargs), *block.block_maps())
     lus = [None] * len(block.blocks)
     mine = _mine(block, owner)
     if batched:
@@ -101,7 +121,9 @@ def echelonize(block, owner=None, batched=False, **kwargs):
 
 def rank(block, owner=None, batched=False, **kwargs):
     """rank(block) = sum of the ranks (src/blocks.jl:117) over the blocks of the share.  batched=True: one api.rank_batch call
-    for the blocks that are still matrices."""
+    for the blocks that are still matrices.  A DeviceBlocks: the ranks of its blocks, from the device."""
+    if _device(block, owner):
+        return sum(block.rank(**kwargs))
     mine = _mine(block, owner)
     if batched:
         mats = [block.blocks[b] for b in mine if isinstance(block.blocks[b], api.CSR)]
@@ -112,7 +134,12 @@ def rank(block, owner=None, batched=False, **kwargs):
 
 def kernel(block, owner=None, batched=False, **kwargs):
     """kernel(block::Block{LU}) (src/blocks.jl:119-137): per-block kernels, rows numbered block after block; a block outside the
-    share (or absent) contributes no rows.  batched=True on a Block of matrices: one api.kernel_batch call for the share."""
+    share (or absent) contributes no rows.  batched=True on a Block of matrices: one api.kernel_batch call for the share.
+    A DeviceBlocks: the kernels of its blocks, from the device."""
+    if _device(block, owner):
+        ks = block.kernel(**kwargs)
+        _, col2block, _, block2col = block.block_maps()
+        return _kernel_block(ks, col2block, block2col)
     ks = [None] * len(block.blocks)
     mine = _mine(block, owner)
     if batched and all(isinstance(block.blocks[b], api.CSR) for b in mine):
@@ -123,10 +150,15 @@ def kernel(block, owner=None, batched=False, **kwargs):
             block = echelonize(block, owner=owner, batched=batched, **kwargs)
         for b in mine:
             ks[b] = api.kernel(block.blocks[b])
+    return _kernel_block(ks, block.col2block, block.block2col)
+
+
+def _kernel_block(ks, col2block, block2col):
+    """the Block of per-block kernels: rows numbered block after block"""
     block2row, row2block, r = [], [], 0
     for b, k in enumerate(ks):
         kn = k.n if k is not None else 0
         block2row.append(list(range(r, r + kn)))
         row2block += [(b, i) for i in range(kn)]
         r += kn
-    return Block(ks, row2block, block.col2block, block2row, block.block2col)
+    return Block(ks, row2block, col2block, block2row, block2col)

@@ -14,6 +14,7 @@
 #include "spgemm.hpp"
 #include "trsolve.hpp"
 #include "batch.hpp"
+#include "blocks.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -6516,8 +6517,9 @@ bool trsolve_once(const struct spasm_csr *T, spasm_ZZp *b, spasm_ZZp *x, const i
 
 // ------------------------------------------------------------------------------------------------
 // Many small matrices in one call (batch.hpp): every matrix whose dense image fits LDS is eliminated by one workgroup; the others,
-// and every matrix of a call that asks for L, go through do_echelonize / do_kernel one at a time.  One upload for the whole
-// batch (descriptors, class-sorted items, row pointers, columns, values in one staging buffer); per chunk of matrices whose
+// and every matrix of a call that asks for L, go through do_echelonize / do_kernel one at a time.  batch_run stages host matrices
+// (one upload of the concatenated row pointers, columns, values) and hands over to batch_fast, which starts from the descriptors
+// and is shared with the blocks of a split matrix that lie on the device already (blocks.hpp); per chunk of matrices whose
 // scratch fits the budget: at most BATCH_NCLASS elimination launches, one scan, one pack, the 8-byte read of the chunk's
 // entry count and one download.
 // ------------------------------------------------------------------------------------------------
@@ -6600,6 +6602,241 @@ struct BatchResults {
 
 inline size_t batch_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
+// A matrix of the LDS path as the descriptors need it: its shape, its prime, and where its n + 1 row pointers start in P.
+struct BatchItem { int n, m; i64 row0; i64 prime; };
+
+// The LDS path from the descriptors on.  fast[f] = place, in the call's list, of the f-th matrix; item[f] describes it; P, J, X: the
+// concatenated CSR on the device (P holds global entry offsets).  Results go to res / ranks at fast[f]; g_batch_stats[3 .. 7] are filled.
+void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, BatchResults &res,
+                std::vector<i64> &ranks)
+{
+    i64 *st = g_batch_stats;
+    const int nf = (int)fast.size();
+    if (nf == 0) return;
+    hipStream_t s = nullptr;
+    const size_t budget = batch_budget();
+    // ---- descriptors, classes, chunks
+    std::vector<BatchDesc> desc((size_t)nf);
+    std::vector<unsigned char> cls((size_t)nf);
+    std::vector<i64> ecap((size_t)nf), recw((size_t)nf);
+    for (int f = 0; f < nf; f++) {
+        const BatchItem *M = &item[(size_t)f];
+        BatchDesc &d = desc[(size_t)f];
+        memset(&d, 0, sizeof d);
+        d.n = M->n;
+        d.m = M->m;
+        d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
+        d.F = zp_field_make(M->prime);
+        d.row0 = M->row0;
+        d.nslots = mode == BATCH_LU ? std::min(M->n, M->m) : M->m;
+        const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
+        int c = 0;
+        while (key > kBatchClass[c].cap) c++;
+        cls[(size_t)f] = (unsigned char)c;
+        ecap[(size_t)f] = mode == BATCH_RANK ? 0 : batch_entry_cap(mode, d.n, d.m);
+        recw[(size_t)f] = mode == BATCH_LU ? ((2 + (i64)d.m + d.n + 1) & ~(i64)1) : 2;
+        st[7] = std::max<i64>(st[7], (i64)d.n * d.ld);
+    }
+    std::vector<int> cut; // chunk c = fast matrices cut[c] .. cut[c + 1] - 1 (in batch order)
+    cut.push_back(0);
+    if (mode == BATCH_RANK) {
+        cut.push_back(nf);
+    } else {
+        size_t used = 0;
+        for (int f = 0; f < nf; f++) {
+            // scratch + packed entries, record, row counts and their scan
+            const size_t need = (size_t)ecap[(size_t)f] * 2 * sizeof(int2) + (size_t)recw[(size_t)f] * sizeof(int) + (size_t)desc[(size_t)f].nslots * (sizeof(int) + sizeof(i64d));
+            if (used > 0 && used + need > budget) { cut.push_back(f); used = 0; }
+            used += need;
+        }
+        cut.push_back(nf);
+    }
+    const int nchunks = (int)cut.size() - 1;
+    // inside a chunk the matrices go by class (a stable counting sort), and their slices are laid out in that order
+    std::vector<int> items((size_t)nf);
+    struct ChunkPlan { int hist[BATCH_NCLASS]; i64 slots, recs, ents; };
+    std::vector<ChunkPlan> plan((size_t)nchunks);
+    for (int c = 0; c < nchunks; c++) {
+        ChunkPlan &pl = plan[(size_t)c];
+        memset(&pl, 0, sizeof pl);
+        const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+        for (int f = lo; f < hi; f++) pl.hist[cls[(size_t)f]]++;
+        int at[BATCH_NCLASS], sum = lo;
+        for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += pl.hist[k]; }
+        for (int f = lo; f < hi; f++) items[(size_t)at[cls[(size_t)f]]++] = f;
+        for (int q = lo; q < hi; q++) {
+            BatchDesc &d = desc[(size_t)items[(size_t)q]];
+            d.slot0 = pl.slots;
+            d.rec = pl.recs;
+            d.slice = pl.ents;
+            pl.slots += d.nslots;
+            pl.recs += recw[(size_t)items[(size_t)q]];
+            pl.ents += ecap[(size_t)items[(size_t)q]];
+        }
+    }
+    // ---- descriptors | items to the device (the row pointers, columns and values are there already)
+    const size_t o_desc = 0;
+    const size_t o_items = batch_align(o_desc + (size_t)nf * sizeof(BatchDesc));
+    const size_t in_bytes = batch_align(o_items + (size_t)nf * sizeof(int));
+    std::vector<unsigned char> stage(in_bytes);
+    memcpy(stage.data() + o_desc, desc.data(), (size_t)nf * sizeof(BatchDesc));
+    memcpy(stage.data() + o_items, items.data(), (size_t)nf * sizeof(int));
+    DevBuf<unsigned char> in;
+    in.alloc(in_bytes);
+    HIPCHK(hipMemcpyAsync(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, s));
+    BatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = (const BatchDesc *)(in.p + o_desc);
+    a.P = dP;
+    a.J = dJ;
+    a.X = dX;
+    a.mode = mode;
+    const int *d_items = (const int *)(in.p + o_items);
+    SpgEvents ev;
+    i64 launches = 0, entries = 0;
+    double ms = 0;
+
+    if (mode == BATCH_RANK) {
+        DevBuf<int> drank;
+        drank.alloc((size_t)nf);
+        a.rank = drank.p;
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        int first = 0;
+        for (int k = 0; k < BATCH_NCLASS; k++) {
+            const int cn = plan[0].hist[k];
+            if (cn > 0) { batch_launch_class(k, a, d_items + first, cn, s); launches++; }
+            first += cn;
+        }
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        std::vector<int> hr((size_t)nf);
+        HIPCHK(hipMemcpyAsync(hr.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        ms += ev.ms(0, 1);
+        for (int f = 0; f < nf; f++) ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
+    } else {
+        DevBuf<int2> scratch;
+        DevBuf<unsigned char> out;
+        DevBuf<i64d> rowstart;
+        DevBuf<unsigned char> scan_tmp;
+        std::vector<unsigned char> host;
+        for (int c = 0; c < nchunks; c++) {
+            const ChunkPlan &pl = plan[(size_t)c];
+            const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+            // the chunk's output buffer: row counts (+ 1 for the scan) | records | packed entries
+            const size_t o_rec = batch_align((size_t)(pl.slots + 1) * sizeof(int));
+            const size_t o_ent = batch_align(o_rec + (size_t)pl.recs * sizeof(int));
+            scratch.ensure((size_t)pl.ents + 1);
+            out.ensure(o_ent + (size_t)pl.ents * sizeof(int2) + 16);
+            rowstart.ensure((size_t)pl.slots + 1);
+            int *d_cnt = (int *)out.p;
+            a.cnt = d_cnt;
+            a.rec = (int *)(out.p + o_rec);
+            a.scratch = scratch.p;
+            HIPCHK(hipMemsetAsync(d_cnt + pl.slots, 0, sizeof(int), s));
+            HIPCHK(hipEventRecord(ev.e[0], s));
+            int first = lo;
+            for (int k = 0; k < BATCH_NCLASS; k++) {
+                if (pl.hist[k] > 0) { batch_launch_class(k, a, d_items + first, pl.hist[k], s); launches++; }
+                first += pl.hist[k];
+            }
+            {
+                size_t bytes = 0;
+                HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
+                scan_tmp.ensure(bytes);
+                HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
+                launches++;
+            }
+            i64d total = 0;
+            HIPCHK(hipMemcpyAsync(&total, rowstart.p + pl.slots, sizeof total, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (total < 0 || total > pl.ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+            if (total > 0) {
+                hipLaunchKernelGGL(k_batch_pack, dim3(hi - lo), dim3(64), 0, s, a.desc, d_items + lo, mode, (const int *)a.rec, (const int *)d_cnt,
+                                   (const i64d *)rowstart.p, (const int2 *)scratch.p, (int2 *)(out.p + o_ent));
+                HIPCHK(hipGetLastError());
+                launches++;
+            }
+            HIPCHK(hipEventRecord(ev.e[1], s));
+            const size_t out_bytes = o_ent + (size_t)total * sizeof(int2);
+            if (host.size() < out_bytes) host.resize(out_bytes);
+            HIPCHK(hipMemcpyAsync(host.data(), out.p, out_bytes, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            ms += ev.ms(0, 1);
+            entries += total;
+            // ---- the chunk's results, in the order of its slices
+            const int *h_cnt = (const int *)host.data();
+            const int *h_rec = (const int *)(host.data() + o_rec);
+            const int2 *h_ent = (const int2 *)(host.data() + o_ent);
+            i64 at = 0;
+            for (int q = lo; q < hi; q++) {
+                const int f = items[(size_t)q], i = fast[(size_t)f];
+                const BatchDesc &d = desc[(size_t)f];
+                const int *rec = h_rec + d.rec, *rc = h_cnt + d.slot0;
+                const int r = rec[0], n = d.n, m = d.m;
+                const int nrows = mode == BATCH_LU ? r : m - r;
+                if (r < 0 || r > std::min(n, m)) throw EngineError("internal error: rank outside its bounds");
+                i64 nz = 0;
+                for (int k = 0; k < nrows; k++) nz += rc[k];
+                if (at + nz > total) throw EngineError("internal error: row counts and entry count disagree");
+                struct spasm_csr *R = spasm_csr_alloc(nrows, m, nz, d.F.p, true);
+                if (!R) throw EngineError("out of host memory");
+                for (int k = 0; k < nrows; k++) R->p[k + 1] = R->p[k] + rc[k];
+                for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[at + e].x; R->x[e] = h_ent[at + e].y; }
+                at += nz;
+                ranks[(size_t)i] = r;
+                if (mode == BATCH_KERNEL) { res.K[(size_t)i] = R; continue; }
+                struct spasm_lu *N = (struct spasm_lu *)malloc(sizeof *N);
+                const int plen = std::max(std::max(n, m), 1);
+                int *qinv = (int *)malloc(sizeof(int) * (size_t)std::max(m, 1));
+                int *p = (int *)malloc(sizeof(int) * (size_t)plen);
+                if (!N || !qinv || !p) { free(N); free(qinv); free(p); spasm_csr_free(R); throw EngineError("out of host memory"); }
+                if (m > 0) memcpy(qinv, rec + 2, sizeof(int) * (size_t)m);
+                if (n > 0) memcpy(p, rec + 2 + m, sizeof(int) * (size_t)n);
+                for (int w = n; w < plen; w++) p[w] = -1;
+                N->r = r;
+                N->complete = false;
+                N->L = nullptr;
+                N->U = R;
+                N->qinv = qinv;
+                N->p = p;
+                N->Ltmp = nullptr;
+                res.lu[(size_t)i] = N;
+            }
+        }
+    }
+    st[3] = nchunks;
+    st[4] = launches;
+    st[5] = (i64)(ms * 1000.0);
+    st[6] = entries;
+}
+
+// one matrix through the general path
+void batch_slow(int mode, int i, const struct spasm_csr *M, struct echelonize_opts *opts, BatchResults &res, std::vector<i64> &ranks)
+{
+    if (mode == BATCH_RANK) {
+        i64 r = -1;
+        if (opts && opts->L) {
+            struct spasm_lu *N = do_echelonize(M, opts);
+            r = N->r;
+            spasm_lu_free(N);
+        } else {
+            (void)do_echelonize(M, opts, &r);
+        }
+        ranks[(size_t)i] = r;
+    } else if (mode == BATCH_LU) {
+        res.lu[(size_t)i] = do_echelonize(M, opts);
+    } else {
+        struct spasm_lu *N = do_echelonize(M, opts);
+        try {
+            res.K[(size_t)i] = do_kernel(N);
+        } catch (...) {
+            spasm_lu_free(N);
+            throw;
+        }
+        spasm_lu_free(N);
+    }
+}
+
 // mode BATCH_LU: lu_out[count]; BATCH_KERNEL: k_out[count]; BATCH_RANK: rank_out[count].  Nothing is written before all is done.
 void batch_run(int mode, int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_lu **lu_out, struct spasm_csr **k_out, i64 *rank_out)
 {
@@ -6646,82 +6883,23 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
     st[1] = (i64)fast.size();
     st[2] = (i64)slow.size();
 
+    // ---- staging of the host matrices: one upload of row pointers | columns | values, concatenated
     const int nf = (int)fast.size();
     if (nf > 0) {
         hipStream_t s = nullptr;
-        const size_t budget = batch_budget();
-        // ---- descriptors, classes, chunks
-        std::vector<BatchDesc> desc((size_t)nf);
-        std::vector<unsigned char> cls((size_t)nf);
-        std::vector<i64> ecap((size_t)nf), recw((size_t)nf);
+        std::vector<BatchItem> item((size_t)nf);
         i64 rows_total = 0, nnz_total = 0;
         for (int f = 0; f < nf; f++) {
             const struct spasm_csr *M = A[fast[(size_t)f]];
-            BatchDesc &d = desc[(size_t)f];
-            memset(&d, 0, sizeof d);
-            d.n = M->n;
-            d.m = M->m;
-            d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
-            d.F = zp_field_make(M->field->p);
-            d.row0 = rows_total;
-            d.nslots = mode == BATCH_LU ? std::min(M->n, M->m) : M->m;
-            const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
-            int c = 0;
-            while (key > kBatchClass[c].cap) c++;
-            cls[(size_t)f] = (unsigned char)c;
-            ecap[(size_t)f] = mode == BATCH_RANK ? 0 : batch_entry_cap(mode, d.n, d.m);
-            recw[(size_t)f] = mode == BATCH_LU ? ((2 + (i64)d.m + d.n + 1) & ~(i64)1) : 2;
-            st[7] = std::max<i64>(st[7], (i64)d.n * d.ld);
+            item[(size_t)f] = BatchItem{M->n, M->m, rows_total, M->field->p};
             rows_total += (i64)M->n + 1;
             nnz_total += M->p[M->n];
         }
-        std::vector<int> cut; // chunk c = fast matrices cut[c] .. cut[c + 1] - 1 (in batch order)
-        cut.push_back(0);
-        if (mode == BATCH_RANK) {
-            cut.push_back(nf);
-        } else {
-            size_t used = 0;
-            for (int f = 0; f < nf; f++) {
-                // scratch + packed entries, record, row counts and their scan
-                const size_t need = (size_t)ecap[(size_t)f] * 2 * sizeof(int2) + (size_t)recw[(size_t)f] * sizeof(int) + (size_t)desc[(size_t)f].nslots * (sizeof(int) + sizeof(i64d));
-                if (used > 0 && used + need > budget) { cut.push_back(f); used = 0; }
-                used += need;
-            }
-            cut.push_back(nf);
-        }
-        const int nchunks = (int)cut.size() - 1;
-        // inside a chunk the matrices go by class (a stable counting sort), and their slices are laid out in that order
-        std::vector<int> items((size_t)nf);
-        struct ChunkPlan { int hist[BATCH_NCLASS]; i64 slots, recs, ents; };
-        std::vector<ChunkPlan> plan((size_t)nchunks);
-        for (int c = 0; c < nchunks; c++) {
-            ChunkPlan &pl = plan[(size_t)c];
-            memset(&pl, 0, sizeof pl);
-            const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
-            for (int f = lo; f < hi; f++) pl.hist[cls[(size_t)f]]++;
-            int at[BATCH_NCLASS], sum = lo;
-            for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += pl.hist[k]; }
-            for (int f = lo; f < hi; f++) items[(size_t)at[cls[(size_t)f]]++] = f;
-            for (int q = lo; q < hi; q++) {
-                BatchDesc &d = desc[(size_t)items[(size_t)q]];
-                d.slot0 = pl.slots;
-                d.rec = pl.recs;
-                d.slice = pl.ents;
-                pl.slots += d.nslots;
-                pl.recs += recw[(size_t)items[(size_t)q]];
-                pl.ents += ecap[(size_t)items[(size_t)q]];
-            }
-        }
-        // ---- one upload: descriptors | items | row pointers | columns | values
-        const size_t o_desc = 0;
-        const size_t o_items = batch_align(o_desc + (size_t)nf * sizeof(BatchDesc));
-        const size_t o_p = batch_align(o_items + (size_t)nf * sizeof(int));
+        const size_t o_p = 0;
         const size_t o_j = batch_align(o_p + (size_t)rows_total * sizeof(i64d));
         const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
         const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
         std::vector<unsigned char> stage(in_bytes);
-        memcpy(stage.data() + o_desc, desc.data(), (size_t)nf * sizeof(BatchDesc));
-        memcpy(stage.data() + o_items, items.data(), (size_t)nf * sizeof(int));
         {
             i64d *P = (i64d *)(stage.data() + o_p);
             int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
@@ -6741,159 +6919,364 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
         DevBuf<unsigned char> in;
         in.alloc(in_bytes);
         HIPCHK(hipMemcpyAsync(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, s));
-        BatchArgs a;
-        memset(&a, 0, sizeof a);
-        a.desc = (const BatchDesc *)(in.p + o_desc);
-        a.P = (const i64d *)(in.p + o_p);
-        a.J = (const int *)(in.p + o_j);
-        a.X = (const int *)(in.p + o_x);
-        a.mode = mode;
-        const int *d_items = (const int *)(in.p + o_items);
-        SpgEvents ev;
-        i64 launches = 0, entries = 0;
-        double ms = 0;
-
-        if (mode == BATCH_RANK) {
-            DevBuf<int> drank;
-            drank.alloc((size_t)nf);
-            a.rank = drank.p;
-            HIPCHK(hipEventRecord(ev.e[0], s));
-            int first = 0;
-            for (int k = 0; k < BATCH_NCLASS; k++) {
-                const int cn = plan[0].hist[k];
-                if (cn > 0) { batch_launch_class(k, a, d_items + first, cn, s); launches++; }
-                first += cn;
-            }
-            HIPCHK(hipEventRecord(ev.e[1], s));
-            std::vector<int> hr((size_t)nf);
-            HIPCHK(hipMemcpyAsync(hr.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            ms += ev.ms(0, 1);
-            for (int f = 0; f < nf; f++) ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
-        } else {
-            DevBuf<int2> scratch;
-            DevBuf<unsigned char> out;
-            DevBuf<i64d> rowstart;
-            DevBuf<unsigned char> scan_tmp;
-            std::vector<unsigned char> host;
-            for (int c = 0; c < nchunks; c++) {
-                const ChunkPlan &pl = plan[(size_t)c];
-                const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
-                // the chunk's output buffer: row counts (+ 1 for the scan) | records | packed entries
-                const size_t o_rec = batch_align((size_t)(pl.slots + 1) * sizeof(int));
-                const size_t o_ent = batch_align(o_rec + (size_t)pl.recs * sizeof(int));
-                scratch.ensure((size_t)pl.ents + 1);
-                out.ensure(o_ent + (size_t)pl.ents * sizeof(int2) + 16);
-                rowstart.ensure((size_t)pl.slots + 1);
-                int *d_cnt = (int *)out.p;
-                a.cnt = d_cnt;
-                a.rec = (int *)(out.p + o_rec);
-                a.scratch = scratch.p;
-                HIPCHK(hipMemsetAsync(d_cnt + pl.slots, 0, sizeof(int), s));
-                HIPCHK(hipEventRecord(ev.e[0], s));
-                int first = lo;
-                for (int k = 0; k < BATCH_NCLASS; k++) {
-                    if (pl.hist[k] > 0) { batch_launch_class(k, a, d_items + first, pl.hist[k], s); launches++; }
-                    first += pl.hist[k];
-                }
-                {
-                    size_t bytes = 0;
-                    HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
-                    scan_tmp.ensure(bytes);
-                    HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
-                    launches++;
-                }
-                i64d total = 0;
-                HIPCHK(hipMemcpyAsync(&total, rowstart.p + pl.slots, sizeof total, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                if (total < 0 || total > pl.ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
-                if (total > 0) {
-                    hipLaunchKernelGGL(k_batch_pack, dim3(hi - lo), dim3(64), 0, s, a.desc, d_items + lo, mode, (const int *)a.rec, (const int *)d_cnt,
-                                       (const i64d *)rowstart.p, (const int2 *)scratch.p, (int2 *)(out.p + o_ent));
-                    HIPCHK(hipGetLastError());
-                    launches++;
-                }
-                HIPCHK(hipEventRecord(ev.e[1], s));
-                const size_t out_bytes = o_ent + (size_t)total * sizeof(int2);
-                if (host.size() < out_bytes) host.resize(out_bytes);
-                HIPCHK(hipMemcpyAsync(host.data(), out.p, out_bytes, hipMemcpyDeviceToHost, s));
-                HIPCHK(hipStreamSynchronize(s));
-                ms += ev.ms(0, 1);
-                entries += total;
-                // ---- the chunk's results, in the order of its slices
-                const int *h_cnt = (const int *)host.data();
-                const int *h_rec = (const int *)(host.data() + o_rec);
-                const int2 *h_ent = (const int2 *)(host.data() + o_ent);
-                i64 at = 0;
-                for (int q = lo; q < hi; q++) {
-                    const int f = items[(size_t)q], i = fast[(size_t)f];
-                    const BatchDesc &d = desc[(size_t)f];
-                    const int *rec = h_rec + d.rec, *rc = h_cnt + d.slot0;
-                    const int r = rec[0], n = d.n, m = d.m;
-                    const int nrows = mode == BATCH_LU ? r : m - r;
-                    if (r < 0 || r > std::min(n, m)) throw EngineError("internal error: rank outside its bounds");
-                    i64 nz = 0;
-                    for (int k = 0; k < nrows; k++) nz += rc[k];
-                    if (at + nz > total) throw EngineError("internal error: row counts and entry count disagree");
-                    struct spasm_csr *R = spasm_csr_alloc(nrows, m, nz, d.F.p, true);
-                    if (!R) throw EngineError("out of host memory");
-                    for (int k = 0; k < nrows; k++) R->p[k + 1] = R->p[k] + rc[k];
-                    for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[at + e].x; R->x[e] = h_ent[at + e].y; }
-                    at += nz;
-                    ranks[(size_t)i] = r;
-                    if (mode == BATCH_KERNEL) { res.K[(size_t)i] = R; continue; }
-                    struct spasm_lu *N = (struct spasm_lu *)malloc(sizeof *N);
-                    const int plen = std::max(std::max(n, m), 1);
-                    int *qinv = (int *)malloc(sizeof(int) * (size_t)std::max(m, 1));
-                    int *p = (int *)malloc(sizeof(int) * (size_t)plen);
-                    if (!N || !qinv || !p) { free(N); free(qinv); free(p); spasm_csr_free(R); throw EngineError("out of host memory"); }
-                    if (m > 0) memcpy(qinv, rec + 2, sizeof(int) * (size_t)m);
-                    if (n > 0) memcpy(p, rec + 2 + m, sizeof(int) * (size_t)n);
-                    for (int w = n; w < plen; w++) p[w] = -1;
-                    N->r = r;
-                    N->complete = false;
-                    N->L = nullptr;
-                    N->U = R;
-                    N->qinv = qinv;
-                    N->p = p;
-                    N->Ltmp = nullptr;
-                    res.lu[(size_t)i] = N;
-                }
-            }
-        }
-        st[3] = nchunks;
-        st[4] = launches;
-        st[5] = (i64)(ms * 1000.0);
-        st[6] = entries;
+        batch_fast(mode, fast, item, (const i64d *)(in.p + o_p), (const int *)(in.p + o_j), (const int *)(in.p + o_x), res, ranks);
     }
     // ---- the others through the general path, one at a time
-    for (int i : slow) {
-        if (mode == BATCH_RANK) {
-            i64 r = -1;
-            if (opts && opts->L) {
-                struct spasm_lu *N = do_echelonize(A[i], opts);
-                r = N->r;
-                spasm_lu_free(N);
-            } else {
-                (void)do_echelonize(A[i], opts, &r);
-            }
-            ranks[(size_t)i] = r;
-        } else if (mode == BATCH_LU) {
-            res.lu[(size_t)i] = do_echelonize(A[i], opts);
-        } else {
-            struct spasm_lu *N = do_echelonize(A[i], opts);
-            try {
-                res.K[(size_t)i] = do_kernel(N);
-            } catch (...) {
-                spasm_lu_free(N);
-                throw;
-            }
-            spasm_lu_free(N);
+    for (int i : slow) batch_slow(mode, i, A[i], opts, res, ranks);
+    if (mode == BATCH_LU) { memcpy(lu_out, res.lu.data(), sizeof(struct spasm_lu *) * (size_t)count); res.lu.clear(); }
+    else if (mode == BATCH_KERNEL) { memcpy(k_out, res.K.data(), sizeof(struct spasm_csr *) * (size_t)count); res.K.clear(); }
+    else memcpy(rank_out, ranks.data(), sizeof(i64) * (size_t)count);
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
+// A matrix split into the connected components of its row/column graph, on the device (blocks.hpp).  The handle owns the maps and
+// the blocks as ONE concatenated CSR in the layout the batch reads, so rank / echelonize / kernel of all blocks start from the
+// descriptors: no entry crosses the host on the way.
+// ------------------------------------------------------------------------------------------------
+struct spasm_amd_blocks {
+    int dev = 0;
+    int n = 0, m = 0, nb = 0;
+    i64 nnz = 0;
+    i64 prime = 0;
+    DevBuf<int> row_block, row_pos, col_block, col_pos, block_rows, block_cols;   // n, n, m, m, n, m
+    DevBuf<i64d> row_start, col_start;                                             // nb + 1 each
+    DevBuf<i64d> P;                                                                // n + nb: rows + 1 pointers per block
+    DevBuf<int> J, X;                                                              // nnz each
+    std::vector<i64> h_row_start, h_col_start, h_nnz, h_ent0;                      // nb + 1, nb + 1, nb, nb + 1 (first entry of a block)
+    i64 us[3] = {0, 0, 0};                                                         // device time: components, numbering, split
+    i64 big[3] = {0, 0, 0};                                                        // the block with most entries: rows, columns, entries
+    i64 empty = 0;                                                                 // blocks without entries
+};
+
+namespace {
+
+template <int PH> void blk_launch_rows(const BlkArgs &a, i64 nnz, hipStream_t s)
+{
+    if (a.n == 0 || nnz == 0) return;
+    const i64 avg = nnz / a.n;
+    if (avg <= 3) hipLaunchKernelGGL((k_blk_rows<PH, 1>), dim3(cdiv(a.n, 256)), dim3(256), 0, s, a);
+    else if (avg <= 24) hipLaunchKernelGGL((k_blk_rows<PH, 8>), dim3(cdiv((i64)a.n * 8, 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_blk_rows<PH, 64>), dim3(cdiv((i64)a.n * 64, 256)), dim3(256), 0, s, a);
+    // the long rows: at most nnz / BLK_LONG of them; the list is complete when phase (a)'s row kernel has ended
+    const int grid = (int)std::min<i64>(std::max<i64>(nnz / BLK_LONG, 1), 4096);
+    hipLaunchKernelGGL((k_blk_long<PH>), dim3(grid), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+}
+
+// sort (block, index) pairs by block, stable; end_bit covers nb - 1
+void blk_sort(DevBuf<unsigned char> &tmp, const int *key, int *key_out, const int *val, int *val_out, int cnt, int nb, hipStream_t s)
+{
+    if (cnt == 0) return;
+    int bits = 1;
+    while (bits < 31 && ((i64)1 << bits) < nb) bits++;
+    size_t bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_out, val, val_out, (size_t)cnt, 0, bits, s));
+    tmp.ensure(bytes);
+    HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, key, key_out, val, val_out, (size_t)cnt, 0, bits, s));
+}
+
+// components, numbering and split of the n x m matrix (dP, dJ, dX) that lies on the current device
+spasm_amd_blocks *blocks_build(int n, int m, i64 nnz, i64 prime, const i64d *dP, const int *dJ, const int *dX)
+{
+    hipStream_t s = nullptr;
+    std::unique_ptr<spasm_amd_blocks> B(new spasm_amd_blocks());
+    HIPCHK(hipGetDevice(&B->dev));
+    B->n = n;
+    B->m = m;
+    B->nnz = nnz;
+    B->prime = prime;
+    const int nv = n + m;
+    {
+        // what the build holds at its peak, next to the matrix: the forest and the flags, two maps and two sort buffers per vertex,
+        // the lengths and their scan (at most n + m blocks), the split entries, the temporaries of rocprim (a key/value copy at most)
+        const double need = 4.0 * nv * 9 + 8.0 * (2.0 * nv + n) * 2 + 8.0 * (double)nnz + 4.0 * (nnz / BLK_LONG + 1) + (double)(1 << 20);
+        size_t fr = 0, tot = 0;
+        HIPCHK(hipMemGetInfo(&fr, &tot));
+        if (need > (double)fr) {
+            char b[200];
+            snprintf(b, sizeof b, "the working set of %.2f GiB does not fit the free device memory (%.2f GiB)", need / 1073741824.0, (double)fr / 1073741824.0);
+            throw EngineError(b);
         }
+    }
+    SpgEvents ev;
+    Scanner scan;
+    DevBuf<unsigned char> sort_tmp;
+    DevBuf<int> parent, root, num, nlong, longrows, iota, key_sorted;
+    parent.alloc((size_t)nv);
+    root.alloc((size_t)nv + 1);
+    num.alloc((size_t)nv + 1);
+    nlong.alloc(1);
+    longrows.alloc((size_t)(nnz / BLK_LONG) + 1);
+    nlong.zero(s);
+    BlkArgs a;
+    memset(&a, 0, sizeof a);
+    a.n = n;
+    a.m = m;
+    a.P = dP;
+    a.J = dJ;
+    a.X = dX;
+    a.parent = parent.p;
+    a.nlong = nlong.p;
+    a.longrows = longrows.p;
+    // ---- components
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    if (nv > 0) {
+        hipLaunchKernelGGL(k_blk_init, dim3(cdiv(nv, 256)), dim3(256), 0, s, nv, parent.p);
+        blk_launch_rows<BLK_MINCOL>(a, nnz, s);
+        blk_launch_rows<BLK_UNITE>(a, nnz, s);
+        hipLaunchKernelGGL(k_blk_flatten, dim3(cdiv(nv, 256)), dim3(256), 0, s, nv, parent.p, root.p);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    // ---- numbering
+    HIPCHK(hipMemsetAsync(root.p + nv, 0, sizeof(int), s));
+    scan.exclusive<int>(root.p, num.p, (size_t)nv + 1, s);
+    int nb = 0;
+    HIPCHK(hipMemcpyAsync(&nb, num.p + nv, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nb < 0 || nb > nv) throw EngineError("internal error: block count outside its bounds");
+    B->nb = nb;
+    B->row_block.alloc((size_t)n);
+    B->row_pos.alloc((size_t)n);
+    B->block_rows.alloc((size_t)n);
+    B->col_block.alloc((size_t)m);
+    B->col_pos.alloc((size_t)m);
+    B->block_cols.alloc((size_t)m);
+    B->row_start.alloc((size_t)nb + 1);
+    B->col_start.alloc((size_t)nb + 1);
+    B->P.alloc((size_t)n + nb);
+    B->J.alloc((size_t)nnz);
+    B->X.alloc((size_t)nnz);
+    DevBuf<i64d> len, bnnz;
+    len.alloc((size_t)n + nb);
+    bnnz.alloc((size_t)nb);
+    len.zero(s);
+    iota.alloc((size_t)std::max(n, m));
+    key_sorted.alloc((size_t)std::max(n, m));
+    if (nv > 0) {
+        hipLaunchKernelGGL(k_blk_label, dim3(cdiv(nv, 256)), dim3(256), 0, s, n, m, (const int *)parent.p, (const int *)num.p, B->row_block.p, B->col_block.p, iota.p);
+        HIPCHK(hipGetLastError());
+    }
+    // columns first: key_sorted is reused, and the rows' pass also fills the row lengths
+    blk_sort(sort_tmp, B->col_block.p, key_sorted.p, iota.p, B->block_cols.p, m, nb, s);
+    hipLaunchKernelGGL(k_blk_starts, dim3(cdiv((i64)nb + 1, 256)), dim3(256), 0, s, nb, m, (const int *)key_sorted.p, B->col_start.p);
+    if (m > 0)
+        hipLaunchKernelGGL(k_blk_pos, dim3(cdiv(m, 256)), dim3(256), 0, s, m, (const int *)key_sorted.p, (const int *)B->block_cols.p, (const i64d *)B->col_start.p, B->col_pos.p,
+                           (const i64d *)nullptr, (i64d *)nullptr);
+    blk_sort(sort_tmp, B->row_block.p, key_sorted.p, iota.p, B->block_rows.p, n, nb, s);
+    hipLaunchKernelGGL(k_blk_starts, dim3(cdiv((i64)nb + 1, 256)), dim3(256), 0, s, nb, n, (const int *)key_sorted.p, B->row_start.p);
+    if (n > 0)
+        hipLaunchKernelGGL(k_blk_pos, dim3(cdiv(n, 256)), dim3(256), 0, s, n, (const int *)key_sorted.p, (const int *)B->block_rows.p, (const i64d *)B->row_start.p, B->row_pos.p, dP,
+                           len.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    // ---- split
+    if (n + nb > 0) scan.exclusive<i64d>(len.p, B->P.p, (size_t)n + nb, s);
+    a.row_block = B->row_block.p;
+    a.row_pos = B->row_pos.p;
+    a.col_pos = B->col_pos.p;
+    a.row_start = B->row_start.p;
+    a.cP = B->P.p;
+    a.cJ = B->J.p;
+    a.cX = B->X.p;
+    blk_launch_rows<BLK_COPY>(a, nnz, s);
+    if (nb > 0) hipLaunchKernelGGL(k_blk_nnz, dim3(cdiv(nb, 256)), dim3(256), 0, s, nb, (const i64d *)B->row_start.p, (const i64d *)B->P.p, bnnz.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e[3], s));
+    B->h_row_start.assign((size_t)nb + 1, 0);
+    B->h_col_start.assign((size_t)nb + 1, 0);
+    B->h_nnz.assign((size_t)nb, 0);
+    B->h_ent0.assign((size_t)nb + 1, 0);
+    static_assert(sizeof(i64d) == sizeof(i64), "starts are copied as they are");
+    HIPCHK(hipMemcpyAsync(B->h_row_start.data(), B->row_start.p, ((size_t)nb + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(B->h_col_start.data(), B->col_start.p, ((size_t)nb + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    if (nb > 0) HIPCHK(hipMemcpyAsync(B->h_nnz.data(), bnnz.p, (size_t)nb * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int k = 0; k < 3; k++) B->us[k] = (i64)(ev.ms(k, k + 1) * 1000.0);
+    if (B->h_row_start[(size_t)nb] != n || B->h_col_start[(size_t)nb] != m) throw EngineError("internal error: the blocks do not cover the matrix");
+    for (int b = 0; b < nb; b++) {
+        const i64 z = B->h_nnz[(size_t)b], r = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], c = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+        if (z < 0 || r < 0 || c < 0) throw EngineError("internal error: a block of negative size");
+        B->h_ent0[(size_t)b + 1] = B->h_ent0[(size_t)b] + z;
+        if (z == 0) B->empty++;
+        if (b == 0 || z > B->big[2]) { B->big[0] = r; B->big[1] = c; B->big[2] = z; }
+    }
+    if (B->h_ent0[(size_t)nb] != nnz) throw EngineError("internal error: the blocks do not hold the entries of the matrix");
+    return B.release();
+}
+
+// the checks that need no device; who names the entry's argument
+void blocks_check_host(const struct spasm_csr *A)
+{
+    if (!A) throw EngineError("NULL matrix");
+    if (!A->x) throw EngineError("matrix without values (A->x == NULL)");
+    if (A->field->p <= 2 || A->field->p > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    if (A->n < 0 || A->m < 0) throw EngineError("malformed matrix");
+    if ((i64)A->n + (i64)A->m >= ((i64)1 << 31)) throw EngineError("n + m must be below 2^31");
+    if (!A->p || A->p[0] != 0) throw EngineError("malformed matrix");
+    for (int i = 0; i < A->n; i++)
+        if (A->p[i + 1] < A->p[i]) throw EngineError("row pointers must not decrease");
+    if (A->p[A->n] > 0 && !A->j) throw EngineError("malformed matrix");
+}
+
+spasm_amd_blocks *blocks_create(const struct spasm_csr *A)
+{
+    blocks_check_host(A);
+    require_device();
+    hipStream_t s = nullptr;
+    const int n = A->n, m = A->m;
+    const i64 nnz = A->p[n];
+    DevBuf<i64d> dp;
+    DevBuf<int> dj, dx, bad;
+    dp.alloc((size_t)n + 1);
+    dj.alloc((size_t)nnz);
+    dx.alloc((size_t)nnz);
+    bad.alloc(1);
+    bad.zero(s);
+    HIPCHK(hipMemcpyAsync(dp.p, A->p, ((size_t)n + 1) * sizeof(i64d), hipMemcpyHostToDevice, s));
+    if (nnz > 0) {
+        HIPCHK(hipMemcpyAsync(dj.p, A->j, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dx.p, A->x, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        // before anything indexes the forest by a column
+        hipLaunchKernelGGL(k_spg_check_cols, dim3((int)std::min<i64>(cdiv(nnz, 256), 65536)), dim3(256), 0, s, (i64d)nnz, m, (const int *)dj.p, bad.p);
+        HIPCHK(hipGetLastError());
+        int hbad = 0;
+        HIPCHK(hipMemcpyAsync(&hbad, bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (hbad) throw EngineError("a column index lies outside the matrix");
+    }
+    return blocks_build(n, m, nnz, A->field->p, dp.p, dj.p, dx.p);
+}
+
+spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D)
+{
+    if (!D) throw EngineError("NULL matrix");
+    if (D->F.p <= 2 || D->F.p > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    if ((i64)D->n + (i64)D->m >= ((i64)1 << 31)) throw EngineError("n + m must be below 2^31");
+    hipStream_t s = nullptr;
+    DevBuf<int> dj, dx;
+    dj.alloc((size_t)D->nnz);
+    dx.alloc((size_t)D->nnz);
+    if (D->nnz > 0) {
+        hipLaunchKernelGGL(k_spg_unpack, dim3((int)std::min<i64>(cdiv(D->nnz, 256), 65536)), dim3(256), 0, s, (i64d)D->nnz, (const int2 *)D->ent.p, dj.p, dx.p);
+        HIPCHK(hipGetLastError());
+    }
+    return blocks_build(D->n, D->m, D->nnz, D->F.p, D->p.p, dj.p, dx.p);
+}
+
+void blocks_need(const spasm_amd_blocks *B)
+{
+    if (!B) throw EngineError("NULL handle");
+}
+
+// block b as a host matrix (the caller frees it)
+struct spasm_csr *blocks_fetch(const spasm_amd_blocks *B, int b)
+{
+    blocks_need(B);
+    if (b < 0 || b >= B->nb) throw EngineError("block index out of range");
+    hipStream_t s = nullptr;
+    const i64 r0 = B->h_row_start[(size_t)b], rn = B->h_row_start[(size_t)b + 1] - r0, cn = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+    const i64 e0 = B->h_ent0[(size_t)b], nz = B->h_nnz[(size_t)b];
+    struct spasm_csr *R = spasm_csr_alloc((int)rn, (int)cn, nz, B->prime, true);
+    if (!R) throw EngineError("out of host memory");
+    try {
+        HIPCHK(hipMemcpyAsync(R->p, B->P.p + r0 + b, ((size_t)rn + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+        if (nz > 0) {
+            HIPCHK(hipMemcpyAsync(R->j, B->J.p + e0, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(R->x, B->X.p + e0, (size_t)nz * sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        for (i64 t = 0; t <= rn; t++) R->p[t] -= e0;
+        if (R->p[0] != 0 || R->p[rn] != nz) throw EngineError("internal error: the row pointers of a block disagree with its size");
+    } catch (...) {
+        spasm_csr_free(R);
+        throw;
+    }
+    return R;
+}
+
+// what the batch returns for an n x m matrix without entries: rank 0; U 0 x m, qinv = -1, p = the rows ascending; the kernel is the
+// whole space, vector t = -1 on column t
+void blocks_empty_result(int mode, int i, int n, int m, i64 prime, BatchResults &res, std::vector<i64> &ranks)
+{
+    ranks[(size_t)i] = 0;
+    if (mode == BATCH_RANK) return;
+    if (mode == BATCH_KERNEL) {
+        struct spasm_csr *K = spasm_csr_alloc(m, m, m, prime, true);
+        if (!K) throw EngineError("out of host memory");
+        for (int t = 0; t < m; t++) { K->p[t + 1] = t + 1; K->j[t] = t; K->x[t] = -1; }
+        res.K[(size_t)i] = K;
+        return;
+    }
+    struct spasm_csr *U = spasm_csr_alloc(0, m, 0, prime, true);
+    struct spasm_lu *N = (struct spasm_lu *)malloc(sizeof *N);
+    const int plen = std::max(std::max(n, m), 1);
+    int *qinv = (int *)malloc(sizeof(int) * (size_t)std::max(m, 1));
+    int *p = (int *)malloc(sizeof(int) * (size_t)plen);
+    if (!U || !N || !qinv || !p) { free(N); free(qinv); free(p); spasm_csr_free(U); throw EngineError("out of host memory"); }
+    for (int c = 0; c < std::max(m, 1); c++) qinv[c] = -1;
+    for (int w = 0; w < plen; w++) p[w] = w < n ? w : -1;
+    N->r = 0;
+    N->complete = false;
+    N->L = nullptr;
+    N->U = U;
+    N->qinv = qinv;
+    N->p = p;
+    N->Ltmp = nullptr;
+    res.lu[(size_t)i] = N;
+}
+
+// rank / echelonize / kernel of every block: the batch with its input on the device already
+void blocks_run(int mode, spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_lu **lu_out, struct spasm_csr **k_out, i64 *rank_out)
+{
+    memset(g_batch_stats, 0, sizeof g_batch_stats);
+    blocks_need(B);
+    if ((mode == BATCH_LU && !lu_out) || (mode == BATCH_KERNEL && !k_out) || (mode == BATCH_RANK && !rank_out)) throw EngineError("NULL array");
+    const int count = B->nb;
+    if (count == 0) return;
+    const bool fast_ok = !opts || !opts->L;
+    std::vector<int> fast, slow, none;
+    std::vector<BatchItem> item;
+    for (int b = 0; b < count; b++) {
+        const i64 rn = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], cn = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+        if (!(fast_ok && rn <= BATCH_LIMIT && cn <= BATCH_LIMIT && rn * cn <= BATCH_LIMIT)) slow.push_back(b);
+        else if (B->h_nnz[(size_t)b] == 0) none.push_back(b);
+        else {
+            fast.push_back(b);
+            item.push_back(BatchItem{(int)rn, (int)cn, B->h_row_start[(size_t)b] + b, B->prime});
+        }
+    }
+    BatchResults res;
+    if (mode == BATCH_LU) res.lu.assign((size_t)count, nullptr);
+    if (mode == BATCH_KERNEL) res.K.assign((size_t)count, nullptr);
+    std::vector<i64> ranks((size_t)count, 0);
+    i64 *st = g_batch_stats;
+    st[0] = count;
+    st[1] = (i64)(fast.size() + none.size()); // (a block without entries belongs to the LDS path, which has nothing to do for it)
+    st[2] = (i64)slow.size();
+    batch_fast(mode, fast, item, B->P.p, B->J.p, B->X.p, res, ranks);
+    for (int b : none)
+        blocks_empty_result(mode, b, (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]), (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]), B->prime, res, ranks);
+    for (int b : slow) {
+        struct spasm_csr *M = blocks_fetch(B, b);
+        try {
+            batch_slow(mode, b, M, opts, res, ranks);
+        } catch (...) {
+            spasm_csr_free(M);
+            throw;
+        }
+        spasm_csr_free(M);
     }
     if (mode == BATCH_LU) { memcpy(lu_out, res.lu.data(), sizeof(struct spasm_lu *) * (size_t)count); res.lu.clear(); }
     else if (mode == BATCH_KERNEL) { memcpy(k_out, res.K.data(), sizeof(struct spasm_csr *) * (size_t)count); res.K.clear(); }
     else memcpy(rank_out, ranks.data(), sizeof(i64) * (size_t)count);
+}
+
+template <class T> void blocks_copy_out(T *dst, const DevBuf<T> &src, size_t cnt, hipStream_t s)
+{
+    if (dst && cnt > 0) HIPCHK(hipMemcpyAsync(dst, src.p, cnt * sizeof(T), hipMemcpyDeviceToHost, s));
 }
 
 } // namespace
@@ -7759,6 +8142,83 @@ SPASM_API int spasm_amd_kernel_batch(int count, const struct spasm_csr *const *A
 SPASM_API void spasm_amd_batch_stats(i64 *out)
 {
     if (out) memcpy(out, g_batch_stats, sizeof g_batch_stats);
+}
+
+// ---- a matrix split into its connected components on the device (blocks.hpp; engine extension) ----
+#define BLOCKS_TRY(who, body, fail)                        \
+    spasm_clear_error();                                   \
+    try {                                                  \
+        DeviceGuard g;                                     \
+        body                                               \
+    } catch (const std::exception &e) {                    \
+        spasm_set_error("%s: %s", who, e.what());          \
+        return fail;                                       \
+    }
+#define BLOCKS_ON(B) if (B) HIPCHK(hipSetDevice((B)->dev));
+
+SPASM_API spasm_amd_blocks *spasm_amd_blocks_create(const struct spasm_csr *A) { BLOCKS_TRY("spasm_amd_blocks_create", return blocks_create(A);, nullptr) }
+
+SPASM_API spasm_amd_blocks *spasm_amd_blocks_create_dcsr(const spasm_amd_dcsr *D)
+{
+    BLOCKS_TRY("spasm_amd_blocks_create_dcsr", BLOCKS_ON(D) return blocks_create_dcsr(D);, nullptr)
+}
+
+SPASM_API void spasm_amd_blocks_info(const spasm_amd_blocks *B, i64 *out)
+{
+    if (!B || !out) return;
+    const i64 v[11] = {B->nb, B->n, B->m, B->nnz, B->big[0], B->big[1], B->big[2], B->empty, B->us[0], B->us[1], B->us[2]};
+    memcpy(out, v, sizeof v);
+}
+
+SPASM_API int spasm_amd_blocks_shapes(const spasm_amd_blocks *B, int *rows, int *cols, i64 *nnz)
+{
+    BLOCKS_TRY("spasm_amd_blocks_shapes", blocks_need(B);
+               for (int b = 0; b < B->nb; b++) {
+                   if (rows) rows[b] = (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]);
+                   if (cols) cols[b] = (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]);
+                   if (nnz) nnz[b] = B->h_nnz[(size_t)b];
+               } return 0;, -1)
+}
+
+SPASM_API int spasm_amd_blocks_maps(const spasm_amd_blocks *B, int *row_block, int *row_pos, int *col_block, int *col_pos, int *block_rows, i64 *row_start,
+                                    int *block_cols, i64 *col_start)
+{
+    BLOCKS_TRY("spasm_amd_blocks_maps", blocks_need(B); BLOCKS_ON(B) hipStream_t s = nullptr;
+               blocks_copy_out(row_block, B->row_block, (size_t)B->n, s); blocks_copy_out(row_pos, B->row_pos, (size_t)B->n, s);
+               blocks_copy_out(col_block, B->col_block, (size_t)B->m, s); blocks_copy_out(col_pos, B->col_pos, (size_t)B->m, s);
+               blocks_copy_out(block_rows, B->block_rows, (size_t)B->n, s); blocks_copy_out(block_cols, B->block_cols, (size_t)B->m, s);
+               HIPCHK(hipStreamSynchronize(s));
+               if (row_start) memcpy(row_start, B->h_row_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
+               if (col_start) memcpy(col_start, B->h_col_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
+               return 0;, -1)
+}
+
+SPASM_API struct spasm_csr *spasm_amd_blocks_fetch(const spasm_amd_blocks *B, int b)
+{
+    BLOCKS_TRY("spasm_amd_blocks_fetch", blocks_need(B); BLOCKS_ON(B) return blocks_fetch(B, b);, nullptr)
+}
+
+SPASM_API int spasm_amd_blocks_rank(spasm_amd_blocks *B, struct echelonize_opts *opts, i64 *rank)
+{
+    BLOCKS_TRY("spasm_amd_blocks_rank", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_RANK, B, opts, nullptr, nullptr, rank); return 0;, -1)
+}
+
+SPASM_API int spasm_amd_blocks_echelonize(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_lu **out)
+{
+    BLOCKS_TRY("spasm_amd_blocks_echelonize", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_LU, B, opts, out, nullptr, nullptr); return 0;, -1)
+}
+
+SPASM_API int spasm_amd_blocks_kernel(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_csr **K)
+{
+    BLOCKS_TRY("spasm_amd_blocks_kernel", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_KERNEL, B, opts, nullptr, K, nullptr); return 0;, -1)
+}
+
+SPASM_API void spasm_amd_blocks_free(spasm_amd_blocks *B)
+{
+    if (!B) return;
+    DeviceGuard g;
+    (void)hipSetDevice(B->dev);
+    delete B;
 }
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
