@@ -597,6 +597,52 @@ int spasm_amd_blocks_echelonize(spasm_amd_blocks *B, struct echelonize_opts *opt
 int spasm_amd_blocks_kernel(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_csr **K);
 void spasm_amd_blocks_free(spasm_amd_blocks *B);
 
+/* ---- Engine extension: X * A = B for many small matrices, and block by block (csrc/solve_batch.hpp) ----
+ * spasm_gesv / spasm_solve need a factorization that carries L, which the LDS path of the batch does not produce, and the general
+ * path costs milliseconds per matrix.  These entries solve X[i] * A[i] = B[i] for `count` systems at once; the systems of one call
+ * may differ in shape and in prime.  A[i] is n_i x m_i, B[i] is K_i x m_i over the same prime (K_i may be 0, rows of B[i] may be
+ * empty), X[i] is K_i x n_i (free it with spasm_csr_free) and ok[i] points to K_i bytes.
+ *   LDS path      a system with m * (n + 1) <= 32768 is solved by workgroups that hold the transposed image of A, augmented by a
+ *                 slab of right-hand sides, in LDS, and eliminate it with the election rule of the batch.  A system with more
+ *                 right-hand sides than its class holds is cut into slabs, one workgroup each; the result does not depend on where
+ *                 the slabs are cut.  Chunks, uploads and downloads as for the batch entries above.
+ *                   ok[i][k] = 1 iff B[i][k] lies in the row space of A[i]
+ *                   ok = 1:  X[i][k] is the UNIQUE solution of x * A[i] = B[i][k] that is zero outside the CANONICAL ROW BASIS of
+ *                            A[i]: row j of A[i] belongs to that basis iff it is not a combination of rows 0 .. j-1
+ *                   ok = 0:  X[i][k] is an empty row
+ *                 X is canonical in the sense of the dcsr contract: columns ascending inside a row, no stored zero, balanced
+ *                 residues, nzmax == nnz == p[n].  Two runs are byte-identical.
+ *   shapes        n = 0: ok[i][k] = 1 iff the row of B is zero mod p; m = 0: every ok = 1; X has no entries.  Neither needs a
+ *                 launch (nor K = 0); such systems count with the LDS path.
+ *   input         values of A and B may be any int32 (reduced on load); rows need not be sorted; a row must not hold a column
+ *                 twice; an explicit zero is allowed
+ *   general path  a system over the limit goes through spasm_echelonize with L set and spasm_gesv as they are.  ok has the same
+ *                 meaning and X[i][k] * A[i] == B[i][k], but the support of X is that factorization's pivotal rows: the
+ *                 canonical-basis guarantee DOES NOT HOLD there.  (Rows without a solution are empty, columns ascend, no stored zero.)
+ *   blocks_solve  X * A = Rhs for the matrix A the handle was split from: Rhs is K x m over the handle's prime, X is K x n, ok has K
+ *                 bytes.  The entries of Rhs are dealt to the blocks by col_block / col_pos on the device (Rhs is uploaded once); block
+ *                 b receives, as right-hand sides, the rows of Rhs that hold an entry in its columns.  Blocks inside the limit are
+ *                 solved from the resident concatenated CSR: no entry of such a block crosses the bus.  Blocks over the limit are
+ *                 fetched and take the general path.  An entry of Rhs that is non-zero mod p on an empty column of A (a 0 x 1
+ *                 block) makes its row unsolvable.  ok[k] is the AND over the blocks; X[k] places each block's solution on the block's
+ *                 rows (block_rows), columns ascending, and is an empty row when ok[k] = 0.  X is put together on the device.
+ *                 The components of A span disjoint column sets, so the union of the blocks' canonical bases is the canonical basis
+ *                 of A: whenever A as a whole is inside the limit, blocks_solve returns BYTE FOR BYTE what spasm_amd_solve_batch
+ *                 returns for (A, Rhs) as one system.
+ *   stats         of the last solve call of this thread: out[8] = systems (blocks_solve: the blocks that received a right-hand side),
+ *                 systems through the LDS path, systems through the general path, jobs (matrix-slab workgroups), kernel launches of
+ *                 the LDS path (eliminations, scans, packs), device microseconds of the LDS path (HIP events; blocks_solve: the split
+ *                 of Rhs, the eliminations and the assembly of X), entries of X written by the LDS path (blocks_solve: entries of X),
+ *                 right-hand-side rows without a solution
+ *   errors        count < 0, a NULL array, a NULL matrix, x == NULL in a matrix, primes of A[i] and B[i] that differ, B[i]->m !=
+ *                 A[i]->m, a column index outside the matrix, malformed row pointers, no device ("no HIP device"), out of memory; for
+ *                 blocks_solve also a NULL handle, Rhs->m != m of the handle, a prime that differs from the handle's: -1, NO output
+ *                 slot is written (neither X nor ok), spasm_amd_last_error() names the function, the cause and the index of the
+ *                 matrix.  count == 0 succeeds (and needs no device).  After success the error text is empty. */
+int spasm_amd_solve_batch(int count, const struct spasm_csr *const *A, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok);
+int spasm_amd_blocks_solve(spasm_amd_blocks *Bk, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok);
+void spasm_amd_solve_stats(i64 *out);   /* of the last solve call of this thread */
+
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 

@@ -283,6 +283,9 @@ SIGNATURES = {
     "spasm_amd_blocks_echelonize": (C.c_int32, [C.c_void_p, _P(EchelonizeOptsStruct), _P(_P(LuStruct))]),
     "spasm_amd_blocks_kernel": (C.c_int32, [C.c_void_p, _P(EchelonizeOptsStruct), _P(_P(CsrStruct))]),
     "spasm_amd_blocks_free": (None, [C.c_void_p]),
+    "spasm_amd_solve_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(_P(CsrStruct)), _P(_P(CsrStruct)), _P(_P(C.c_ubyte))]),
+    "spasm_amd_blocks_solve": (C.c_int32, [C.c_void_p, _P(CsrStruct), _P(_P(CsrStruct)), _P(C.c_ubyte)]),
+    "spasm_amd_solve_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

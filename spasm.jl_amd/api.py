@@ -1269,6 +1269,59 @@ class DeviceBlocks:
             raise SpasmError(_abi.last_error() or "spasm_amd_blocks_kernel failed")
         return [CSR(out[i]) for i in range(self._nb)]
 
+    def solve(self, B, verbose=False):
+        """(X, ok) with X * A == B row by row for the matrix A this handle was split from (spasm_amd_blocks_solve): the columns of B
+        are dealt to the blocks on the device, every block inside the LDS limit is solved from the resident blocks, and X comes back
+        assembled.  Whenever A as a whole is inside the limit this is byte for byte what solve_batch([A], [B]) returns."""
+        if not isinstance(B, CSR):
+            raise TypeError("a CSR expected")
+        if B.m != self.shape[1]:
+            raise ValueError("B needs as many columns as the matrix of the handle")
+        out = C.POINTER(_abi.CsrStruct)()
+        ok = np.zeros(max(B.n, 1), dtype=np.uint8)
+        with _quiet(not verbose):
+            rc = _abi.lib().spasm_amd_blocks_solve(self._need(), B.data, C.byref(out), ok.ctypes.data_as(C.POINTER(C.c_ubyte)))
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_solve failed")
+        return CSR(out), ok[: B.n].astype(np.bool_)
+
+
+# ---------------------------------------------------------------------------------------------
+# X * A = B for many small matrices, and block by block  (spasm_amd_solve_batch / _blocks_solve; csrc/solve_batch.hpp)
+# ---------------------------------------------------------------------------------------------
+SOLVE_STATS = ("systems", "lds_path", "general_path", "jobs", "launches", "device_us", "entries", "unsolved")
+
+
+def solve_batch(mats, rhs, verbose=False):
+    """solve_batch([A, ...], [B, ...]) -> ([X, ...], [ok, ...]) (spasm_amd_solve_batch): X[i] * A[i] == B[i] row by row, ok[i] a
+    np.bool_ array with one flag per row of B[i].  Systems with m * (n + 1) <= 32768 are solved inside LDS: X[i][k] is then the
+    unique solution that is zero outside the canonical row basis of A[i] (the rows that are no combination of the rows before
+    them), and an empty row where ok[i][k] is False.  The others go through echelonize(L=True) + gesv one at a time."""
+    mats, rhs = list(mats), list(rhs)
+    for M in mats + rhs:
+        if not isinstance(M, CSR):
+            raise TypeError("lists of CSR expected")
+    if len(mats) != len(rhs):
+        raise ValueError("as many right-hand sides as matrices expected")
+    cnt = len(mats)
+    arr = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))(*[A.data for A in mats])
+    brr = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))(*[B.data for B in rhs])
+    out = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))()
+    oks = [np.zeros(max(B.n, 1), dtype=np.uint8) for B in rhs]
+    okp = (C.POINTER(C.c_ubyte) * max(cnt, 1))(*[o.ctypes.data_as(C.POINTER(C.c_ubyte)) for o in oks])
+    with _quiet(not verbose):
+        rc = _abi.lib().spasm_amd_solve_batch(cnt, arr, brr, out, okp)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_solve_batch failed")
+    return [CSR(out[i]) for i in range(cnt)], [o[: B.n].astype(np.bool_) for o, B in zip(oks, rhs)]
+
+
+def solve_stats():
+    """Counters of the last solve_batch / DeviceBlocks.solve call of this thread (spasm_amd_solve_stats), keyed by SOLVE_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_solve_stats(out)
+    return {k: int(v) for k, v in zip(SOLVE_STATS, out)}
+
 
 def last_rounds(max_rounds=4096):
     """Per-round records of the most recent echelonize call on this thread (engine extension)."""

@@ -6,7 +6,8 @@ src/blocks.jl:35-105); `echelonize`, `rank`, `kernel` then run block by block (:
 process per GPU, `owner=(rank, world)` makes a process work only on its share (zero communication).
 
 `api.DeviceBlocks(A)` is the same split done on the device (csrc/blocks.hpp); `echelonize`, `rank`, `kernel` take it in place of
-a Block and run all blocks as one batch whose input never leaves the device.
+a Block and run all blocks as one batch whose input never leaves the device.  `solve(block, B)` is the reference's
+sparse_triangular_solve(block::Block{LU{F}}, B) (src/blocks.jl:172-226) without the factorization in between: X with X * A == B.
 """
 import numpy as np
 
@@ -151,6 +152,44 @@ def kernel(block, owner=None, batched=False, **kwargs):
         for b in mine:
             ks[b] = api.kernel(block.blocks[b])
     return _kernel_block(ks, block.col2block, block.block2col)
+
+
+def solve(block, B):
+    """(X, ok) with X * A == B row by row for the matrix A the block was split from (reference src/blocks.jl:172-226, from the
+    matrices instead of their LUs).  A DeviceBlocks goes to the device entry (api.DeviceBlocks.solve).  A host Block of matrices
+    deals the entries of B to the blocks by col2block, solves all blocks with ONE api.solve_batch call and places each block's
+    solution on the block's rows through block2row; a row of B is solvable iff it is in every block, and an entry that is non-zero
+    mod p on an empty column of A (a block without rows) makes its row unsolvable."""
+    if isinstance(block, api.DeviceBlocks):
+        return block.solve(B)
+    if not isinstance(B, api.CSR):
+        raise TypeError("a CSR expected")
+    n, m = block.shape
+    if B.m != m:
+        raise ValueError("B needs as many columns as the block matrix")
+    prime = B.prime
+    K = B.n
+    nb = len(block.blocks)
+    pieces = [dict() for _ in range(nb)]  # block -> {row of B: [(position, value), ...]}, rows in ascending order
+    for k, row in enumerate(B.rows()):
+        p0, p1 = int(B.p[k]), int(B.p[k + 1])
+        for c, v in zip(B.j[p0:p1].tolist(), B.x[p0:p1].tolist()):
+            b, pos = block.col2block[c]
+            pieces[b].setdefault(k, []).append((pos, v))
+    used = [b for b in range(nb) if pieces[b]]
+    for b in used:
+        if not isinstance(block.blocks[b], api.CSR):
+            raise TypeError("a Block of CSR expected")
+    rhs = [api.CSR.from_rows([pieces[b][k] for k in sorted(pieces[b])], block.blocks[b].m, prime=prime) for b in used]
+    xs, oks = api.solve_batch([block.blocks[b] for b in used], rhs)
+    ok = np.ones(K, dtype=np.bool_)
+    rows = [[] for _ in range(K)]
+    for b, Xb, okb in zip(used, xs, oks):
+        for t, (k, xr) in enumerate(zip(sorted(pieces[b]), Xb.rows())):
+            ok[k] &= bool(okb[t])
+            rows[k] += [(block.block2row[b][c], v) for c, v in xr]
+    X = api.CSR.from_rows([sorted(r) if ok[k] else [] for k, r in enumerate(rows)], n, prime=prime)
+    return X, ok
 
 
 def _kernel_block(ks, col2block, block2col):

@@ -15,6 +15,7 @@
 #include "trsolve.hpp"
 #include "batch.hpp"
 #include "blocks.hpp"
+#include "solve_batch.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -7281,6 +7282,697 @@ template <class T> void blocks_copy_out(T *dst, const DevBuf<T> &src, size_t cnt
 
 } // namespace
 
+// ------------------------------------------------------------------------------------------------
+// X * A = B for many small matrices in one call, and block by block for a split matrix (solve_batch.hpp).  A system whose
+// transposed image with one right-hand side fits LDS (m * (n + 1) <= BATCH_LIMIT) is cut into jobs, one per slab of right-hand sides;
+// a job is one workgroup of k_solve_elim.  Per chunk of jobs whose scratch fits the budget: at most BATCH_NCLASS elimination
+// launches, one scan, one pack, the 8-byte read of the chunk's entry count and one download.  The other systems go through
+// do_echelonize with L and do_gesv one at a time.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+thread_local i64 g_solve_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+// a system of the LDS path (n, m, K >= 1): where its row pointers and those of its right-hand sides start, and its first slot
+struct SolveSys { int n, m, K; i64 row0, brow0, slot0; i64 prime; };
+
+inline bool solve_fits(i64 n, i64 m) { return n <= BATCH_LIMIT && m <= BATCH_LIMIT && m * (n + 1) <= BATCH_LIMIT; }
+
+// Class, slab width and stride of a system.  The smallest class that holds all K right-hand sides next to A in one slab; when none
+// does, the largest class and as many as it holds (a job repeats the elimination of A, so wide slabs are what saves work).  Stride:
+// solve_batch.hpp, "Row stride".
+void solve_shape(int n, int m, int K, int &cls, int &w, int &ld)
+{
+    int c = 0;
+    i64 fit = 0;
+    for (;; c++) {
+        fit = kBatchClass[c].cap / m - n; // right-hand sides the class holds next to A (>= 1 in the last class: solve_fits)
+        if (fit >= K || c == BATCH_NCLASS - 1) break;
+    }
+    w = (int)std::min<i64>(K, fit);
+    const int W = n + w;
+    ld = W;
+    if (W % 2 == 0) {
+        if ((i64)m * (W + 1) <= kBatchClass[c].cap) ld = W + 1;
+        else if (w < K && w > 1) { w--; ld = n + w; }
+    }
+    cls = c;
+}
+
+// the jobs of the systems, in (system, slab) order; slots and slices are global here (solve_chunks makes them relative to a chunk)
+void solve_jobs(const std::vector<SolveSys> &sys, std::vector<SolveDesc> &desc, std::vector<unsigned char> &cls, std::vector<i64> &ecap)
+{
+    for (const SolveSys &S : sys) {
+        int c = 0, w = 0, ld = 0;
+        solve_shape(S.n, S.m, S.K, c, w, ld);
+        for (int t0 = 0; t0 < S.K; t0 += w) {
+            SolveDesc d;
+            memset(&d, 0, sizeof d);
+            d.row0 = S.row0;
+            d.brow0 = S.brow0 + t0;
+            d.slot0 = S.slot0 + t0;
+            d.n = S.n;
+            d.m = S.m;
+            d.w = std::min(w, S.K - t0);
+            d.ld = ld;
+            d.F = zp_field_make(S.prime);
+            desc.push_back(d);
+            cls.push_back((unsigned char)c);
+            ecap.push_back((i64)d.w * (std::min(S.n, S.m) + 1));
+        }
+    }
+}
+
+template <int BS> void solve_launch(const SolveBatchArgs &a, int nitems, size_t lds, hipStream_t s)
+{
+    static bool attr_done[kMaxDev] = {false};
+    bool &done = attr_done[current_device()];
+    if (!done) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_solve_elim<BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
+    }
+    hipLaunchKernelGGL((k_solve_elim<BS>), dim3(nitems), dim3(BS), lds, s, a);
+}
+
+void solve_launch_class(int cls, SolveBatchArgs a, const int *items, int nitems, hipStream_t s)
+{
+    a.items = items;
+    a.cap = kBatchClass[cls].cap;
+    batch_layout(cls, a.bw, a.rmax);
+    const size_t lds = (size_t)batch_lds_words(a.cap, a.bw, a.rmax) * sizeof(int);
+    switch (cls) {
+    case 0: solve_launch<64>(a, nitems, lds, s); break;
+    case 1: solve_launch<128>(a, nitems, lds, s); break;
+    case 2: solve_launch<256>(a, nitems, lds, s); break;
+    default: solve_launch<512>(a, nitems, lds, s); break;
+    }
+    HIPCHK(hipGetLastError());
+}
+
+// jobs lo .. hi by class (a stable counting sort into items[lo .. hi)), one launch per class that occurs; returns the launches
+int solve_launch_jobs(const std::vector<unsigned char> &cls, int lo, int hi, std::vector<int> &items, int *d_items, const SolveBatchArgs &a, hipStream_t s)
+{
+    int hist[BATCH_NCLASS] = {0, 0, 0, 0}, at[BATCH_NCLASS], sum = lo, launches = 0;
+    for (int q = lo; q < hi; q++) hist[cls[(size_t)q]]++;
+    for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += hist[k]; }
+    for (int q = lo; q < hi; q++) items[(size_t)at[cls[(size_t)q]]++] = q;
+    HIPCHK(hipMemcpyAsync(d_items + lo, items.data() + lo, (size_t)(hi - lo) * sizeof(int), hipMemcpyHostToDevice, s));
+    int first = lo;
+    for (int k = 0; k < BATCH_NCLASS; k++) {
+        if (hist[k] > 0) { solve_launch_class(k, a, d_items + first, hist[k], s); launches++; }
+        first += hist[k];
+    }
+    return launches;
+}
+
+// The LDS path of spasm_amd_solve_batch from the systems on: h_cnt / h_ok per slot, h_ent the rows of X back to back in slot order.
+void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, const int *dJ, const int *dX, const i64d *dBP, const int *dBJ, const int *dBX,
+                std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok, std::vector<int2> &h_ent)
+{
+    i64 *st = g_solve_stats;
+    if (sys.empty()) return;
+    hipStream_t s = nullptr;
+    const size_t budget = batch_budget();
+    std::vector<SolveDesc> desc;
+    std::vector<unsigned char> cls;
+    std::vector<i64> ecap;
+    solve_jobs(sys, desc, cls, ecap);
+    const int nj = (int)desc.size();
+    st[3] = nj;
+    // ---- chunks of consecutive jobs; slots and slices relative to the chunk
+    std::vector<int> cut;
+    cut.push_back(0);
+    {
+        size_t used = 0;
+        for (int q = 0; q < nj; q++) {
+            // scratch + packed entries, and per slot: count, its scan, source, ok
+            const size_t need = (size_t)ecap[(size_t)q] * 2 * sizeof(int2) + (size_t)desc[(size_t)q].w * (sizeof(int) + 2 * sizeof(i64d) + 1);
+            if (used > 0 && used + need > budget) { cut.push_back(q); used = 0; }
+            used += need;
+        }
+        cut.push_back(nj);
+    }
+    const int nchunks = (int)cut.size() - 1;
+    std::vector<i64> c_slot0((size_t)nchunks), c_slots((size_t)nchunks), c_ents((size_t)nchunks);
+    for (int c = 0; c < nchunks; c++) {
+        const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+        const i64 s0 = desc[(size_t)lo].slot0;
+        i64 ents = 0;
+        for (int q = lo; q < hi; q++) {
+            desc[(size_t)q].slot0 -= s0;
+            desc[(size_t)q].slice = ents;
+            ents += ecap[(size_t)q];
+        }
+        c_slot0[(size_t)c] = s0;
+        c_slots[(size_t)c] = desc[(size_t)hi - 1].slot0 + desc[(size_t)hi - 1].w;
+        c_ents[(size_t)c] = ents;
+    }
+    DevBuf<SolveDesc> d_desc;
+    DevBuf<int> d_items, d_cnt;
+    DevBuf<i64d> d_src, rowstart;
+    DevBuf<unsigned char> d_ok, scan_tmp;
+    DevBuf<int2> scratch, out;
+    d_desc.alloc((size_t)nj);
+    d_items.alloc((size_t)nj);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
+    std::vector<int> items((size_t)nj);
+    SolveBatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = d_desc.p;
+    a.P = dP; a.J = dJ; a.X = dX;
+    a.BP = dBP; a.BJ = dBJ; a.BX = dBX;
+    SpgEvents ev;
+    i64 launches = 0, entries = 0;
+    double ms = 0;
+    h_cnt.assign((size_t)nslots, 0);
+    h_ok.assign((size_t)nslots, 0);
+    h_ent.clear();
+    for (int c = 0; c < nchunks; c++) {
+        const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
+        const i64 slots = c_slots[(size_t)c], ents = c_ents[(size_t)c], s0 = c_slot0[(size_t)c];
+        d_cnt.ensure((size_t)slots + 1);
+        d_src.ensure((size_t)slots);
+        d_ok.ensure((size_t)slots);
+        rowstart.ensure((size_t)slots + 1);
+        scratch.ensure((size_t)ents + 1);
+        a.cnt = d_cnt.p;
+        a.src = d_src.p;
+        a.ok = d_ok.p;
+        a.scratch = scratch.p;
+        HIPCHK(hipMemsetAsync(d_cnt.p + slots, 0, sizeof(int), s));
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        launches += solve_launch_jobs(cls, lo, hi, items, d_items.p, a, s);
+        {
+            size_t bytes = 0;
+            HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt.p, rowstart.p, (i64d)0, (size_t)slots + 1, rocprim::plus<i64d>(), s));
+            scan_tmp.ensure(bytes);
+            HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt.p, rowstart.p, (i64d)0, (size_t)slots + 1, rocprim::plus<i64d>(), s));
+            launches++;
+        }
+        i64d total = 0;
+        HIPCHK(hipMemcpyAsync(&total, rowstart.p + slots, sizeof total, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (total < 0 || total > ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+        if (total > 0) {
+            out.ensure((size_t)total);
+            hipLaunchKernelGGL(k_solve_pack, dim3((unsigned)slots), dim3(64), 0, s, (const int *)d_cnt.p, (const i64d *)d_src.p, (const i64d *)rowstart.p,
+                               (const int2 *)scratch.p, out.p);
+            HIPCHK(hipGetLastError());
+            launches++;
+        }
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        const size_t at = h_ent.size();
+        h_ent.resize(at + (size_t)total);
+        HIPCHK(hipMemcpyAsync(h_cnt.data() + s0, d_cnt.p, (size_t)slots * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h_ok.data() + s0, d_ok.p, (size_t)slots, hipMemcpyDeviceToHost, s));
+        if (total > 0) HIPCHK(hipMemcpyAsync(h_ent.data() + at, out.p, (size_t)total * sizeof(int2), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        ms += ev.ms(0, 1);
+        entries += total;
+    }
+    st[4] = launches;
+    st[5] = (i64)(ms * 1000.0);
+    st[6] = entries;
+}
+
+struct CsrList {
+    std::vector<struct spasm_csr *> v;
+    ~CsrList() { for (auto *x : v) spasm_csr_free(x); }
+};
+
+// One system through the general path: A echelonized with L, then do_gesv.  Rows without a solution are emptied; the others get
+// their columns in ascending order and lose their stored zeros.  ok[K].
+struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *B, unsigned char *ok)
+{
+    const i64 prime = A->field->p;
+    const ZpField F = zp_field_make(prime);
+    const int K = B->n;
+    // the right-hand side with reduced values
+    struct spasm_csr *Bn = spasm_csr_alloc(K, B->m, B->p[K], prime, true);
+    if (!Bn) throw EngineError("out of host memory");
+    std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Bguard(Bn, spasm_csr_free);
+    for (int k = 0; k <= K; k++) Bn->p[k] = B->p[k];
+    for (i64 e = 0; e < B->p[K]; e++) { Bn->j[e] = B->j[e]; Bn->x[e] = zp_reduce(F, (int64_t)B->x[e]); }
+    struct echelonize_opts o;
+    spasm_echelonize_init_opts(&o);
+    o.L = 1;
+    struct spasm_lu *N = do_echelonize(A, &o);
+    std::unique_ptr<struct spasm_lu, void (*)(struct spasm_lu *)> Nguard(N, spasm_lu_free);
+    struct spasm_csr *Xs = do_gesv(N, Bn, ok);
+    std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Xguard(Xs, spasm_csr_free);
+    std::vector<std::pair<int, int>> row;
+    i64 nz = 0;
+    for (int k = 0; k < K; k++)
+        if (ok[k])
+            for (i64 e = Xs->p[k]; e < Xs->p[k + 1]; e++) nz += Xs->x[e] != 0;
+    struct spasm_csr *X = spasm_csr_alloc(K, A->n, nz, prime, true);
+    if (!X) throw EngineError("out of host memory");
+    i64 w = 0;
+    for (int k = 0; k < K; k++) {
+        X->p[k] = w;
+        if (!ok[k]) continue;
+        row.clear();
+        for (i64 e = Xs->p[k]; e < Xs->p[k + 1]; e++)
+            if (Xs->x[e] != 0) row.push_back({Xs->j[e], Xs->x[e]});
+        std::sort(row.begin(), row.end());
+        for (auto &cv : row) { X->j[w] = cv.first; X->x[w] = cv.second; w++; }
+    }
+    X->p[K] = w;
+    return X;
+}
+
+// the checks of a matrix that need no device; NULL when it is well formed
+const char *solve_check(const struct spasm_csr *M)
+{
+    if (!M) return "NULL matrix";
+    if (M->field->p <= 2 || M->field->p > 0xfffffffbLL) return "prime out of range (2 < p <= 0xfffffffb)";
+    if (M->n < 0 || M->m < 0 || !M->p || M->p[0] != 0) return "malformed matrix";
+    if (!M->x) return "matrix without values (x == NULL)";
+    for (int t = 0; t < M->n; t++)
+        if (M->p[t + 1] < M->p[t]) return "row pointers must not decrease";
+    const i64 nz = M->p[M->n];
+    if (nz > 0 && !M->j) return "malformed matrix";
+    const unsigned um = (unsigned)M->m;
+    for (i64 k = 0; k < nz; k++)
+        if ((unsigned)M->j[k] >= um) return "a column index lies outside the matrix";
+    return nullptr;
+}
+
+// concatenated row pointers | columns | values of the matrices list[f] on the device; row0[f] = where the pointers of f start
+void solve_stage(const std::vector<const struct spasm_csr *> &list, DevBuf<unsigned char> &in, std::vector<i64> &row0, const i64d *&dP, const int *&dJ, const int *&dX,
+                 hipStream_t s)
+{
+    i64 rows_total = 0, nnz_total = 0;
+    row0.assign(list.size(), 0);
+    for (size_t f = 0; f < list.size(); f++) {
+        row0[f] = rows_total;
+        rows_total += (i64)list[f]->n + 1;
+        nnz_total += list[f]->p[list[f]->n];
+    }
+    const size_t o_j = batch_align((size_t)rows_total * sizeof(i64d));
+    const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
+    const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
+    std::vector<unsigned char> stage(in_bytes);
+    i64d *P = (i64d *)stage.data();
+    int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
+    i64 e0 = 0, r0 = 0;
+    for (const struct spasm_csr *M : list) {
+        const i64 nz = M->p[M->n];
+        for (int t = 0; t <= M->n; t++) P[r0 + t] = (i64d)(e0 + M->p[t]);
+        if (nz > 0) {
+            memcpy(J + e0, M->j, (size_t)nz * sizeof(int));
+            memcpy(X + e0, M->x, (size_t)nz * sizeof(int));
+        }
+        r0 += (i64)M->n + 1;
+        e0 += nz;
+    }
+    in.alloc(in_bytes);
+    HIPCHK(hipMemcpy(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice));
+    (void)s;
+    dP = (const i64d *)in.p;
+    dJ = (const int *)(in.p + o_j);
+    dX = (const int *)(in.p + o_x);
+}
+
+// Nothing is written to X / ok before all is done.
+void solve_batch_run(int count, const struct spasm_csr *const *A, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
+{
+    memset(g_solve_stats, 0, sizeof g_solve_stats);
+    if (count < 0) throw EngineError("count < 0");
+    if (count == 0) return;
+    if (!A || !B || !X || !ok) throw EngineError("NULL array");
+    char msg[200];
+    for (int i = 0; i < count; i++) {
+        const char *bad = solve_check(A[i]);
+        const char *which = "A";
+        if (!bad) { bad = solve_check(B[i]); which = "B"; }
+        if (!bad && A[i]->field->p != B[i]->field->p) { bad = "the primes of A and B differ"; which = "B"; }
+        if (!bad && B[i]->m != A[i]->m) { bad = "B->m != A->m"; which = "B"; }
+        if (!bad && B[i]->n > 0 && !ok[i]) { bad = "NULL array (ok)"; which = "B"; }
+        if (bad) {
+            snprintf(msg, sizeof msg, "matrix %d (%s): %s", i, which, bad);
+            throw EngineError(msg);
+        }
+    }
+    i64 *st = g_solve_stats;
+    st[0] = count;
+    CsrList res;
+    res.v.assign((size_t)count, nullptr);
+    std::vector<std::vector<unsigned char>> oks((size_t)count);
+    std::vector<int> fast, slow;
+    for (int i = 0; i < count; i++) {
+        const int n = A[i]->n, m = A[i]->m, K = B[i]->n;
+        oks[(size_t)i].assign((size_t)K, 1);
+        if (n == 0 || m == 0 || K == 0) {
+            // no launch: without rows only the zero row is reachable, without columns everything is
+            const ZpField F = zp_field_make(A[i]->field->p);
+            for (int k = 0; k < K && n == 0; k++)
+                for (i64 e = B[i]->p[k]; e < B[i]->p[k + 1]; e++)
+                    if (zp_reduce(F, (int64_t)B[i]->x[e]) != 0) oks[(size_t)i][(size_t)k] = 0;
+            res.v[(size_t)i] = spasm_csr_alloc(K, n, 0, A[i]->field->p, true);
+            if (!res.v[(size_t)i]) throw EngineError("out of host memory");
+            for (int k = 0; k <= K; k++) res.v[(size_t)i]->p[k] = 0;
+            st[1]++;
+        } else if (solve_fits(n, m)) fast.push_back(i);
+        else slow.push_back(i);
+    }
+    if (!fast.empty() || !slow.empty()) require_device();
+    st[1] += (i64)fast.size();
+    st[2] = (i64)slow.size();
+    if (!fast.empty()) {
+        hipStream_t s = nullptr;
+        std::vector<const struct spasm_csr *> la, lb;
+        for (int i : fast) { la.push_back(A[i]); lb.push_back(B[i]); }
+        DevBuf<unsigned char> ina, inb;
+        std::vector<i64> arow0, brow0;
+        const i64d *dP, *dBP;
+        const int *dJ, *dX, *dBJ, *dBX;
+        solve_stage(la, ina, arow0, dP, dJ, dX, s);
+        solve_stage(lb, inb, brow0, dBP, dBJ, dBX, s);
+        std::vector<SolveSys> sys;
+        i64 nslots = 0;
+        for (size_t f = 0; f < fast.size(); f++) {
+            const int i = fast[f];
+            sys.push_back(SolveSys{A[i]->n, A[i]->m, B[i]->n, arow0[f], brow0[f], nslots, A[i]->field->p});
+            nslots += B[i]->n;
+        }
+        std::vector<int> h_cnt;
+        std::vector<unsigned char> h_ok;
+        std::vector<int2> h_ent;
+        solve_fast(sys, nslots, dP, dJ, dX, dBP, dBJ, dBX, h_cnt, h_ok, h_ent);
+        i64 at = 0;
+        for (size_t f = 0; f < fast.size(); f++) {
+            const int i = fast[f], K = sys[f].K;
+            const int *rc = h_cnt.data() + sys[f].slot0;
+            i64 nz = 0;
+            for (int k = 0; k < K; k++) nz += rc[k];
+            if (at + nz > (i64)h_ent.size()) throw EngineError("internal error: row counts and entry count disagree");
+            struct spasm_csr *R = spasm_csr_alloc(K, sys[f].n, nz, sys[f].prime, true);
+            if (!R) throw EngineError("out of host memory");
+            res.v[(size_t)i] = R;
+            R->p[0] = 0;
+            for (int k = 0; k < K; k++) R->p[k + 1] = R->p[k] + rc[k];
+            for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[(size_t)(at + e)].x; R->x[e] = h_ent[(size_t)(at + e)].y; }
+            at += nz;
+            memcpy(oks[(size_t)i].data(), h_ok.data() + sys[f].slot0, (size_t)K);
+        }
+    }
+    for (int i : slow) res.v[(size_t)i] = solve_slow(A[i], B[i], oks[(size_t)i].data());
+    for (int i = 0; i < count; i++)
+        for (unsigned char v : oks[(size_t)i]) st[7] += v ? 0 : 1;
+    for (int i = 0; i < count; i++)
+        if (!oks[(size_t)i].empty()) memcpy(ok[i], oks[(size_t)i].data(), oks[(size_t)i].size());
+    memcpy(X, res.v.data(), sizeof(struct spasm_csr *) * (size_t)count);
+    res.v.clear();
+}
+
+// 64-bit keys with 32-bit values, stable, on the low `bits` bits
+void solve_sort(DevBuf<unsigned char> &tmp, const unsigned long long *key, unsigned long long *key_out, const int *val, int *val_out, i64 cnt, int bits, hipStream_t s)
+{
+    if (cnt == 0) return;
+    size_t bytes = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, key, key_out, val, val_out, (size_t)cnt, 0, bits, s));
+    tmp.ensure(bytes);
+    HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, key, key_out, val, val_out, (size_t)cnt, 0, bits, s));
+}
+
+inline int solve_bits(i64 v)
+{
+    int bits = 1;
+    while (bits < 32 && ((i64)1 << bits) < v) bits++;
+    return bits;
+}
+
+// Rows k0 .. k1 of Rhs (on the device as rp / rj / rx) against the blocks of the handle.  Appends to xp (row lengths become
+// pointers at the caller), xj, xx and writes ok[k0 .. k1).  The pipeline, every step on the device unless it says otherwise:
+//   keys      (block of the entry's column, row) per entry; a stable sort; the runs of equal keys = the right-hand sides of the blocks
+//   plan      where the runs of each block start comes to the host (nb + 1 words): jobs for the blocks inside the limit; the blocks
+//             over it are fetched with their runs and solved by solve_slow, their rows of X uploaded behind the jobs' slices
+//   solve     k_solve_elim from the resident concatenated CSR; a run of a block without rows is solvable iff it vanishes
+//   assemble  the runs by row (a second stable sort), ok[k] = AND over the runs of row k, the entries of the solvable rows as
+//             (row, row of A) keys through block_rows, one sort, row pointers by bisection, one download
+void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, const i64 *h_rp, const int *rj, const int *rx, std::vector<i64> &xlen,
+                       std::vector<int> &xj, std::vector<int> &xx, unsigned char *ok)
+{
+    i64 *st = g_solve_stats;
+    hipStream_t s = nullptr;
+    const int K = k1 - k0, nb = B->nb;
+    const i64 e0 = h_rp[k0], ne = h_rp[k1] - e0;
+    const ZpField F = zp_field_make(B->prime);
+    if (ne == 0) {
+        for (int k = 0; k < K; k++) { ok[k0 + k] = 1; xlen[(size_t)(k0 + k)] = 0; }
+        return;
+    }
+    Scanner scan;
+    DevBuf<unsigned char> sort_tmp;
+    DevBuf<unsigned long long> key, skey;
+    DevBuf<int> val, sval, head, runid, sj, sx;
+    key.alloc((size_t)ne);
+    skey.alloc((size_t)ne);
+    val.alloc((size_t)ne);
+    sval.alloc((size_t)ne);
+    head.alloc((size_t)ne + 1);
+    runid.alloc((size_t)ne + 1);
+    sj.alloc((size_t)ne);
+    sx.alloc((size_t)ne);
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    hipLaunchKernelGGL(k_sv_keys, dim3(cdiv(ne, 256)), dim3(256), 0, s, K, (i64d)e0, (i64d)ne, rp + k0, rj, (const int *)B->col_block.p, key.p, val.p);
+    HIPCHK(hipGetLastError());
+    solve_sort(sort_tmp, key.p, skey.p, val.p, sval.p, ne, 32 + solve_bits(nb), s);
+    hipLaunchKernelGGL(k_sv_heads, dim3(cdiv(ne + 1, 256)), dim3(256), 0, s, (i64d)ne, (const unsigned long long *)skey.p, head.p);
+    HIPCHK(hipGetLastError());
+    scan.exclusive<int>(head.p, runid.p, (size_t)ne + 1, s);
+    int nruns = 0;
+    HIPCHK(hipMemcpyAsync(&nruns, runid.p + ne, sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (nruns <= 0 || nruns > ne) throw EngineError("internal error: run count outside its bounds");
+    DevBuf<i64d> run_start, brun, d_src, krun, off;
+    DevBuf<int> run_block, run_row, d_cnt, iota, byrow, krow, len;
+    DevBuf<unsigned char> d_ok, rowok;
+    run_start.alloc((size_t)nruns + 1);
+    run_block.alloc((size_t)nruns);
+    run_row.alloc((size_t)nruns);
+    brun.alloc((size_t)nb + 1);
+    d_cnt.alloc((size_t)nruns);
+    d_src.alloc((size_t)nruns);
+    d_ok.alloc((size_t)nruns);
+    iota.alloc((size_t)nruns);
+    hipLaunchKernelGGL(k_sv_runs, dim3(cdiv(ne + 1, 256)), dim3(256), 0, s, (i64d)e0, (i64d)ne, (const unsigned long long *)skey.p, (const int *)sval.p, (const int *)head.p,
+                       (const int *)runid.p, rj, rx, (const int *)B->col_pos.p, run_start.p, run_block.p, run_row.p, sj.p, sx.p);
+    hipLaunchKernelGGL(k_blk_starts, dim3(cdiv((i64)nb + 1, 256)), dim3(256), 0, s, nb, nruns, (const int *)run_block.p, brun.p);
+    hipLaunchKernelGGL(k_sv_init, dim3(cdiv(nruns, 256)), dim3(256), 0, s, nruns, F, (const i64d *)run_start.p, (const int *)run_block.p, (const i64d *)B->row_start.p,
+                       (const int *)sx.p, d_cnt.p, d_src.p, d_ok.p, iota.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<i64> h_brun((size_t)nb + 1);
+    HIPCHK(hipMemcpyAsync(h_brun.data(), brun.p, ((size_t)nb + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    // ---- plan (host: one step per block)
+    std::vector<SolveSys> sys;
+    std::vector<int> slow;
+    for (int b = 0; b < nb; b++) {
+        const i64 Kb = h_brun[(size_t)b + 1] - h_brun[(size_t)b];
+        if (Kb == 0) continue;
+        const i64 rn = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], cn = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+        st[0]++;
+        if (rn == 0) st[1]++;
+        else if (solve_fits(rn, cn)) {
+            st[1]++;
+            sys.push_back(SolveSys{(int)rn, (int)cn, (int)Kb, B->h_row_start[(size_t)b] + b, h_brun[(size_t)b], h_brun[(size_t)b], B->prime});
+        } else {
+            st[2]++;
+            slow.push_back(b);
+        }
+    }
+    std::vector<SolveDesc> desc;
+    std::vector<unsigned char> cls;
+    std::vector<i64> ecap;
+    solve_jobs(sys, desc, cls, ecap);
+    const int nj = (int)desc.size();
+    st[3] += nj;
+    i64 ents = 0;
+    for (int q = 0; q < nj; q++) { desc[(size_t)q].slice = ents; ents += ecap[(size_t)q]; }
+    // ---- the blocks over the limit, on the host; their rows of X go behind the slices
+    std::vector<int2> slow_ent;
+    std::vector<int> slow_cnt;
+    std::vector<i64> slow_src, slow_run;
+    std::vector<unsigned char> slow_ok;
+    for (int b : slow) {
+        const i64 q0 = h_brun[(size_t)b], Kb = h_brun[(size_t)b + 1] - q0;
+        struct spasm_csr *M = blocks_fetch(B, b);
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Mguard(M, spasm_csr_free);
+        std::vector<i64> rs((size_t)Kb + 1);
+        HIPCHK(hipMemcpy(rs.data(), run_start.p + q0, ((size_t)Kb + 1) * sizeof(i64d), hipMemcpyDeviceToHost));
+        const i64 z0 = rs[0], z = rs[(size_t)Kb] - z0;
+        struct spasm_csr *Rb = spasm_csr_alloc((int)Kb, M->m, z, B->prime, true);
+        if (!Rb) throw EngineError("out of host memory");
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Rguard(Rb, spasm_csr_free);
+        for (i64 t = 0; t <= Kb; t++) Rb->p[t] = rs[(size_t)t] - z0;
+        if (z > 0) {
+            HIPCHK(hipMemcpy(Rb->j, sj.p + z0, (size_t)z * sizeof(int), hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(Rb->x, sx.p + z0, (size_t)z * sizeof(int), hipMemcpyDeviceToHost));
+        }
+        std::vector<unsigned char> okb((size_t)Kb, 0);
+        struct spasm_csr *Xb = solve_slow(M, Rb, okb.data());
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Xguard(Xb, spasm_csr_free);
+        for (i64 t = 0; t < Kb; t++) {
+            slow_run.push_back(q0 + t);
+            slow_ok.push_back(okb[(size_t)t]);
+            slow_cnt.push_back((int)(Xb->p[t + 1] - Xb->p[t]));
+            slow_src.push_back(ents + (i64)slow_ent.size());
+            for (i64 e = Xb->p[t]; e < Xb->p[t + 1]; e++) slow_ent.push_back(make_int2(Xb->j[e], Xb->x[e]));
+        }
+    }
+    DevBuf<int2> scratch;
+    scratch.alloc((size_t)ents + slow_ent.size() + 1);
+    if (!slow_ent.empty()) HIPCHK(hipMemcpy(scratch.p + ents, slow_ent.data(), slow_ent.size() * sizeof(int2), hipMemcpyHostToDevice));
+    for (size_t t = 0; t < slow_run.size(); t++) {
+        HIPCHK(hipMemcpy(d_cnt.p + slow_run[t], &slow_cnt[t], sizeof(int), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_src.p + slow_run[t], &slow_src[t], sizeof(i64d), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_ok.p + slow_run[t], &slow_ok[t], 1, hipMemcpyHostToDevice));
+    }
+    // ---- solve
+    i64 launches = 0;
+    DevBuf<SolveDesc> d_desc;
+    DevBuf<int> d_items;
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    if (nj > 0) {
+        d_desc.alloc((size_t)nj);
+        d_items.alloc((size_t)nj);
+        HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
+        std::vector<int> items((size_t)nj);
+        SolveBatchArgs a;
+        memset(&a, 0, sizeof a);
+        a.desc = d_desc.p;
+        a.P = B->P.p; a.J = B->J.p; a.X = B->X.p;
+        a.BP = run_start.p; a.BJ = sj.p; a.BX = sx.p;
+        a.cnt = d_cnt.p;
+        a.src = d_src.p;
+        a.ok = d_ok.p;
+        a.scratch = scratch.p;
+        launches += solve_launch_jobs(cls, 0, nj, items, d_items.p, a, s);
+        HIPCHK(hipStreamSynchronize(s)); // (items and desc are host vectors of this scope)
+    }
+    // ---- assemble
+    byrow.alloc((size_t)nruns);
+    krow.alloc((size_t)nruns);
+    krun.alloc((size_t)K + 1);
+    len.alloc((size_t)nruns + 1);
+    off.alloc((size_t)nruns + 1);
+    rowok.alloc((size_t)K);
+    blk_sort(sort_tmp, run_row.p, krow.p, iota.p, byrow.p, nruns, K, s);
+    hipLaunchKernelGGL(k_blk_starts, dim3(cdiv((i64)K + 1, 256)), dim3(256), 0, s, K, nruns, (const int *)krow.p, krun.p);
+    HIPCHK(hipMemsetAsync(len.p + nruns, 0, sizeof(int), s));
+    hipLaunchKernelGGL(k_sv_rowok, dim3(cdiv(K, 256)), dim3(256), 0, s, K, (const i64d *)krun.p, (const int *)byrow.p, (const unsigned char *)d_ok.p, (const int *)d_cnt.p,
+                       rowok.p, len.p);
+    HIPCHK(hipGetLastError());
+    {
+        size_t bytes = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)len.p, off.p, (i64d)0, (size_t)nruns + 1, rocprim::plus<i64d>(), s));
+        scan.tmp.ensure(bytes);
+        HIPCHK(rocprim::exclusive_scan(scan.tmp.p, bytes, (const int *)len.p, off.p, (i64d)0, (size_t)nruns + 1, rocprim::plus<i64d>(), s));
+    }
+    i64d total = 0;
+    HIPCHK(hipMemcpyAsync(&total, off.p + nruns, sizeof total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total < 0 || total > ents + (i64)slow_ent.size()) throw EngineError("internal error: the rows of X hold more entries than the slices");
+    std::vector<i64> h_p((size_t)K + 1, 0);
+    const size_t at = xj.size();
+    xj.resize(at + (size_t)total);
+    xx.resize(at + (size_t)total);
+    DevBuf<unsigned long long> xkey, xskey;
+    DevBuf<int> xval, xsval, outj;
+    DevBuf<i64d> outp;
+    outp.alloc((size_t)K + 1);
+    xkey.alloc((size_t)total);
+    xskey.alloc((size_t)total);
+    xval.alloc((size_t)total);
+    xsval.alloc((size_t)total);
+    outj.alloc((size_t)total);
+    if (total > 0) {
+        hipLaunchKernelGGL(k_sv_emit, dim3((unsigned)nruns), dim3(64), 0, s, (const int *)len.p, (const i64d *)off.p, (const i64d *)d_src.p, (const int *)run_block.p,
+                           (const int *)run_row.p, (const i64d *)B->row_start.p, (const int *)B->block_rows.p, (const int2 *)scratch.p, xkey.p, xval.p);
+        HIPCHK(hipGetLastError());
+        solve_sort(sort_tmp, xkey.p, xskey.p, xval.p, xsval.p, total, 32 + solve_bits(K), s);
+    }
+    hipLaunchKernelGGL(k_sv_finish, dim3(cdiv(std::max<i64>(total, (i64)K + 1), 256)), dim3(256), 0, s, K, total, (const unsigned long long *)xskey.p, outp.p, outj.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ev.e[3], s));
+    HIPCHK(hipMemcpyAsync(h_p.data(), outp.p, ((size_t)K + 1) * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(ok + k0, rowok.p, (size_t)K, hipMemcpyDeviceToHost, s));
+    if (total > 0) {
+        HIPCHK(hipMemcpyAsync(xj.data() + at, outj.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(xx.data() + at, xsval.p, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    if (h_p[0] != 0 || h_p[(size_t)K] != total) throw EngineError("internal error: the row pointers of X disagree with its entries");
+    for (int k = 0; k < K; k++) xlen[(size_t)(k0 + k)] = h_p[(size_t)k + 1] - h_p[(size_t)k];
+    st[4] += launches;
+    st[5] += (i64)((ev.ms(0, 1) + ev.ms(2, 3)) * 1000.0);
+    st[6] += total;
+}
+
+void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+{
+    memset(g_solve_stats, 0, sizeof g_solve_stats);
+    blocks_need(B);
+    if (!Rhs) throw EngineError("NULL matrix");
+    if (Rhs->m != B->m) throw EngineError("Rhs->m differs from the columns of the handle's matrix");
+    if (Rhs->field->p != B->prime) throw EngineError("the prime of Rhs differs from the handle's");
+    const char *bad = solve_check(Rhs);
+    if (bad) throw EngineError(bad);
+    if (!X || (Rhs->n > 0 && !ok)) throw EngineError("NULL array");
+    HIPCHK(hipSetDevice(B->dev));
+    hipStream_t s = nullptr;
+    const int K = Rhs->n;
+    const i64 nnz = Rhs->p[K];
+    std::vector<i64> xlen((size_t)K, 0);
+    std::vector<int> xj, xx;
+    std::vector<unsigned char> hok((size_t)K, 1);
+    if (K > 0 && nnz > 0) {
+        DevBuf<i64d> rp;
+        DevBuf<int> rj, rx;
+        rp.alloc((size_t)K + 1);
+        rj.alloc((size_t)nnz);
+        rx.alloc((size_t)nnz);
+        static_assert(sizeof(i64d) == sizeof(i64), "row pointers are copied as they are");
+        HIPCHK(hipMemcpyAsync(rp.p, Rhs->p, ((size_t)K + 1) * sizeof(i64d), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(rj.p, Rhs->j, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(rx.p, Rhs->x, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        // chunks of rows: an entry of Rhs opens at most one run, a run holds at most min(rows, cols) + 1 entries of its block, and
+        // every such entry is held about five times on the way (scratch, key and value twice, column)
+        i64 rmax = 1;
+        for (int b = 0; b < B->nb; b++)
+            rmax = std::max(rmax, std::min(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]) + 1);
+        const double per = 64.0 + 48.0 * (double)rmax;
+        const i64 cap = std::min<i64>((i64)std::max(1.0, (double)batch_budget() / per), ((i64)1 << 31) - 2);
+        int k0 = 0;
+        while (k0 < K) {
+            int k1 = k0 + 1;
+            while (k1 < K && Rhs->p[k1 + 1] - Rhs->p[k0] <= cap) k1++;
+            if (Rhs->p[k1] - Rhs->p[k0] > ((i64)1 << 31) - 2) throw EngineError("a row of Rhs holds 2^31 entries or more");
+            solve_blocks_rows(B, k0, k1, rp.p, Rhs->p, rj.p, rx.p, xlen, xj, xx, hok.data());
+            k0 = k1;
+        }
+    }
+    struct spasm_csr *R = spasm_csr_alloc(K, B->n, (i64)xj.size(), B->prime, true);
+    if (!R) throw EngineError("out of host memory");
+    R->p[0] = 0;
+    for (int k = 0; k < K; k++) R->p[k + 1] = R->p[k] + xlen[(size_t)k];
+    if (R->p[K] != (i64)xj.size()) { spasm_csr_free(R); throw EngineError("internal error: the rows of X disagree with its entries"); }
+    if (!xj.empty()) {
+        memcpy(R->j, xj.data(), xj.size() * sizeof(int));
+        memcpy(R->x, xx.data(), xx.size() * sizeof(int));
+    }
+    for (int k = 0; k < K; k++) g_solve_stats[7] += hok[(size_t)k] ? 0 : 1;
+    if (K > 0) memcpy(ok, hok.data(), (size_t)K);
+    *X = R;
+}
+
+} // namespace
+
 // ================================================================================================
 // C ABI
 // ================================================================================================
@@ -8219,6 +8911,22 @@ SPASM_API void spasm_amd_blocks_free(spasm_amd_blocks *B)
     DeviceGuard g;
     (void)hipSetDevice(B->dev);
     delete B;
+}
+
+// ---- X * A = B for many small matrices, and block by block (solve_batch.hpp; engine extension) ----
+SPASM_API int spasm_amd_solve_batch(int count, const struct spasm_csr *const *A, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
+{
+    BATCH_TRY("spasm_amd_solve_batch", solve_batch_run(count, A, B, X, ok);)
+}
+
+SPASM_API int spasm_amd_blocks_solve(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+{
+    BLOCKS_TRY("spasm_amd_blocks_solve", solve_blocks_run(B, Rhs, X, ok); return 0;, -1)
+}
+
+SPASM_API void spasm_amd_solve_stats(i64 *out)
+{
+    if (out) memcpy(out, g_solve_stats, sizeof g_solve_stats);
 }
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
