@@ -1,16 +1,10 @@
 // batch.hpp -- many small matrices echelonized in one launch: one workgroup per matrix, resident in LDS from first load to last store.
+// The elimination itself (batch_eliminate) is shared with solve_batch.hpp.
 //
 // The whole batch is one concatenated device CSR (row pointers P as global entry offsets, columns J, values X) plus one
 // descriptor per matrix.  A workgroup scatters its matrix into a dense n x m image of balanced residues (32-bit words, row
-// stride ld) and eliminates it column by column with the rule dense.hpp:5 states: the pivot of a column is the first row, not
-// yet a pivot, that holds a non-zero there.  The pivot row is subtracted from EVERY other row that holds the column (earlier
-// pivot rows too), so the image ends as the reduced row echelon form and the pivot columns are the canonical ones.
-//
-// Two shortcuts keep it to three barriers per column, both invisible in the result:
-//   - pivot rows are not normalised in place: row k stays a multiple of its normalised form and the inverse of its pivot is
-//     kept (pinv[k]); the factor of a row is f * pinv and the output multiplies by pinv once;
-//   - column c is not zeroed: the factors are written over it (each row its own word) and read from there by the update.
-//     Pivot columns of the final image therefore hold leftovers; the output never reads them (the pivot is written as 1).
+// stride ld), eliminates it with batch_eliminate over all m columns, so the image ends as the reduced row echelon form and the
+// pivot columns are the canonical ones, and writes its output from the image.
 //
 // Row stride: the election and the factor pass walk DOWN a column, lane i at word i * ld + c.  ds_read_b32 / ds_write_b32 bank
 // on (word mod 32) per half wave, so an odd ld makes the walk conflict-free and an even one folds it onto 32 / gcd(ld, 32) banks.
@@ -61,6 +55,126 @@ struct BatchArgs {
 // words of LDS of a class besides the image: two bitsets (pivot rows, pivot columns), three pivot lists, the election's mailbox
 __host__ __device__ inline int batch_lds_words(int cap, int bw, int rmax) { return cap + 2 * bw + 3 * rmax + 16; }
 
+// the dynamic LDS of a class, carved in the order batch_lds_words counts it
+struct BatchLds {
+    int *img;
+    unsigned *rowflag, *colflag;   // bit i: image row i is a pivot row / column i is a pivot column (colflag NULL: not kept)
+    int *pivrow, *pivcol, *pinv;   // the k-th pivot: its image row, its column, the inverse of its entry
+    int *wmin;                     // the election's mailbox: 2 parities x 8 waves
+    __device__ BatchLds(int *base, int cap, int bw, int rmax, bool keep_colflag)
+        : img(base), rowflag((unsigned *)(base + cap)), colflag(keep_colflag ? rowflag + bw : nullptr), pivrow((int *)(rowflag + 2 * bw)), pivcol(pivrow + rmax),
+          pinv(pivcol + rmax), wmin(pinv + rmax)
+    {
+    }
+};
+
+// a zero image of `words` words and empty bitsets; the caller's barrier follows
+template <int BS> __device__ inline void batch_lds_clear(const BatchLds &L, int words, int bw)
+{
+    for (int e = threadIdx.x; e < words; e += BS) L.img[e] = 0;
+    for (int w = threadIdx.x; w < bw; w += BS) {
+        L.rowflag[w] = 0;
+        if (L.colflag) L.colflag[w] = 0;
+    }
+}
+
+// Gauss-Jordan elimination of the image (`rows` rows of stride ld) inside LDS by the whole workgroup; returns the rank.  Columns
+// 0 .. ecols - 1 are candidates for a pivot, in that order; the update reaches columns 0 .. ucols - 1 (ucols >= ecols: what lies
+// right of the candidates rides along).  The rule is the one dense.hpp:5 states: the pivot of a column is the first row, not yet a
+// pivot, that holds a non-zero there.  The pivot row is subtracted from EVERY other row that holds the column (earlier pivot rows
+// too), so the candidate columns end in reduced row echelon form and the pivot columns are the canonical ones.
+//
+// Two shortcuts keep it to three barriers per pivot (one per block of BS rows the election scans, one after the factors, one
+// after the update), both invisible in the result:
+//   - pivot rows are not normalised in place: row pivrow[k] stays a multiple of its normalised form and the inverse of its pivot
+//     is kept (pinv[k]); the factor of a row is f * pinv and whoever reads a pivot row multiplies by pinv once;
+//   - column c is not zeroed: the factors are written over it (each row its own word) and read from there by the update.
+//     Pivot columns of the final image therefore hold leftovers; nobody reads them (the pivot counts as 1).
+// The election posts one candidate per wave into a mailbox and reads all of them after a barrier.  The mailbox has two halves
+// used in turn (par): a wave that is still reading the one of this step cannot meet the writes of the next step, and the half of
+// the step before last is free again because a barrier lies between.
+//
+// Once every row is a pivot no election can succeed, so the loop ends there.  skip_done_rows (wave-uniform): rows that are pivots
+// already get the factor 0, which leaves the rank as it is and nothing else meaningful.  WITH_QINV: qinv[c] (global memory) = k for
+// the k-th pivot's column c, -1 for a candidate column without pivot; without it qinv is not looked at.  (A template parameter
+// because k_batch_elim needs 106 scalar registers with a run-time test of the pointer, which costs it the eighth wave per SIMD.)
+template <int BS, bool WITH_QINV>
+__device__ inline int batch_eliminate(const ZpField &F, const BatchLds &L, int ld, int rows, int ecols, int ucols, bool skip_done_rows, int *qinv)
+{
+    constexpr int NW = BS / 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int *img = L.img, *wmin = L.wmin;
+    unsigned *rowflag = L.rowflag;
+    // the update: TX lanes per row (a power of two, at most a wave), TY rows at a time
+    int lt = 0;
+    while ((1 << lt) < ucols && lt < 6) lt++;
+    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
+
+    int r = 0, par = 0, c = 0;
+    for (; c < ecols && r < rows; c++) {
+        // ---- election: the first row that is not a pivot yet and holds column c
+        int pr = 0x7fffffff;
+        for (int base = 0; base < rows; base += BS) {
+            const int i = base + tid;
+            const bool hit = i < rows && !((rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + c] != 0;
+            const unsigned long long b = __ballot(hit);
+            if (lane == 0) wmin[par * 8 + wave] = b ? base + wave * 64 + (__ffsll((long long)b) - 1) : 0x7fffffff;
+            __syncthreads();
+            int best = 0x7fffffff;
+#pragma unroll
+            for (int w = 0; w < NW; w++) best = min(best, wmin[par * 8 + w]);
+            par ^= 1;
+            if (best != 0x7fffffff) { pr = best; break; }
+        }
+        if (pr == 0x7fffffff) {
+            if (WITH_QINV && tid == 0) qinv[c] = -1;
+            continue;
+        }
+        const int inv = zp_inverse(F, img[pr * ld + c]);
+        // ---- factors, in place on column c
+        for (int i = tid; i < rows; i += BS) {
+            if (i == pr) continue;
+            const int f = img[i * ld + c];
+            if (f == 0) continue;
+            const bool done = skip_done_rows && ((rowflag[i >> 5] >> (i & 31)) & 1u);
+            img[i * ld + c] = done ? 0 : zp_mul(F, f, inv);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            rowflag[pr >> 5] |= 1u << (pr & 31);
+            if (L.colflag) L.colflag[c >> 5] |= 1u << (c & 31);
+            L.pivrow[r] = pr;
+            L.pivcol[r] = c;
+            L.pinv[r] = inv;
+            if (WITH_QINV) qinv[c] = r;
+        }
+        // ---- update: row i -= factor * pivot row, on the columns right of c
+        for (int i = ty; i < rows; i += TY) {
+            if (i == pr) continue;
+            const int g = img[i * ld + c];
+            if (g == 0) continue;
+            for (int j = c + 1 + tx; j < ucols; j += TX) {
+                const int v = img[pr * ld + j];
+                if (v != 0) img[i * ld + j] = zp_axpy(F, -g, v, img[i * ld + j]);
+            }
+        }
+        __syncthreads();
+        r++;
+    }
+    if (WITH_QINV)
+        for (int k = c + tid; k < ecols; k += BS) qinv[k] = -1;
+    return r;
+}
+
+// wave-level compaction: appends (j, v) of the lanes with v != 0 at dst[count ..], in lane order, and advances count (the same
+// in every lane); the whole wave calls it
+__device__ inline void batch_append(int2 *dst, int &count, int j, int v)
+{
+    const unsigned long long b = __ballot(v != 0);
+    if (v != 0) dst[count + __popcll(b & ((1ull << (threadIdx.x & 63)) - 1ull))] = make_int2(j, v);
+    count += __popcll(b);
+}
+
 template <int BS>
 __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
 {
@@ -71,79 +185,26 @@ __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
     const BatchDesc d = a.desc[item];
     const ZpField F = d.F;
     const int n = d.n, m = d.m, ld = d.ld, mode = a.mode;
-    int *img = s_batch;
-    unsigned *rowflag = (unsigned *)(img + a.cap);
-    unsigned *colflag = rowflag + a.bw;
-    int *pivrow = (int *)(colflag + a.bw);
-    int *pivcol = pivrow + a.rmax;
-    int *pinv = pivcol + a.rmax;
-    int *wmin = pinv + a.rmax;
+    const BatchLds L(s_batch, a.cap, a.bw, a.rmax, true);
+    int *img = L.img, *pivrow = L.pivrow, *pivcol = L.pivcol, *pinv = L.pinv;
+    unsigned *rowflag = L.rowflag, *colflag = L.colflag;
 
-    for (int e = tid; e < n * ld; e += BS) img[e] = 0;
-    for (int w = tid; w < a.bw; w += BS) { rowflag[w] = 0; colflag[w] = 0; }
+    batch_lds_clear<BS>(L, n * ld, a.bw);
     __syncthreads();
-    // TX lanes per row (a power of two, at most a wave), TY rows at a time
-    int lt = 0;
-    while ((1 << lt) < m && lt < 6) lt++;
-    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
-    for (int i = ty; i < n; i += TY) {
-        const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
-        for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
-    }
-    __syncthreads();
-
-    int r = 0, par = 0;
-    int *qinv = a.rec + d.rec + 2;
-    for (int c = 0; c < m; c++) {
-        // ---- election: the first row that is not a pivot yet and holds column c
-        int pr = 0x7fffffff;
-        for (int base = 0; base < n; base += BS) {
-            const int i = base + tid;
-            const bool hit = i < n && !((rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + c] != 0;
-            const unsigned long long b = __ballot(hit);
-            if (lane == 0) wmin[par * 8 + wave] = b ? base + wave * 64 + (__ffsll((long long)b) - 1) : 0x7fffffff;
-            __syncthreads();
-            int best = 0x7fffffff;
-#pragma unroll
-            for (int w = 0; w < NW; w++) best = min(best, wmin[par * 8 + w]);
-            par ^= 1; // (the mailbox of the step before last is free again: a barrier lies between)
-            if (best != 0x7fffffff) { pr = best; break; }
-        }
-        if (pr == 0x7fffffff) {
-            if (tid == 0 && mode == BATCH_LU) qinv[c] = -1;
-            continue;
-        }
-        const int inv = zp_inverse(F, img[pr * ld + c]);
-        // ---- factors, in place on column c
-        for (int i = tid; i < n; i += BS) {
-            if (i == pr) continue;
-            const int f = img[i * ld + c];
-            if (f == 0) continue;
-            const bool done = mode == BATCH_RANK && ((rowflag[i >> 5] >> (i & 31)) & 1u);
-            img[i * ld + c] = done ? 0 : zp_mul(F, f, inv);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            rowflag[pr >> 5] |= 1u << (pr & 31);
-            colflag[c >> 5] |= 1u << (c & 31);
-            pivrow[r] = pr;
-            pivcol[r] = c;
-            pinv[r] = inv;
-            if (mode == BATCH_LU) qinv[c] = r;
-        }
-        // ---- update: row i -= factor * pivot row, on the columns right of c
+    {
+        // TX lanes per row (a power of two, at most a wave), TY rows at a time
+        int lt = 0;
+        while ((1 << lt) < m && lt < 6) lt++;
+        const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
         for (int i = ty; i < n; i += TY) {
-            if (i == pr) continue;
-            const int g = img[i * ld + c];
-            if (g == 0) continue;
-            for (int j = c + 1 + tx; j < m; j += TX) {
-                const int v = img[pr * ld + j];
-                if (v != 0) img[i * ld + j] = zp_axpy(F, -g, v, img[i * ld + j]);
-            }
+            const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
+            for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
         }
-        __syncthreads();
-        r++;
     }
+    __syncthreads();
+
+    const int r = mode == BATCH_LU ? batch_eliminate<BS, true>(F, L, ld, n, m, m, false, a.rec + d.rec + 2)
+                                   : batch_eliminate<BS, false>(F, L, ld, n, m, m, mode == BATCH_RANK, nullptr);
 
     if (mode == BATCH_RANK) {
         if (tid == 0) a.rank[item] = r;
@@ -152,7 +213,6 @@ __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
     int *rec = a.rec + d.rec;
     int *cnt = a.cnt + d.slot0;
     if (tid == 0) { rec[0] = r; rec[1] = 0; }
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     if (mode == BATCH_LU) {
         const int stride = m - r + 1;
         for (int k = wave; k < r; k += NW) {
@@ -167,9 +227,7 @@ __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
                     const int x = img[pr * ld + j];
                     if (x != 0) v = zp_mul(F, x, inv);
                 }
-                const unsigned long long b = __ballot(v != 0);
-                if (v != 0) dst[count + __popcll(b & lt_mask)] = make_int2(j, v);
-                count += __popcll(b);
+                batch_append(dst, count, j, v);
             }
             if (lane == 0) cnt[k] = count;
         }
@@ -213,9 +271,7 @@ __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
                         if (x != 0) v = zp_mul(F, x, pinv[k]);
                     }
                 }
-                const unsigned long long b = __ballot(v != 0);
-                if (v != 0) dst[count + __popcll(b & lt_mask)] = make_int2(pc, v);
-                count += __popcll(b);
+                batch_append(dst, count, pc, v);
             }
             if (lane == 0) {
                 dst[count] = make_int2(f, -1);

@@ -99,12 +99,13 @@ struct DevMat {
 
 struct Scanner {
     DevBuf<unsigned char> tmp;
-    template <class T> void exclusive(const T *in, T *out, size_t n, hipStream_t s)
+    // (the sums are formed in the type of the output: 32-bit counts scan into 64-bit offsets)
+    template <class In, class Out> void exclusive(const In *in, Out *out, size_t n, hipStream_t s)
     {
         size_t bytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, T(0), n, rocprim::plus<T>(), s));
+        HIPCHK(rocprim::exclusive_scan(nullptr, bytes, in, out, Out(0), n, rocprim::plus<Out>(), s));
         tmp.ensure(bytes);
-        HIPCHK(rocprim::exclusive_scan(tmp.p, bytes, in, out, T(0), n, rocprim::plus<T>(), s));
+        HIPCHK(rocprim::exclusive_scan(tmp.p, bytes, in, out, Out(0), n, rocprim::plus<Out>(), s));
     }
 };
 
@@ -6523,6 +6524,9 @@ bool trsolve_once(const struct spasm_csr *T, spasm_ZZp *b, spasm_ZZp *x, const i
 // and is shared with the blocks of a split matrix that lie on the device already (blocks.hpp); per chunk of matrices whose
 // scratch fits the budget: at most BATCH_NCLASS elimination launches, one scan, one pack, the 8-byte read of the chunk's
 // entry count and one download.
+//
+// The first part of the section is the driver that the solve (solve_batch.hpp, further down) shares: the check and the staging of
+// host matrices, the launch of a list of jobs class by class, the cut into chunks and the scan that ends a chunk's eliminations.
 // ------------------------------------------------------------------------------------------------
 namespace {
 
@@ -6540,30 +6544,109 @@ void batch_layout(int cls, int &bw, int &rmax)
     while ((i64)rmax * rmax <= lim) rmax++;
 }
 
-template <int BS> void batch_launch(const BatchArgs &a, int nitems, size_t lds, hipStream_t s)
+// the checks of a host matrix that need no device; NULL when it is well formed
+const char *batch_check(const struct spasm_csr *M)
 {
-    static bool attr_done[kMaxDev] = {false};
-    bool &done = attr_done[current_device()];
-    if (!done) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_batch_elim<BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        done = true;
-    }
-    hipLaunchKernelGGL((k_batch_elim<BS>), dim3(nitems), dim3(BS), lds, s, a);
+    if (!M) return "NULL matrix";
+    if (M->field->p <= 2 || M->field->p > 0xfffffffbLL) return "prime out of range (2 < p <= 0xfffffffb)";
+    if (M->n < 0 || M->m < 0 || !M->p || M->p[0] != 0) return "malformed matrix";
+    if (!M->x) return "matrix without values (x == NULL)";
+    for (int t = 0; t < M->n; t++)
+        if (M->p[t + 1] < M->p[t]) return "row pointers must not decrease";
+    const i64 nz = M->p[M->n];
+    if (nz > 0 && !M->j) return "malformed matrix";
+    const unsigned um = (unsigned)M->m;
+    for (i64 k = 0; k < nz; k++)
+        if ((unsigned)M->j[k] >= um) return "a column index lies outside the matrix";
+    return nullptr;
 }
 
-void batch_launch_class(int cls, BatchArgs a, const int *items, int nitems, hipStream_t s)
+inline size_t batch_align(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// host matrices on the device as one concatenated CSR: row pointers (global entry offsets) | columns | values in one buffer;
+// row0[f] = where the n + 1 pointers of list[f] start in P
+struct BatchStaged {
+    DevBuf<unsigned char> buf;
+    const i64d *P = nullptr;
+    const int *J = nullptr, *X = nullptr;
+    std::vector<i64> row0;
+};
+
+void batch_stage(const std::vector<const struct spasm_csr *> &list, BatchStaged &out)
 {
+    i64 rows_total = 0, nnz_total = 0;
+    out.row0.assign(list.size(), 0);
+    for (size_t f = 0; f < list.size(); f++) {
+        out.row0[f] = rows_total;
+        rows_total += (i64)list[f]->n + 1;
+        nnz_total += list[f]->p[list[f]->n];
+    }
+    const size_t o_j = batch_align((size_t)rows_total * sizeof(i64d));
+    const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
+    const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
+    std::vector<unsigned char> stage(in_bytes);
+    i64d *P = (i64d *)stage.data();
+    int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
+    i64 e0 = 0, r0 = 0;
+    for (const struct spasm_csr *M : list) {
+        const i64 nz = M->p[M->n];
+        for (int t = 0; t <= M->n; t++) P[r0 + t] = (i64d)(e0 + M->p[t]);
+        if (nz > 0) {
+            memcpy(J + e0, M->j, (size_t)nz * sizeof(int));
+            memcpy(X + e0, M->x, (size_t)nz * sizeof(int));
+        }
+        r0 += (i64)M->n + 1;
+        e0 += nz;
+    }
+    out.buf.alloc(in_bytes);
+    HIPCHK(hipMemcpy(out.buf.p, stage.data(), in_bytes, hipMemcpyHostToDevice)); // (blocking: stage ends with this scope)
+    out.P = (const i64d *)out.buf.p;
+    out.J = (const int *)(out.buf.p + o_j);
+    out.X = (const int *)(out.buf.p + o_x);
+}
+
+// The elimination kernels of a path, one per class: kern[c] is the instance for kBatchClass[c].bs threads.  Args is BatchArgs or
+// SolveBatchArgs; both carry items and the LDS layout (cap, bw, rmax), which are filled in here.
+template <class Args> struct ElimKernels { void (*k[BATCH_NCLASS])(Args); };
+const ElimKernels<BatchArgs> kBatchElim = {{k_batch_elim<64>, k_batch_elim<128>, k_batch_elim<256>, k_batch_elim<512>}};
+const ElimKernels<SolveBatchArgs> kSolveElim = {{k_solve_elim<64>, k_solve_elim<128>, k_solve_elim<256>, k_solve_elim<512>}};
+
+// one class of jobs; the dynamic-LDS attribute of a kernel is set once per device
+template <class Args> void batch_launch_class(const ElimKernels<Args> &kern, int cls, Args a, const int *items, int nitems, hipStream_t s)
+{
+    static bool attr_done[kMaxDev][BATCH_NCLASS] = {};
     a.items = items;
     a.cap = kBatchClass[cls].cap;
     batch_layout(cls, a.bw, a.rmax);
     const size_t lds = (size_t)batch_lds_words(a.cap, a.bw, a.rmax) * sizeof(int);
-    switch (cls) {
-    case 0: batch_launch<64>(a, nitems, lds, s); break;
-    case 1: batch_launch<128>(a, nitems, lds, s); break;
-    case 2: batch_launch<256>(a, nitems, lds, s); break;
-    default: batch_launch<512>(a, nitems, lds, s); break;
+    bool &done = attr_done[current_device()][cls];
+    if (!done) {
+        HIPCHK(hipFuncSetAttribute((const void *)kern.k[cls], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        done = true;
     }
-    HIPCHK(hipGetLastError());
+    void *args[] = {&a};
+    HIPCHK(hipLaunchKernel((const void *)kern.k[cls], dim3(nitems), dim3(kBatchClass[cls].bs), args, lds, s));
+}
+
+// Jobs lo .. hi - 1 by class (a stable counting sort into items[lo .. hi), which must live until the stream has passed the
+// upload), the items to the device, one launch per class that occurs.  `started`, when given, is recorded between the upload and
+// the first launch.  Returns the launches.
+template <class Args>
+int batch_launch_jobs(const ElimKernels<Args> &kern, const std::vector<unsigned char> &cls, int lo, int hi, std::vector<int> &items, int *d_items, const Args &a,
+                      hipEvent_t started, hipStream_t s)
+{
+    int hist[BATCH_NCLASS] = {0, 0, 0, 0}, at[BATCH_NCLASS], sum = lo, launches = 0;
+    for (int q = lo; q < hi; q++) hist[cls[(size_t)q]]++;
+    for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += hist[k]; }
+    for (int q = lo; q < hi; q++) items[(size_t)at[cls[(size_t)q]]++] = q;
+    HIPCHK(hipMemcpyAsync(d_items + lo, items.data() + lo, (size_t)(hi - lo) * sizeof(int), hipMemcpyHostToDevice, s));
+    if (started) HIPCHK(hipEventRecord(started, s));
+    int first = lo;
+    for (int k = 0; k < BATCH_NCLASS; k++) {
+        if (hist[k] > 0) { batch_launch_class(kern, k, a, d_items + first, hist[k], s); launches++; }
+        first += hist[k];
+    }
+    return launches;
 }
 
 // bytes of device buffers one chunk may use: a third of the free device memory (SPASM_AMD_BATCH_SCRATCH_MB: a smaller figure, for
@@ -6576,6 +6659,50 @@ size_t batch_budget()
     const char *e = getenv("SPASM_AMD_BATCH_SCRATCH_MB");
     if (e && atof(e) > 0) b = std::min(b, (size_t)(atof(e) * 1048576.0));
     return b;
+}
+
+// chunks of consecutive jobs whose needs (bytes, need(q)) fit the budget together; a job over the budget is a chunk of its own.
+// Chunk c = jobs cut[c] .. cut[c + 1] - 1.
+template <class Need> std::vector<int> batch_cut(int njobs, size_t budget, Need need)
+{
+    std::vector<int> cut(1, 0);
+    size_t used = 0;
+    for (int q = 0; q < njobs; q++) {
+        const size_t bytes = need(q);
+        if (used > 0 && used + bytes > budget) { cut.push_back(q); used = 0; }
+        used += bytes;
+    }
+    cut.push_back(njobs);
+    return cut;
+}
+
+// The end of a chunk's eliminations: rowstart[0 .. slots] = exclusive scan of the row counts cnt[0 .. slots] (cnt[slots] is the
+// scan's sentinel, which the caller has zeroed before the timed span).  Returns the entries of the chunk, read back from
+// rowstart[slots]; they must fit the slices (ents).
+i64 batch_chunk_entries(const int *cnt, i64 slots, i64 ents, DevBuf<i64d> &rowstart, Scanner &scan, hipStream_t s)
+{
+    rowstart.ensure((size_t)slots + 1);
+    scan.exclusive(cnt, rowstart.p, (size_t)slots + 1, s);
+    i64d total = 0;
+    HIPCHK(hipMemcpyAsync(&total, rowstart.p + slots, sizeof total, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (total < 0 || total > ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+    return total;
+}
+
+// nrows x m matrix from the lengths of its rows and the packed entries ent[at ..] (of which there are `total`); advances at
+struct spasm_csr *batch_rows_to_csr(int nrows, int m, i64 prime, const int *len, const int2 *ent, i64 total, i64 &at)
+{
+    i64 nz = 0;
+    for (int k = 0; k < nrows; k++) nz += len[k];
+    if (at + nz > total) throw EngineError("internal error: row counts and entry count disagree");
+    struct spasm_csr *R = spasm_csr_alloc(nrows, m, nz, prime, true);
+    if (!R) throw EngineError("out of host memory");
+    R->p[0] = 0;
+    for (int k = 0; k < nrows; k++) R->p[k + 1] = R->p[k] + len[k];
+    for (i64 e = 0; e < nz; e++) { R->j[e] = ent[at + e].x; R->x[e] = ent[at + e].y; }
+    at += nz;
+    return R;
 }
 
 // most entries of the output of an n x m matrix: U of rank r has r rows of at most m - r + 1 entries, K has m - r rows of at most
@@ -6591,25 +6718,32 @@ i64 batch_entry_cap(int mode, int n, int m)
     return (m - r) * (r + 1);
 }
 
+// what a call returns, owned until it is handed over: lu (BATCH_LU) or K (BATCH_KERNEL) per matrix, and every rank
 struct BatchResults {
     std::vector<struct spasm_lu *> lu;
     std::vector<struct spasm_csr *> K;
+    std::vector<i64> ranks;
+    BatchResults(int mode, int count) : lu(mode == BATCH_LU ? (size_t)count : 0, nullptr), K(mode == BATCH_KERNEL ? (size_t)count : 0, nullptr), ranks((size_t)count, 0) {}
     ~BatchResults()
     {
         for (auto *x : lu) spasm_lu_free(x);
         for (auto *x : K) spasm_csr_free(x);
     }
+    // to the caller's array of the mode, all at once
+    void hand_over(int mode, struct spasm_lu **lu_out, struct spasm_csr **k_out, i64 *rank_out)
+    {
+        if (mode == BATCH_LU) { memcpy(lu_out, lu.data(), sizeof(struct spasm_lu *) * lu.size()); lu.clear(); }
+        else if (mode == BATCH_KERNEL) { memcpy(k_out, K.data(), sizeof(struct spasm_csr *) * K.size()); K.clear(); }
+        else memcpy(rank_out, ranks.data(), sizeof(i64) * ranks.size());
+    }
 };
-
-inline size_t batch_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // A matrix of the LDS path as the descriptors need it: its shape, its prime, and where its n + 1 row pointers start in P.
 struct BatchItem { int n, m; i64 row0; i64 prime; };
 
 // The LDS path from the descriptors on.  fast[f] = place, in the call's list, of the f-th matrix; item[f] describes it; P, J, X: the
-// concatenated CSR on the device (P holds global entry offsets).  Results go to res / ranks at fast[f]; g_batch_stats[3 .. 7] are filled.
-void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, BatchResults &res,
-                std::vector<i64> &ranks)
+// concatenated CSR on the device (P holds global entry offsets).  Results go to res at fast[f]; g_batch_stats[3 .. 7] are filled.
+void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, BatchResults &res)
 {
     i64 *st = g_batch_stats;
     const int nf = (int)fast.size();
@@ -6638,61 +6772,40 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
         recw[(size_t)f] = mode == BATCH_LU ? ((2 + (i64)d.m + d.n + 1) & ~(i64)1) : 2;
         st[7] = std::max<i64>(st[7], (i64)d.n * d.ld);
     }
-    std::vector<int> cut; // chunk c = fast matrices cut[c] .. cut[c + 1] - 1 (in batch order)
-    cut.push_back(0);
-    if (mode == BATCH_RANK) {
-        cut.push_back(nf);
-    } else {
-        size_t used = 0;
-        for (int f = 0; f < nf; f++) {
-            // scratch + packed entries, record, row counts and their scan
-            const size_t need = (size_t)ecap[(size_t)f] * 2 * sizeof(int2) + (size_t)recw[(size_t)f] * sizeof(int) + (size_t)desc[(size_t)f].nslots * (sizeof(int) + sizeof(i64d));
-            if (used > 0 && used + need > budget) { cut.push_back(f); used = 0; }
-            used += need;
-        }
-        cut.push_back(nf);
-    }
+    // per matrix: scratch + packed entries, record, row counts and their scan; the ranks alone need none of them
+    const std::vector<int> cut = batch_cut(nf, budget, [&](int f) {
+        return mode == BATCH_RANK ? (size_t)0 : (size_t)ecap[(size_t)f] * 2 * sizeof(int2) + (size_t)recw[(size_t)f] * sizeof(int) + (size_t)desc[(size_t)f].nslots * (sizeof(int) + sizeof(i64d));
+    });
     const int nchunks = (int)cut.size() - 1;
-    // inside a chunk the matrices go by class (a stable counting sort), and their slices are laid out in that order
-    std::vector<int> items((size_t)nf);
-    struct ChunkPlan { int hist[BATCH_NCLASS]; i64 slots, recs, ents; };
-    std::vector<ChunkPlan> plan((size_t)nchunks);
+    // slots, records and slices of a chunk, laid out in batch order
+    struct ChunkPlan { i64 slots, recs, ents; };
+    std::vector<ChunkPlan> plan((size_t)nchunks, ChunkPlan{0, 0, 0});
     for (int c = 0; c < nchunks; c++) {
         ChunkPlan &pl = plan[(size_t)c];
-        memset(&pl, 0, sizeof pl);
-        const int lo = cut[(size_t)c], hi = cut[(size_t)c + 1];
-        for (int f = lo; f < hi; f++) pl.hist[cls[(size_t)f]]++;
-        int at[BATCH_NCLASS], sum = lo;
-        for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += pl.hist[k]; }
-        for (int f = lo; f < hi; f++) items[(size_t)at[cls[(size_t)f]]++] = f;
-        for (int q = lo; q < hi; q++) {
-            BatchDesc &d = desc[(size_t)items[(size_t)q]];
+        for (int f = cut[(size_t)c]; f < cut[(size_t)c + 1]; f++) {
+            BatchDesc &d = desc[(size_t)f];
             d.slot0 = pl.slots;
             d.rec = pl.recs;
             d.slice = pl.ents;
             pl.slots += d.nslots;
-            pl.recs += recw[(size_t)items[(size_t)q]];
-            pl.ents += ecap[(size_t)items[(size_t)q]];
+            pl.recs += recw[(size_t)f];
+            pl.ents += ecap[(size_t)f];
         }
     }
-    // ---- descriptors | items to the device (the row pointers, columns and values are there already)
-    const size_t o_desc = 0;
-    const size_t o_items = batch_align(o_desc + (size_t)nf * sizeof(BatchDesc));
-    const size_t in_bytes = batch_align(o_items + (size_t)nf * sizeof(int));
-    std::vector<unsigned char> stage(in_bytes);
-    memcpy(stage.data() + o_desc, desc.data(), (size_t)nf * sizeof(BatchDesc));
-    memcpy(stage.data() + o_items, items.data(), (size_t)nf * sizeof(int));
-    DevBuf<unsigned char> in;
-    in.alloc(in_bytes);
-    HIPCHK(hipMemcpyAsync(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, s));
+    // ---- descriptors to the device (the row pointers, columns and values are there already)
+    DevBuf<BatchDesc> d_desc;
+    DevBuf<int> d_items;
+    d_desc.alloc((size_t)nf);
+    d_items.alloc((size_t)nf);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+    std::vector<int> items((size_t)nf);
     BatchArgs a;
     memset(&a, 0, sizeof a);
-    a.desc = (const BatchDesc *)(in.p + o_desc);
+    a.desc = d_desc.p;
     a.P = dP;
     a.J = dJ;
     a.X = dX;
     a.mode = mode;
-    const int *d_items = (const int *)(in.p + o_items);
     SpgEvents ev;
     i64 launches = 0, entries = 0;
     double ms = 0;
@@ -6701,24 +6814,18 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
         DevBuf<int> drank;
         drank.alloc((size_t)nf);
         a.rank = drank.p;
-        HIPCHK(hipEventRecord(ev.e[0], s));
-        int first = 0;
-        for (int k = 0; k < BATCH_NCLASS; k++) {
-            const int cn = plan[0].hist[k];
-            if (cn > 0) { batch_launch_class(k, a, d_items + first, cn, s); launches++; }
-            first += cn;
-        }
+        launches += batch_launch_jobs(kBatchElim, cls, 0, nf, items, d_items.p, a, ev.e[0], s);
         HIPCHK(hipEventRecord(ev.e[1], s));
         std::vector<int> hr((size_t)nf);
         HIPCHK(hipMemcpyAsync(hr.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         ms += ev.ms(0, 1);
-        for (int f = 0; f < nf; f++) ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
+        for (int f = 0; f < nf; f++) res.ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
     } else {
         DevBuf<int2> scratch;
         DevBuf<unsigned char> out;
         DevBuf<i64d> rowstart;
-        DevBuf<unsigned char> scan_tmp;
+        Scanner scan;
         std::vector<unsigned char> host;
         for (int c = 0; c < nchunks; c++) {
             const ChunkPlan &pl = plan[(size_t)c];
@@ -6728,31 +6835,15 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
             const size_t o_ent = batch_align(o_rec + (size_t)pl.recs * sizeof(int));
             scratch.ensure((size_t)pl.ents + 1);
             out.ensure(o_ent + (size_t)pl.ents * sizeof(int2) + 16);
-            rowstart.ensure((size_t)pl.slots + 1);
-            int *d_cnt = (int *)out.p;
-            a.cnt = d_cnt;
+            a.cnt = (int *)out.p;
             a.rec = (int *)(out.p + o_rec);
             a.scratch = scratch.p;
-            HIPCHK(hipMemsetAsync(d_cnt + pl.slots, 0, sizeof(int), s));
-            HIPCHK(hipEventRecord(ev.e[0], s));
-            int first = lo;
-            for (int k = 0; k < BATCH_NCLASS; k++) {
-                if (pl.hist[k] > 0) { batch_launch_class(k, a, d_items + first, pl.hist[k], s); launches++; }
-                first += pl.hist[k];
-            }
-            {
-                size_t bytes = 0;
-                HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
-                scan_tmp.ensure(bytes);
-                HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt, rowstart.p, (i64d)0, (size_t)pl.slots + 1, rocprim::plus<i64d>(), s));
-                launches++;
-            }
-            i64d total = 0;
-            HIPCHK(hipMemcpyAsync(&total, rowstart.p + pl.slots, sizeof total, hipMemcpyDeviceToHost, s));
-            HIPCHK(hipStreamSynchronize(s));
-            if (total < 0 || total > pl.ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+            HIPCHK(hipMemsetAsync(a.cnt + pl.slots, 0, sizeof(int), s));
+            launches += batch_launch_jobs(kBatchElim, cls, lo, hi, items, d_items.p, a, ev.e[0], s);
+            const i64 total = batch_chunk_entries(a.cnt, pl.slots, pl.ents, rowstart, scan, s);
+            launches++;
             if (total > 0) {
-                hipLaunchKernelGGL(k_batch_pack, dim3(hi - lo), dim3(64), 0, s, a.desc, d_items + lo, mode, (const int *)a.rec, (const int *)d_cnt,
+                hipLaunchKernelGGL(k_batch_pack, dim3(hi - lo), dim3(64), 0, s, a.desc, (const int *)d_items.p + lo, mode, (const int *)a.rec, (const int *)a.cnt,
                                    (const i64d *)rowstart.p, (const int2 *)scratch.p, (int2 *)(out.p + o_ent));
                 HIPCHK(hipGetLastError());
                 launches++;
@@ -6769,22 +6860,14 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
             const int *h_rec = (const int *)(host.data() + o_rec);
             const int2 *h_ent = (const int2 *)(host.data() + o_ent);
             i64 at = 0;
-            for (int q = lo; q < hi; q++) {
-                const int f = items[(size_t)q], i = fast[(size_t)f];
+            for (int f = lo; f < hi; f++) {
+                const int i = fast[(size_t)f];
                 const BatchDesc &d = desc[(size_t)f];
-                const int *rec = h_rec + d.rec, *rc = h_cnt + d.slot0;
+                const int *rec = h_rec + d.rec;
                 const int r = rec[0], n = d.n, m = d.m;
-                const int nrows = mode == BATCH_LU ? r : m - r;
                 if (r < 0 || r > std::min(n, m)) throw EngineError("internal error: rank outside its bounds");
-                i64 nz = 0;
-                for (int k = 0; k < nrows; k++) nz += rc[k];
-                if (at + nz > total) throw EngineError("internal error: row counts and entry count disagree");
-                struct spasm_csr *R = spasm_csr_alloc(nrows, m, nz, d.F.p, true);
-                if (!R) throw EngineError("out of host memory");
-                for (int k = 0; k < nrows; k++) R->p[k + 1] = R->p[k] + rc[k];
-                for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[at + e].x; R->x[e] = h_ent[at + e].y; }
-                at += nz;
-                ranks[(size_t)i] = r;
+                struct spasm_csr *R = batch_rows_to_csr(mode == BATCH_LU ? r : m - r, m, d.F.p, h_cnt + d.slot0, h_ent, total, at);
+                res.ranks[(size_t)i] = r;
                 if (mode == BATCH_KERNEL) { res.K[(size_t)i] = R; continue; }
                 struct spasm_lu *N = (struct spasm_lu *)malloc(sizeof *N);
                 const int plen = std::max(std::max(n, m), 1);
@@ -6812,7 +6895,7 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
 }
 
 // one matrix through the general path
-void batch_slow(int mode, int i, const struct spasm_csr *M, struct echelonize_opts *opts, BatchResults &res, std::vector<i64> &ranks)
+void batch_slow(int mode, int i, const struct spasm_csr *M, struct echelonize_opts *opts, BatchResults &res)
 {
     if (mode == BATCH_RANK) {
         i64 r = -1;
@@ -6823,7 +6906,7 @@ void batch_slow(int mode, int i, const struct spasm_csr *M, struct echelonize_op
         } else {
             (void)do_echelonize(M, opts, &r);
         }
-        ranks[(size_t)i] = r;
+        res.ranks[(size_t)i] = r;
     } else if (mode == BATCH_LU) {
         res.lu[(size_t)i] = do_echelonize(M, opts);
     } else {
@@ -6845,28 +6928,12 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
     if (count < 0) throw EngineError("count < 0");
     if (count == 0) return;
     if (!A || (mode == BATCH_LU && !lu_out) || (mode == BATCH_KERNEL && !k_out) || (mode == BATCH_RANK && !rank_out)) throw EngineError("NULL array");
-    char msg[160];
-    for (int i = 0; i < count; i++) {
-        const struct spasm_csr *M = A[i];
-        const char *bad = nullptr;
-        if (!M) bad = "NULL matrix";
-        else if (M->field->p <= 2 || M->field->p > 0xfffffffbLL) bad = "prime out of range (2 < p <= 0xfffffffb)";
-        else if (M->n < 0 || M->m < 0 || !M->p || M->p[0] != 0) bad = "malformed matrix";
-        else if (!M->x) bad = "matrix without values (A[i]->x == NULL)";
-        else {
-            for (int t = 0; t < M->n && !bad; t++)
-                if (M->p[t + 1] < M->p[t]) bad = "row pointers must not decrease";
-            const i64 nz = bad ? 0 : M->p[M->n];
-            if (!bad && nz > 0 && !M->j) bad = "malformed matrix";
-            const unsigned um = (unsigned)M->m;
-            for (i64 k = 0; k < nz && !bad; k++)
-                if ((unsigned)M->j[k] >= um) bad = "a column index lies outside the matrix";
-        }
-        if (bad) {
+    for (int i = 0; i < count; i++)
+        if (const char *bad = batch_check(A[i])) {
+            char msg[160];
             snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
             throw EngineError(msg);
         }
-    }
     require_device();
     const bool fast_ok = !opts || !opts->L;
     std::vector<int> fast, slow;
@@ -6875,58 +6942,23 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
         if (fast_ok && M->n <= BATCH_LIMIT && M->m <= BATCH_LIMIT && (i64)M->n * M->m <= BATCH_LIMIT) fast.push_back(i);
         else slow.push_back(i);
     }
-    BatchResults res;
-    if (mode == BATCH_LU) res.lu.assign((size_t)count, nullptr);
-    if (mode == BATCH_KERNEL) res.K.assign((size_t)count, nullptr);
-    std::vector<i64> ranks((size_t)count, 0);
+    BatchResults res(mode, count);
     i64 *st = g_batch_stats;
     st[0] = count;
     st[1] = (i64)fast.size();
     st[2] = (i64)slow.size();
-
-    // ---- staging of the host matrices: one upload of row pointers | columns | values, concatenated
-    const int nf = (int)fast.size();
-    if (nf > 0) {
-        hipStream_t s = nullptr;
-        std::vector<BatchItem> item((size_t)nf);
-        i64 rows_total = 0, nnz_total = 0;
-        for (int f = 0; f < nf; f++) {
-            const struct spasm_csr *M = A[fast[(size_t)f]];
-            item[(size_t)f] = BatchItem{M->n, M->m, rows_total, M->field->p};
-            rows_total += (i64)M->n + 1;
-            nnz_total += M->p[M->n];
-        }
-        const size_t o_p = 0;
-        const size_t o_j = batch_align(o_p + (size_t)rows_total * sizeof(i64d));
-        const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
-        const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
-        std::vector<unsigned char> stage(in_bytes);
-        {
-            i64d *P = (i64d *)(stage.data() + o_p);
-            int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
-            i64 e0 = 0, r0 = 0;
-            for (int f = 0; f < nf; f++) {
-                const struct spasm_csr *M = A[fast[(size_t)f]];
-                const i64 nz = M->p[M->n];
-                for (int t = 0; t <= M->n; t++) P[r0 + t] = (i64d)(e0 + M->p[t]);
-                if (nz > 0) {
-                    memcpy(J + e0, M->j, (size_t)nz * sizeof(int));
-                    memcpy(X + e0, M->x, (size_t)nz * sizeof(int));
-                }
-                r0 += (i64)M->n + 1;
-                e0 += nz;
-            }
-        }
-        DevBuf<unsigned char> in;
-        in.alloc(in_bytes);
-        HIPCHK(hipMemcpyAsync(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice, s));
-        batch_fast(mode, fast, item, (const i64d *)(in.p + o_p), (const int *)(in.p + o_j), (const int *)(in.p + o_x), res, ranks);
+    if (!fast.empty()) {
+        std::vector<const struct spasm_csr *> list;
+        for (int i : fast) list.push_back(A[i]);
+        BatchStaged in;
+        batch_stage(list, in);
+        std::vector<BatchItem> item;
+        for (size_t f = 0; f < list.size(); f++) item.push_back(BatchItem{list[f]->n, list[f]->m, in.row0[f], list[f]->field->p});
+        batch_fast(mode, fast, item, in.P, in.J, in.X, res);
     }
     // ---- the others through the general path, one at a time
-    for (int i : slow) batch_slow(mode, i, A[i], opts, res, ranks);
-    if (mode == BATCH_LU) { memcpy(lu_out, res.lu.data(), sizeof(struct spasm_lu *) * (size_t)count); res.lu.clear(); }
-    else if (mode == BATCH_KERNEL) { memcpy(k_out, res.K.data(), sizeof(struct spasm_csr *) * (size_t)count); res.K.clear(); }
-    else memcpy(rank_out, ranks.data(), sizeof(i64) * (size_t)count);
+    for (int i : slow) batch_slow(mode, i, A[i], opts, res);
+    res.hand_over(mode, lu_out, k_out, rank_out);
 }
 
 } // namespace
@@ -7200,9 +7232,9 @@ struct spasm_csr *blocks_fetch(const spasm_amd_blocks *B, int b)
 
 // what the batch returns for an n x m matrix without entries: rank 0; U 0 x m, qinv = -1, p = the rows ascending; the kernel is the
 // whole space, vector t = -1 on column t
-void blocks_empty_result(int mode, int i, int n, int m, i64 prime, BatchResults &res, std::vector<i64> &ranks)
+void blocks_empty_result(int mode, int i, int n, int m, i64 prime, BatchResults &res)
 {
-    ranks[(size_t)i] = 0;
+    res.ranks[(size_t)i] = 0;
     if (mode == BATCH_RANK) return;
     if (mode == BATCH_KERNEL) {
         struct spasm_csr *K = spasm_csr_alloc(m, m, m, prime, true);
@@ -7249,30 +7281,25 @@ void blocks_run(int mode, spasm_amd_blocks *B, struct echelonize_opts *opts, str
             item.push_back(BatchItem{(int)rn, (int)cn, B->h_row_start[(size_t)b] + b, B->prime});
         }
     }
-    BatchResults res;
-    if (mode == BATCH_LU) res.lu.assign((size_t)count, nullptr);
-    if (mode == BATCH_KERNEL) res.K.assign((size_t)count, nullptr);
-    std::vector<i64> ranks((size_t)count, 0);
+    BatchResults res(mode, count);
     i64 *st = g_batch_stats;
     st[0] = count;
     st[1] = (i64)(fast.size() + none.size()); // (a block without entries belongs to the LDS path, which has nothing to do for it)
     st[2] = (i64)slow.size();
-    batch_fast(mode, fast, item, B->P.p, B->J.p, B->X.p, res, ranks);
+    batch_fast(mode, fast, item, B->P.p, B->J.p, B->X.p, res);
     for (int b : none)
-        blocks_empty_result(mode, b, (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]), (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]), B->prime, res, ranks);
+        blocks_empty_result(mode, b, (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]), (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]), B->prime, res);
     for (int b : slow) {
         struct spasm_csr *M = blocks_fetch(B, b);
         try {
-            batch_slow(mode, b, M, opts, res, ranks);
+            batch_slow(mode, b, M, opts, res);
         } catch (...) {
             spasm_csr_free(M);
             throw;
         }
         spasm_csr_free(M);
     }
-    if (mode == BATCH_LU) { memcpy(lu_out, res.lu.data(), sizeof(struct spasm_lu *) * (size_t)count); res.lu.clear(); }
-    else if (mode == BATCH_KERNEL) { memcpy(k_out, res.K.data(), sizeof(struct spasm_csr *) * (size_t)count); res.K.clear(); }
-    else memcpy(rank_out, ranks.data(), sizeof(i64) * (size_t)count);
+    res.hand_over(mode, lu_out, k_out, rank_out);
 }
 
 template <class T> void blocks_copy_out(T *dst, const DevBuf<T> &src, size_t cnt, hipStream_t s)
@@ -7343,51 +7370,9 @@ void solve_jobs(const std::vector<SolveSys> &sys, std::vector<SolveDesc> &desc, 
     }
 }
 
-template <int BS> void solve_launch(const SolveBatchArgs &a, int nitems, size_t lds, hipStream_t s)
-{
-    static bool attr_done[kMaxDev] = {false};
-    bool &done = attr_done[current_device()];
-    if (!done) {
-        HIPCHK(hipFuncSetAttribute((const void *)k_solve_elim<BS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        done = true;
-    }
-    hipLaunchKernelGGL((k_solve_elim<BS>), dim3(nitems), dim3(BS), lds, s, a);
-}
-
-void solve_launch_class(int cls, SolveBatchArgs a, const int *items, int nitems, hipStream_t s)
-{
-    a.items = items;
-    a.cap = kBatchClass[cls].cap;
-    batch_layout(cls, a.bw, a.rmax);
-    const size_t lds = (size_t)batch_lds_words(a.cap, a.bw, a.rmax) * sizeof(int);
-    switch (cls) {
-    case 0: solve_launch<64>(a, nitems, lds, s); break;
-    case 1: solve_launch<128>(a, nitems, lds, s); break;
-    case 2: solve_launch<256>(a, nitems, lds, s); break;
-    default: solve_launch<512>(a, nitems, lds, s); break;
-    }
-    HIPCHK(hipGetLastError());
-}
-
-// jobs lo .. hi by class (a stable counting sort into items[lo .. hi)), one launch per class that occurs; returns the launches
-int solve_launch_jobs(const std::vector<unsigned char> &cls, int lo, int hi, std::vector<int> &items, int *d_items, const SolveBatchArgs &a, hipStream_t s)
-{
-    int hist[BATCH_NCLASS] = {0, 0, 0, 0}, at[BATCH_NCLASS], sum = lo, launches = 0;
-    for (int q = lo; q < hi; q++) hist[cls[(size_t)q]]++;
-    for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += hist[k]; }
-    for (int q = lo; q < hi; q++) items[(size_t)at[cls[(size_t)q]]++] = q;
-    HIPCHK(hipMemcpyAsync(d_items + lo, items.data() + lo, (size_t)(hi - lo) * sizeof(int), hipMemcpyHostToDevice, s));
-    int first = lo;
-    for (int k = 0; k < BATCH_NCLASS; k++) {
-        if (hist[k] > 0) { solve_launch_class(k, a, d_items + first, hist[k], s); launches++; }
-        first += hist[k];
-    }
-    return launches;
-}
-
 // The LDS path of spasm_amd_solve_batch from the systems on: h_cnt / h_ok per slot, h_ent the rows of X back to back in slot order.
-void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, const int *dJ, const int *dX, const i64d *dBP, const int *dBJ, const int *dBX,
-                std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok, std::vector<int2> &h_ent)
+void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged &A, const BatchStaged &B, std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok,
+                std::vector<int2> &h_ent)
 {
     i64 *st = g_solve_stats;
     if (sys.empty()) return;
@@ -7399,19 +7384,9 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, co
     solve_jobs(sys, desc, cls, ecap);
     const int nj = (int)desc.size();
     st[3] = nj;
-    // ---- chunks of consecutive jobs; slots and slices relative to the chunk
-    std::vector<int> cut;
-    cut.push_back(0);
-    {
-        size_t used = 0;
-        for (int q = 0; q < nj; q++) {
-            // scratch + packed entries, and per slot: count, its scan, source, ok
-            const size_t need = (size_t)ecap[(size_t)q] * 2 * sizeof(int2) + (size_t)desc[(size_t)q].w * (sizeof(int) + 2 * sizeof(i64d) + 1);
-            if (used > 0 && used + need > budget) { cut.push_back(q); used = 0; }
-            used += need;
-        }
-        cut.push_back(nj);
-    }
+    // ---- chunks of consecutive jobs (per job: scratch + packed entries, and per slot: count, its scan, source, ok); slots and
+    // slices relative to the chunk
+    const std::vector<int> cut = batch_cut(nj, budget, [&](int q) { return (size_t)ecap[(size_t)q] * 2 * sizeof(int2) + (size_t)desc[(size_t)q].w * (sizeof(int) + 2 * sizeof(i64d) + 1); });
     const int nchunks = (int)cut.size() - 1;
     std::vector<i64> c_slot0((size_t)nchunks), c_slots((size_t)nchunks), c_ents((size_t)nchunks);
     for (int c = 0; c < nchunks; c++) {
@@ -7430,8 +7405,9 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, co
     DevBuf<SolveDesc> d_desc;
     DevBuf<int> d_items, d_cnt;
     DevBuf<i64d> d_src, rowstart;
-    DevBuf<unsigned char> d_ok, scan_tmp;
+    DevBuf<unsigned char> d_ok;
     DevBuf<int2> scratch, out;
+    Scanner scan;
     d_desc.alloc((size_t)nj);
     d_items.alloc((size_t)nj);
     HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
@@ -7439,8 +7415,8 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, co
     SolveBatchArgs a;
     memset(&a, 0, sizeof a);
     a.desc = d_desc.p;
-    a.P = dP; a.J = dJ; a.X = dX;
-    a.BP = dBP; a.BJ = dBJ; a.BX = dBX;
+    a.P = A.P; a.J = A.J; a.X = A.X;
+    a.BP = B.P; a.BJ = B.J; a.BX = B.X;
     SpgEvents ev;
     i64 launches = 0, entries = 0;
     double ms = 0;
@@ -7453,26 +7429,15 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const i64d *dP, co
         d_cnt.ensure((size_t)slots + 1);
         d_src.ensure((size_t)slots);
         d_ok.ensure((size_t)slots);
-        rowstart.ensure((size_t)slots + 1);
         scratch.ensure((size_t)ents + 1);
         a.cnt = d_cnt.p;
         a.src = d_src.p;
         a.ok = d_ok.p;
         a.scratch = scratch.p;
         HIPCHK(hipMemsetAsync(d_cnt.p + slots, 0, sizeof(int), s));
-        HIPCHK(hipEventRecord(ev.e[0], s));
-        launches += solve_launch_jobs(cls, lo, hi, items, d_items.p, a, s);
-        {
-            size_t bytes = 0;
-            HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)d_cnt.p, rowstart.p, (i64d)0, (size_t)slots + 1, rocprim::plus<i64d>(), s));
-            scan_tmp.ensure(bytes);
-            HIPCHK(rocprim::exclusive_scan(scan_tmp.p, bytes, (const int *)d_cnt.p, rowstart.p, (i64d)0, (size_t)slots + 1, rocprim::plus<i64d>(), s));
-            launches++;
-        }
-        i64d total = 0;
-        HIPCHK(hipMemcpyAsync(&total, rowstart.p + slots, sizeof total, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        if (total < 0 || total > ents) throw EngineError("internal error: a chunk wrote more entries than its slices hold");
+        launches += batch_launch_jobs(kSolveElim, cls, lo, hi, items, d_items.p, a, ev.e[0], s);
+        const i64 total = batch_chunk_entries(d_cnt.p, slots, ents, rowstart, scan, s);
+        launches++;
         if (total > 0) {
             out.ensure((size_t)total);
             hipLaunchKernelGGL(k_solve_pack, dim3((unsigned)slots), dim3(64), 0, s, (const int *)d_cnt.p, (const i64d *)d_src.p, (const i64d *)rowstart.p,
@@ -7541,59 +7506,6 @@ struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *
     return X;
 }
 
-// the checks of a matrix that need no device; NULL when it is well formed
-const char *solve_check(const struct spasm_csr *M)
-{
-    if (!M) return "NULL matrix";
-    if (M->field->p <= 2 || M->field->p > 0xfffffffbLL) return "prime out of range (2 < p <= 0xfffffffb)";
-    if (M->n < 0 || M->m < 0 || !M->p || M->p[0] != 0) return "malformed matrix";
-    if (!M->x) return "matrix without values (x == NULL)";
-    for (int t = 0; t < M->n; t++)
-        if (M->p[t + 1] < M->p[t]) return "row pointers must not decrease";
-    const i64 nz = M->p[M->n];
-    if (nz > 0 && !M->j) return "malformed matrix";
-    const unsigned um = (unsigned)M->m;
-    for (i64 k = 0; k < nz; k++)
-        if ((unsigned)M->j[k] >= um) return "a column index lies outside the matrix";
-    return nullptr;
-}
-
-// concatenated row pointers | columns | values of the matrices list[f] on the device; row0[f] = where the pointers of f start
-void solve_stage(const std::vector<const struct spasm_csr *> &list, DevBuf<unsigned char> &in, std::vector<i64> &row0, const i64d *&dP, const int *&dJ, const int *&dX,
-                 hipStream_t s)
-{
-    i64 rows_total = 0, nnz_total = 0;
-    row0.assign(list.size(), 0);
-    for (size_t f = 0; f < list.size(); f++) {
-        row0[f] = rows_total;
-        rows_total += (i64)list[f]->n + 1;
-        nnz_total += list[f]->p[list[f]->n];
-    }
-    const size_t o_j = batch_align((size_t)rows_total * sizeof(i64d));
-    const size_t o_x = batch_align(o_j + (size_t)nnz_total * sizeof(int));
-    const size_t in_bytes = batch_align(o_x + (size_t)nnz_total * sizeof(int));
-    std::vector<unsigned char> stage(in_bytes);
-    i64d *P = (i64d *)stage.data();
-    int *J = (int *)(stage.data() + o_j), *X = (int *)(stage.data() + o_x);
-    i64 e0 = 0, r0 = 0;
-    for (const struct spasm_csr *M : list) {
-        const i64 nz = M->p[M->n];
-        for (int t = 0; t <= M->n; t++) P[r0 + t] = (i64d)(e0 + M->p[t]);
-        if (nz > 0) {
-            memcpy(J + e0, M->j, (size_t)nz * sizeof(int));
-            memcpy(X + e0, M->x, (size_t)nz * sizeof(int));
-        }
-        r0 += (i64)M->n + 1;
-        e0 += nz;
-    }
-    in.alloc(in_bytes);
-    HIPCHK(hipMemcpy(in.p, stage.data(), in_bytes, hipMemcpyHostToDevice));
-    (void)s;
-    dP = (const i64d *)in.p;
-    dJ = (const int *)(in.p + o_j);
-    dX = (const int *)(in.p + o_x);
-}
-
 // Nothing is written to X / ok before all is done.
 void solve_batch_run(int count, const struct spasm_csr *const *A, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
 {
@@ -7603,9 +7515,9 @@ void solve_batch_run(int count, const struct spasm_csr *const *A, const struct s
     if (!A || !B || !X || !ok) throw EngineError("NULL array");
     char msg[200];
     for (int i = 0; i < count; i++) {
-        const char *bad = solve_check(A[i]);
+        const char *bad = batch_check(A[i]);
         const char *which = "A";
-        if (!bad) { bad = solve_check(B[i]); which = "B"; }
+        if (!bad) { bad = batch_check(B[i]); which = "B"; }
         if (!bad && A[i]->field->p != B[i]->field->p) { bad = "the primes of A and B differ"; which = "B"; }
         if (!bad && B[i]->m != A[i]->m) { bad = "B->m != A->m"; which = "B"; }
         if (!bad && B[i]->n > 0 && !ok[i]) { bad = "NULL array (ok)"; which = "B"; }
@@ -7640,40 +7552,26 @@ void solve_batch_run(int count, const struct spasm_csr *const *A, const struct s
     st[1] += (i64)fast.size();
     st[2] = (i64)slow.size();
     if (!fast.empty()) {
-        hipStream_t s = nullptr;
         std::vector<const struct spasm_csr *> la, lb;
         for (int i : fast) { la.push_back(A[i]); lb.push_back(B[i]); }
-        DevBuf<unsigned char> ina, inb;
-        std::vector<i64> arow0, brow0;
-        const i64d *dP, *dBP;
-        const int *dJ, *dX, *dBJ, *dBX;
-        solve_stage(la, ina, arow0, dP, dJ, dX, s);
-        solve_stage(lb, inb, brow0, dBP, dBJ, dBX, s);
+        BatchStaged ina, inb;
+        batch_stage(la, ina);
+        batch_stage(lb, inb);
         std::vector<SolveSys> sys;
         i64 nslots = 0;
         for (size_t f = 0; f < fast.size(); f++) {
             const int i = fast[f];
-            sys.push_back(SolveSys{A[i]->n, A[i]->m, B[i]->n, arow0[f], brow0[f], nslots, A[i]->field->p});
+            sys.push_back(SolveSys{A[i]->n, A[i]->m, B[i]->n, ina.row0[f], inb.row0[f], nslots, A[i]->field->p});
             nslots += B[i]->n;
         }
         std::vector<int> h_cnt;
         std::vector<unsigned char> h_ok;
         std::vector<int2> h_ent;
-        solve_fast(sys, nslots, dP, dJ, dX, dBP, dBJ, dBX, h_cnt, h_ok, h_ent);
+        solve_fast(sys, nslots, ina, inb, h_cnt, h_ok, h_ent);
         i64 at = 0;
         for (size_t f = 0; f < fast.size(); f++) {
             const int i = fast[f], K = sys[f].K;
-            const int *rc = h_cnt.data() + sys[f].slot0;
-            i64 nz = 0;
-            for (int k = 0; k < K; k++) nz += rc[k];
-            if (at + nz > (i64)h_ent.size()) throw EngineError("internal error: row counts and entry count disagree");
-            struct spasm_csr *R = spasm_csr_alloc(K, sys[f].n, nz, sys[f].prime, true);
-            if (!R) throw EngineError("out of host memory");
-            res.v[(size_t)i] = R;
-            R->p[0] = 0;
-            for (int k = 0; k < K; k++) R->p[k + 1] = R->p[k] + rc[k];
-            for (i64 e = 0; e < nz; e++) { R->j[e] = h_ent[(size_t)(at + e)].x; R->x[e] = h_ent[(size_t)(at + e)].y; }
-            at += nz;
+            res.v[(size_t)i] = batch_rows_to_csr(K, sys[f].n, sys[f].prime, h_cnt.data() + sys[f].slot0, h_ent.data(), (i64)h_ent.size(), at);
             memcpy(oks[(size_t)i].data(), h_ok.data() + sys[f].slot0, (size_t)K);
         }
     }
@@ -7851,7 +7749,7 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
         a.src = d_src.p;
         a.ok = d_ok.p;
         a.scratch = scratch.p;
-        launches += solve_launch_jobs(cls, 0, nj, items, d_items.p, a, s);
+        launches += batch_launch_jobs(kSolveElim, cls, 0, nj, items, d_items.p, a, nullptr, s);
         HIPCHK(hipStreamSynchronize(s)); // (items and desc are host vectors of this scope)
     }
     // ---- assemble
@@ -7867,12 +7765,7 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     hipLaunchKernelGGL(k_sv_rowok, dim3(cdiv(K, 256)), dim3(256), 0, s, K, (const i64d *)krun.p, (const int *)byrow.p, (const unsigned char *)d_ok.p, (const int *)d_cnt.p,
                        rowok.p, len.p);
     HIPCHK(hipGetLastError());
-    {
-        size_t bytes = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, bytes, (const int *)len.p, off.p, (i64d)0, (size_t)nruns + 1, rocprim::plus<i64d>(), s));
-        scan.tmp.ensure(bytes);
-        HIPCHK(rocprim::exclusive_scan(scan.tmp.p, bytes, (const int *)len.p, off.p, (i64d)0, (size_t)nruns + 1, rocprim::plus<i64d>(), s));
-    }
+    scan.exclusive((const int *)len.p, off.p, (size_t)nruns + 1, s);
     i64d total = 0;
     HIPCHK(hipMemcpyAsync(&total, off.p + nruns, sizeof total, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -7920,7 +7813,7 @@ void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct s
     if (!Rhs) throw EngineError("NULL matrix");
     if (Rhs->m != B->m) throw EngineError("Rhs->m differs from the columns of the handle's matrix");
     if (Rhs->field->p != B->prime) throw EngineError("the prime of Rhs differs from the handle's");
-    const char *bad = solve_check(Rhs);
+    const char *bad = batch_check(Rhs);
     if (bad) throw EngineError(bad);
     if (!X || (Rhs->n > 0 && !ok)) throw EngineError("NULL array");
     HIPCHK(hipSetDevice(B->dev));

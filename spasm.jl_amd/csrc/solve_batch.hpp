@@ -1,12 +1,11 @@
 // solve_batch.hpp -- X * A = B for many small matrices in one launch: one workgroup per (matrix, slab of right-hand sides), resident
-// in LDS from first load to last store.  The companion of batch.hpp; it shares that file's limits, classes and LDS layout.
+// in LDS from first load to last store.  The companion of batch.hpp; it shares that file's limits, classes, LDS layout and
+// elimination (batch_eliminate, which states the election rule and what the image holds afterwards).
 //
 // x * A = b is A^T * x^T = b^T.  A workgroup scatters the TRANSPOSED, AUGMENTED image into LDS: m rows (the columns of A), n + w
 // columns (the n rows of A, then the w right-hand sides of its slab, one per column), balanced residues in 32-bit words, row stride
-// ld.  It then runs the Gauss-Jordan elimination of k_batch_elim with the election restricted to the first n columns: the pivot of
-// column c is the first image row, not yet a pivot, that holds a non-zero there; the pivot row is subtracted from every other row
-// that holds the column; pivot rows are not normalised (pinv[k] keeps the inverse); the factors are written over column c; three
-// barriers per pivot.  The right-hand-side columns lie right of every elected column, so they ride along in the update.
+// ld.  It eliminates the image with the first n columns as candidates; the right-hand-side columns lie right of every candidate,
+// so they ride along in the update.
 //
 // Column c of the image is row c of A, and a column is elected exactly when it is not a combination of the columns before it.  The
 // pivot columns are therefore the CANONICAL ROW BASIS of A: row j belongs to it iff it is not a combination of rows 0 .. j-1.  After
@@ -66,20 +65,15 @@ __global__ __launch_bounds__(BS) void k_solve_elim(SolveBatchArgs a)
     const SolveDesc d = a.desc[a.items[blockIdx.x]];
     const ZpField F = d.F;
     const int n = d.n, m = d.m, ld = d.ld, W = d.n + d.w;
-    int *img = s_solve;
-    unsigned *rowflag = (unsigned *)(img + a.cap);
-    int *pivrow = (int *)(rowflag + 2 * a.bw);
-    int *pivcol = pivrow + a.rmax;
-    int *pinv = pivcol + a.rmax;
-    int *wmin = pinv + a.rmax;
+    const BatchLds L(s_solve, a.cap, a.bw, a.rmax, false); // (the pivot columns are not asked for)
+    int *img = L.img;
 
-    for (int e = tid; e < m * ld; e += BS) img[e] = 0;
-    for (int w = tid; w < a.bw; w += BS) rowflag[w] = 0;
+    batch_lds_clear<BS>(L, m * ld, a.bw);
     __syncthreads();
-    // TX lanes per row of A or of B (a power of two, at most a wave), TY rows at a time; a row holds at most m entries
-    int lt = 0;
-    while ((1 << lt) < m && lt < 6) lt++;
     {
+        // TX lanes per row of A or of B (a power of two, at most a wave), TY rows at a time; a row holds at most m entries
+        int lt = 0;
+        while ((1 << lt) < m && lt < 6) lt++;
         const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
         for (int i = ty; i < W; i += TY) {
             const bool rhs = i >= n;
@@ -89,64 +83,16 @@ __global__ __launch_bounds__(BS) void k_solve_elim(SolveBatchArgs a)
         }
     }
     __syncthreads();
-    // the update spreads TX lanes over the columns right of c
-    lt = 0;
-    while ((1 << lt) < W && lt < 6) lt++;
-    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
 
-    int r = 0, par = 0;
-    for (int c = 0; c < n && r < m; c++) {
-        // ---- election: the first image row that is not a pivot yet and holds column c
-        int pr = 0x7fffffff;
-        for (int base = 0; base < m; base += BS) {
-            const int i = base + tid;
-            const bool hit = i < m && !((rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + c] != 0;
-            const unsigned long long b = __ballot(hit);
-            if (lane == 0) wmin[par * 8 + wave] = b ? base + wave * 64 + (__ffsll((long long)b) - 1) : 0x7fffffff;
-            __syncthreads();
-            int best = 0x7fffffff;
-#pragma unroll
-            for (int w = 0; w < NW; w++) best = min(best, wmin[par * 8 + w]);
-            par ^= 1; // (the mailbox of the step before last is free again: a barrier lies between)
-            if (best != 0x7fffffff) { pr = best; break; }
-        }
-        if (pr == 0x7fffffff) continue;
-        const int inv = zp_inverse(F, img[pr * ld + c]);
-        // ---- factors, in place on column c
-        for (int i = tid; i < m; i += BS) {
-            if (i == pr) continue;
-            const int f = img[i * ld + c];
-            if (f != 0) img[i * ld + c] = zp_mul(F, f, inv);
-        }
-        __syncthreads();
-        if (tid == 0) {
-            rowflag[pr >> 5] |= 1u << (pr & 31);
-            pivrow[r] = pr;
-            pivcol[r] = c;
-            pinv[r] = inv;
-        }
-        // ---- update: row i -= factor * pivot row, on the columns right of c (the right-hand sides among them)
-        for (int i = ty; i < m; i += TY) {
-            if (i == pr) continue;
-            const int g = img[i * ld + c];
-            if (g == 0) continue;
-            for (int j = c + 1 + tx; j < W; j += TX) {
-                const int v = img[pr * ld + j];
-                if (v != 0) img[i * ld + j] = zp_axpy(F, -g, v, img[i * ld + j]);
-            }
-        }
-        __syncthreads();
-        r++;
-    }
+    const int r = batch_eliminate<BS, false>(F, L, ld, m, n, W, false, nullptr);
 
     // ---- one wave per right-hand side: the test down its column, then its row of X
-    const unsigned long long lt_mask = (1ull << lane) - 1ull;
     for (int t = wave; t < d.w; t += NW) {
         const int col = n + t;
         bool bad = false;
         for (int i0 = 0; i0 < m && !bad; i0 += 64) {
             const int i = i0 + lane;
-            const bool hit = i < m && !((rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + col] != 0;
+            const bool hit = i < m && !((L.rowflag[i >> 5] >> (i & 31)) & 1u) && img[i * ld + col] != 0;
             bad = __ballot(hit) != 0ull;
         }
         const i64d at = d.slice + (i64d)t * (r + 1);
@@ -156,13 +102,11 @@ __global__ __launch_bounds__(BS) void k_solve_elim(SolveBatchArgs a)
             const int k = k0 + lane;
             int v = 0, pc = 0;
             if (k < r) {
-                pc = pivcol[k];
-                const int x = img[pivrow[k] * ld + col];
-                if (x != 0) v = zp_mul(F, x, pinv[k]);
+                pc = L.pivcol[k];
+                const int x = img[L.pivrow[k] * ld + col];
+                if (x != 0) v = zp_mul(F, x, L.pinv[k]);
             }
-            const unsigned long long b = __ballot(v != 0);
-            if (v != 0) dst[count + __popcll(b & lt_mask)] = make_int2(pc, v);
-            count += __popcll(b);
+            batch_append(dst, count, pc, v);
         }
         if (lane == 0) {
             a.cnt[d.slot0 + t] = count;

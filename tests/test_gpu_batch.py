@@ -177,6 +177,67 @@ def test_rank_and_kernel_batches(S, sweep):
         assert [row[-1] for row in K.rows()] == [(f, -1) for f in free]  # ascending order of the free column
 
 
+def host_elected_rows(D, p):
+    """the rows in the order the election takes them: per column, left to right, the first row that is not a pivot yet and holds a
+    non-zero there once the pivots before it are eliminated (Gauss-Jordan without swaps, Python integers)"""
+    M = [[int(v) % p for v in row] for row in np.asarray(D, dtype=object)]
+    taken = []
+    for c in range(len(M[0]) if M else 0):
+        i = next((i for i in range(len(M)) if i not in taken and M[i][c]), None)
+        if i is None:
+            continue
+        inv = pow(M[i][c], -1, p)
+        for k in range(len(M)):
+            if k != i and M[k][c]:
+                f = M[k][c] * inv % p
+                M[k] = [(a - f * b) % p for a, b in zip(M[k], M[i])]
+        taken.append(i)
+    return taken
+
+
+def test_wide_matrices_end_their_qinv_with_minus_one(S):
+    """Every row is a pivot before the columns run out, so the elimination stops early and the columns left have no pivot: full row
+    rank at 1 x 33, 3 x 40, 2 x 65 (past a bitset word, past a wave) and 5 x 6, and a 4 x 40 of rank 2."""
+    rng = np.random.default_rng(3365)
+    mats, dense = [], []
+    for p in (65521, 127):
+        for (n, m) in ((1, 33), (3, 40), (2, 65), (5, 6)):
+            while True:
+                D = random_dense(rng, n, m, p, 0.7)
+                piv = host_rref(D, p)[1]
+                if len(piv) == n and piv[-1] < m - 1:
+                    break
+            dense.append((D, p))
+    D = random_dense(rng, 4, 40, 65521, 0.7)
+    D[1] = (3 * D[0]) % 65521
+    D[3] = (D[0] + 5 * D[2]) % 65521
+    assert len(host_rref(D, 65521)[1]) == 2 and host_rref(D, 65521)[1][-1] < 39
+    dense.append((D, 65521))
+    mats = [to_csr(S, D, p, rng) for D, p in dense]
+    facts = S.echelonize_batch(mats)
+    st = S.batch_stats()
+    assert st["lds_path"] == len(mats) and st["general_path"] == 0
+    ranks = S.rank_batch(mats)
+    Ks = S.kernel_batch(mats)
+    for A, (D, p), fact, rank, K in zip(mats, dense, facts, ranks, Ks):
+        where = f"{A.n} x {A.m} mod {p}"
+        R, piv = host_rref(D, p)
+        r = len(piv)
+        assert fact.r == rank == r, where
+        want_qinv = [-1] * A.m
+        for k, c in enumerate(piv):
+            want_qinv[c] = k
+        assert np.asarray(fact.qinv).tolist() == want_qinv and want_qinv[-1] == -1, where
+        elected = host_elected_rows(D, p)
+        pp = np.ctypeslib.as_array(fact.data.contents.p, (max(A.n, A.m, 1),))
+        assert pp[: A.n].tolist() == elected + [i for i in range(A.n) if i not in elected], where
+        want = balanced_rows(R, p)
+        assert fact.U.rows() == want, where
+        free = [f for f in range(A.m) if f not in piv]
+        assert K.shape == (A.m - r, A.m), where
+        assert K.rows() == [[(piv[k], v) for k in range(r) for (j, v) in want[k] if j == f] + [(f, -1)] for f in free], where
+
+
 def test_mixed_batch_takes_the_general_path_where_it_must(S, sweep):
     mats, dense = sweep
     rng = np.random.default_rng(5)

@@ -333,6 +333,31 @@ def test_slabs_do_not_show_in_the_result(S):
     assert raw(X2[0]) == raw(X[0]) and ok2[0].tolist() == ok[0].tolist()
 
 
+def test_small_scratch_budget_solves_in_chunks(S, monkeypatch):
+    """60 systems of 20 x 20 with 8 right-hand sides, every third one singular: a job needs about 2.9 KB of the chunk's buffers, so a
+    budget of 0.05 MB cuts the call into three chunks or more, and nothing of that may show in the result."""
+    p, n, K = 65521, 20, 8
+    rng = np.random.default_rng(60)
+    sys = [random_system(rng, n, n, K, p, 0.5, planted=t % 3 == 0) for t in range(60)]
+    unsolved = sum(int((~host_solve(A, B, p)[1]).sum()) for A, B, _ in sys)
+    assert 0 < unsolved < 60 * K // 2
+    As = [make_csr(S, A, p, rng) for A, _, _ in sys]
+    Bs = [make_csr(S, B, p, rng) for _, B, _ in sys]
+    X, ok = S.solve_batch(As, Bs)
+    whole = S.solve_stats()
+    assert whole["lds_path"] == 60 and whole["unsolved"] == unsolved
+    monkeypatch.setenv("SPASM_AMD_BATCH_SCRATCH_MB", "0.05")
+    Xc, okc = S.solve_batch(As, Bs)
+    cut = S.solve_stats()
+    print("solve_stats", whole, cut)
+    assert [raw(x) for x in Xc] == [raw(x) for x in X] and [o.tolist() for o in okc] == [o.tolist() for o in ok]
+    assert cut["jobs"] == whole["jobs"] and cut["entries"] == whole["entries"]
+    assert cut["launches"] > whole["launches"]  # every chunk costs an elimination and a scan at the least
+    monkeypatch.delenv("SPASM_AMD_BATCH_SCRATCH_MB")
+    S.solve_batch(As[:3], Bs[:3])
+    assert S.solve_stats()["launches"] == whole["launches"]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # 5. a mixed batch
 # ---------------------------------------------------------------------------------------------------------------------------------
