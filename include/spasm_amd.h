@@ -643,6 +643,50 @@ int spasm_amd_solve_batch(int count, const struct spasm_csr *const *A, const str
 int spasm_amd_blocks_solve(spasm_amd_blocks *Bk, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok);
 void spasm_amd_solve_stats(i64 *out);   /* of the last solve call of this thread */
 
+/* ---- Engine extension: X * A = B with A factored once (csrc/solver.hpp) ----
+ * spasm_amd_solve_batch and spasm_amd_blocks_solve eliminate A on every call.  A solver handle eliminates every system once and
+ * keeps, per system of the LDS path, an operator of m * rank words on the device; an apply only multiplies the entries of a
+ * right-hand side on the pivot columns of A into it.  Create once, apply many times (like spasm_amd_spmv_* / spasm_amd_trsolve_*).
+ *   create        `count` systems A[i] (n_i x m_i; shapes and primes may differ).  The matrices may be dropped afterwards.
+ *   create_blocks one system per block of the split, built from the handle's resident concatenated CSR (only a block over the limit
+ *                 is fetched).  The solver copies the maps it needs: the blocks handle may be freed afterwards.
+ *   apply         B[i] is K_i x m_i over the prime of A[i]; X[i] (K_i x n_i, free it with spasm_csr_free) and ok[i] (K_i bytes) as
+ *                 for spasm_amd_solve_batch.  The input, output, ok, shape and error rules of spasm_amd_solve_batch apply word for
+ *                 word, and for every system of the LDS path (m * (n + 1) <= 32768) apply returns BYTE FOR BYTE what
+ *                 spasm_amd_solve_batch returns for the same (A, B): the unique solution that is zero outside the CANONICAL ROW BASIS
+ *                 of A[i], an empty row where ok = 0.  Two applies of the same input are byte-identical, and an apply leaves the
+ *                 handle as it was.
+ *   apply_blocks  Rhs, X and ok as for spasm_amd_blocks_solve, whose rules apply word for word; returns BYTE FOR BYTE what
+ *                 spasm_amd_blocks_solve returns whenever no block that meets Rhs is over the limit.
+ *   general path  a system over the limit keeps its factorization with L (spasm_echelonize, once, at create); apply runs spasm_gesv
+ *                 on it.  X * A == B and ok as on the LDS path, but the canonical-basis guarantee DOES NOT HOLD there.
+ *   shapes        n = 0, m = 0 and rank 0 need no launch at create, and none at apply beyond the test that the row of B vanishes.
+ *   info          out[8] = systems, systems on the LDS path (empty shapes included), systems on the general path, operator words
+ *                 (sum of m * rank over the LDS path; the buffer has room for min(n, m) columns per system), sum of the ranks,
+ *                 factor jobs (system-slab workgroups of create), kernel launches of create, device microseconds of create (HIP
+ *                 events).
+ *   ranks         rank[i] = rank of system i (count words)
+ *   basis         rows[0 .. r) = the canonical row basis of system i, ascending: the rows of A[i] every solution lives on.  rows has
+ *                 room for n_i ints; returns r, -1 on error.  For a system of the general path these are that factorization's
+ *                 pivotal rows, ascending, NOT the canonical basis.
+ *   stats         of the last apply of this thread, in the layout of spasm_amd_solve_stats
+ *   use           one apply at a time per handle; a handle belongs to the device it was created on
+ *   errors        as for spasm_amd_solve_batch / spasm_amd_blocks_solve (the prime and m of B[i] are checked against A[i]'s), and:
+ *                 a NULL handle; apply on a handle made by create_blocks, apply_blocks on one made by create; a system index out of
+ *                 range.  create returns NULL, the others -1; NO output slot is written; spasm_amd_last_error() names the function,
+ *                 the cause and the index of the matrix; the handle stays usable.  count == 0 succeeds at create and at apply (and
+ *                 needs no device).  spasm_amd_solver_free(NULL) is harmless. */
+typedef struct spasm_amd_solver spasm_amd_solver;
+spasm_amd_solver *spasm_amd_solver_create(int count, const struct spasm_csr *const *A);
+spasm_amd_solver *spasm_amd_solver_create_blocks(const spasm_amd_blocks *Bk);
+int spasm_amd_solver_apply(spasm_amd_solver *S, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok);
+int spasm_amd_solver_apply_blocks(spasm_amd_solver *S, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok);
+void spasm_amd_solver_info(const spasm_amd_solver *S, i64 *out);
+int spasm_amd_solver_ranks(const spasm_amd_solver *S, i64 *rank);
+int spasm_amd_solver_basis(const spasm_amd_solver *S, int i, int *rows);
+void spasm_amd_solver_stats(i64 *out);   /* of the last apply of this thread */
+void spasm_amd_solver_free(spasm_amd_solver *S);
+
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 

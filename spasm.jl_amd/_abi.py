@@ -286,6 +286,15 @@ SIGNATURES = {
     "spasm_amd_solve_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(_P(CsrStruct)), _P(_P(CsrStruct)), _P(_P(C.c_ubyte))]),
     "spasm_amd_blocks_solve": (C.c_int32, [C.c_void_p, _P(CsrStruct), _P(_P(CsrStruct)), _P(C.c_ubyte)]),
     "spasm_amd_solve_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_solver_create": (C.c_void_p, [C.c_int32, _P(_P(CsrStruct))]),
+    "spasm_amd_solver_create_blocks": (C.c_void_p, [C.c_void_p]),
+    "spasm_amd_solver_apply": (C.c_int32, [C.c_void_p, _P(_P(CsrStruct)), _P(_P(CsrStruct)), _P(_P(C.c_ubyte))]),
+    "spasm_amd_solver_apply_blocks": (C.c_int32, [C.c_void_p, _P(CsrStruct), _P(_P(CsrStruct)), _P(C.c_ubyte)]),
+    "spasm_amd_solver_info": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_solver_ranks": (C.c_int32, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_solver_basis": (C.c_int32, [C.c_void_p, C.c_int32, _P(C.c_int32)]),
+    "spasm_amd_solver_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_solver_free": (None, [C.c_void_p]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

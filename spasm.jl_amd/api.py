@@ -1285,6 +1285,11 @@ class DeviceBlocks:
             raise SpasmError(_abi.last_error() or "spasm_amd_blocks_solve failed")
         return CSR(out), ok[: B.n].astype(np.bool_)
 
+    def solver(self):
+        """A BatchSolver of all blocks (spasm_amd_solver_create_blocks): the blocks are factored once, from the device, and
+        solver.solve(B) returns what solve(B) returns without eliminating them again.  It outlives this handle."""
+        return BatchSolver.from_blocks(self)
+
 
 # ---------------------------------------------------------------------------------------------
 # X * A = B for many small matrices, and block by block  (spasm_amd_solve_batch / _blocks_solve; csrc/solve_batch.hpp)
@@ -1320,6 +1325,143 @@ def solve_stats():
     """Counters of the last solve_batch / DeviceBlocks.solve call of this thread (spasm_amd_solve_stats), keyed by SOLVE_STATS."""
     out = (C.c_int64 * 8)()
     _abi.lib().spasm_amd_solve_stats(out)
+    return {k: int(v) for k, v in zip(SOLVE_STATS, out)}
+
+
+# ---------------------------------------------------------------------------------------------
+# X * A = B with A factored once  (spasm_amd_solver_*; csrc/solver.hpp)
+# ---------------------------------------------------------------------------------------------
+SOLVER_INFO = ("systems", "lds_path", "general_path", "operator_words", "rank_sum", "factor_jobs", "create_launches", "create_us")
+
+
+class BatchSolver:
+    """The systems A[i] factored once and resident on the device for repeated solves X[i] * A[i] = B[i] (spasm_amd_solver_*; engine
+    extension).  BatchSolver(mats) takes a list of CSR, which may be dropped afterwards; BatchSolver.from_blocks(device_blocks) (or
+    DeviceBlocks.solver()) takes the blocks of a split matrix, and the DeviceBlocks may be closed afterwards.
+
+    solve(rhs) -> (X, ok): for a solver made from a list, rhs is a list with one CSR per system and the result is what
+    solve_batch(mats, rhs) returns, byte for byte on the LDS path; for one made from blocks, rhs is one CSR and the result is what
+    DeviceBlocks.solve(rhs) returns.  One solve at a time per solver."""
+
+    def __init__(self, mats):
+        mats = list(mats)
+        for M in mats:
+            if not isinstance(M, CSR):
+                raise TypeError("a list of CSR expected")
+        cnt = len(mats)
+        arr = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))(*[A.data for A in mats])
+        with _quiet(True):
+            self._h = _abi.lib().spasm_amd_solver_create(cnt, arr)
+        if not self._h:
+            raise SpasmError(_abi.last_error() or "spasm_amd_solver_create failed")
+        self._blocks = False
+        self._count = cnt
+        self.shapes = [A.shape for A in mats]
+        self.primes = [A.prime for A in mats]
+
+    @classmethod
+    def from_blocks(cls, device_blocks):
+        """The solver of all blocks of a DeviceBlocks, built from the blocks on the device"""
+        if not isinstance(device_blocks, DeviceBlocks):
+            raise TypeError("a DeviceBlocks expected")
+        self = cls.__new__(cls)
+        with _quiet(True):
+            self._h = _abi.lib().spasm_amd_solver_create_blocks(device_blocks._need())
+        if not self._h:
+            raise SpasmError(_abi.last_error() or "spasm_amd_solver_create_blocks failed")
+        self._blocks = True
+        self._count = len(device_blocks)
+        self.shape = device_blocks.shape
+        self.prime = device_blocks.prime
+        return self
+
+    def _need(self):
+        if not getattr(self, "_h", None):
+            raise SpasmError("the solver is closed")
+        return self._h
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _abi.lib().spasm_amd_solver_free(h)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __len__(self):
+        return self._count
+
+    def info(self):
+        out = (C.c_int64 * 8)()
+        _abi.lib().spasm_amd_solver_info(self._need(), out)
+        return {k: int(v) for k, v in zip(SOLVER_INFO, out)}
+
+    @property
+    def ranks(self):
+        """[rank of system i, ...]"""
+        out = (C.c_int64 * max(self._count, 1))()
+        if _abi.lib().spasm_amd_solver_ranks(self._need(), out) != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_solver_ranks failed")
+        return [int(out[i]) for i in range(self._count)]
+
+    def basis(self, i):
+        """The rows of system i its solutions live on, ascending (int32 array): the canonical row basis on the LDS path, the
+        factorization's pivotal rows on the general path."""
+        i = int(i)
+        if not 0 <= i < self._count:
+            raise IndexError("system index out of range")
+        h = self._need()
+        n = self.shape[0] if self._blocks else self.shapes[i][0]
+        rows = np.zeros(max(n, 1), dtype=np.int32)
+        r = _abi.lib().spasm_amd_solver_basis(h, i, rows.ctypes.data_as(C.POINTER(C.c_int32)))
+        if r < 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_solver_basis failed")
+        return rows[:r].copy()
+
+    def solve(self, rhs, verbose=False):
+        h = self._need()
+        if self._blocks:
+            if not isinstance(rhs, CSR):
+                raise TypeError("a CSR expected")
+            out = C.POINTER(_abi.CsrStruct)()
+            ok = np.zeros(max(rhs.n, 1), dtype=np.uint8)
+            with _quiet(not verbose):
+                rc = _abi.lib().spasm_amd_solver_apply_blocks(h, rhs.data, C.byref(out), ok.ctypes.data_as(C.POINTER(C.c_ubyte)))
+            if rc != 0:
+                raise SpasmError(_abi.last_error() or "spasm_amd_solver_apply_blocks failed")
+            return CSR(out), ok[: rhs.n].astype(np.bool_)
+        rhs = list(rhs)
+        for M in rhs:
+            if not isinstance(M, CSR):
+                raise TypeError("a list of CSR expected")
+        if len(rhs) != self._count:
+            raise ValueError("as many right-hand sides as systems expected")
+        cnt = self._count
+        brr = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))(*[B.data for B in rhs])
+        out = (C.POINTER(_abi.CsrStruct) * max(cnt, 1))()
+        oks = [np.zeros(max(B.n, 1), dtype=np.uint8) for B in rhs]
+        okp = (C.POINTER(C.c_ubyte) * max(cnt, 1))(*[o.ctypes.data_as(C.POINTER(C.c_ubyte)) for o in oks])
+        with _quiet(not verbose):
+            rc = _abi.lib().spasm_amd_solver_apply(h, brr, out, okp)
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_solver_apply failed")
+        return [CSR(out[i]) for i in range(cnt)], [o[: B.n].astype(np.bool_) for o, B in zip(oks, rhs)]
+
+
+def solver_stats():
+    """Counters of the last BatchSolver.solve call of this thread (spasm_amd_solver_stats), keyed by SOLVE_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_solver_stats(out)
     return {k: int(v) for k, v in zip(SOLVE_STATS, out)}
 
 

@@ -192,6 +192,14 @@ def solve(block, B):
     return X, ok
 
 
+def solver(block):
+    """The resident solver of a split matrix: api.BatchSolver.from_blocks for a DeviceBlocks (the blocks are factored once, on the
+    device; solver.solve(B) then returns what solve(block, B) returns without eliminating them again)."""
+    if not isinstance(block, api.DeviceBlocks):
+        raise TypeError("a DeviceBlocks expected: the blocks of a resident solver live on the device")
+    return block.solver()
+
+
 def _kernel_block(ks, col2block, block2col):
     """the Block of per-block kernels: rows numbered block after block"""
     block2row, row2block, r = [], [], 0

@@ -16,6 +16,7 @@
 #include "batch.hpp"
 #include "blocks.hpp"
 #include "solve_batch.hpp"
+#include "solver.hpp"
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -7370,22 +7371,17 @@ void solve_jobs(const std::vector<SolveSys> &sys, std::vector<SolveDesc> &desc, 
     }
 }
 
-// The LDS path of spasm_amd_solve_batch from the systems on: h_cnt / h_ok per slot, h_ent the rows of X back to back in slot order.
-void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged &A, const BatchStaged &B, std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok,
-                std::vector<int2> &h_ent)
+// The chunks of a list of jobs (Desc carries slot0, slice, w; Args carries desc, cnt, src, ok, scratch), shared by solve_fast and the
+// resident solver: consecutive jobs whose scratch fits the budget (per job: scratch + packed entries, and per slot: count, its scan,
+// source, ok), slots and slices made relative to the chunk; per chunk the launches of `kern`, the scan, k_solve_pack and one
+// download.  h_cnt / h_ok per slot, h_ent the rows of X back to back in slot order; st[4 .. 6] are filled.
+template <class Desc, class Args>
+void solve_chunks(const ElimKernels<Args> &kern, std::vector<Desc> &desc, const std::vector<unsigned char> &cls, const std::vector<i64> &ecap, Args a, i64 nslots,
+                  std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok, std::vector<int2> &h_ent, i64 *st)
 {
-    i64 *st = g_solve_stats;
-    if (sys.empty()) return;
     hipStream_t s = nullptr;
     const size_t budget = batch_budget();
-    std::vector<SolveDesc> desc;
-    std::vector<unsigned char> cls;
-    std::vector<i64> ecap;
-    solve_jobs(sys, desc, cls, ecap);
     const int nj = (int)desc.size();
-    st[3] = nj;
-    // ---- chunks of consecutive jobs (per job: scratch + packed entries, and per slot: count, its scan, source, ok); slots and
-    // slices relative to the chunk
     const std::vector<int> cut = batch_cut(nj, budget, [&](int q) { return (size_t)ecap[(size_t)q] * 2 * sizeof(int2) + (size_t)desc[(size_t)q].w * (sizeof(int) + 2 * sizeof(i64d) + 1); });
     const int nchunks = (int)cut.size() - 1;
     std::vector<i64> c_slot0((size_t)nchunks), c_slots((size_t)nchunks), c_ents((size_t)nchunks);
@@ -7402,7 +7398,7 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged 
         c_slots[(size_t)c] = desc[(size_t)hi - 1].slot0 + desc[(size_t)hi - 1].w;
         c_ents[(size_t)c] = ents;
     }
-    DevBuf<SolveDesc> d_desc;
+    DevBuf<Desc> d_desc;
     DevBuf<int> d_items, d_cnt;
     DevBuf<i64d> d_src, rowstart;
     DevBuf<unsigned char> d_ok;
@@ -7410,13 +7406,9 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged 
     Scanner scan;
     d_desc.alloc((size_t)nj);
     d_items.alloc((size_t)nj);
-    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(Desc), hipMemcpyHostToDevice, s));
     std::vector<int> items((size_t)nj);
-    SolveBatchArgs a;
-    memset(&a, 0, sizeof a);
     a.desc = d_desc.p;
-    a.P = A.P; a.J = A.J; a.X = A.X;
-    a.BP = B.P; a.BJ = B.J; a.BX = B.X;
     SpgEvents ev;
     i64 launches = 0, entries = 0;
     double ms = 0;
@@ -7435,7 +7427,7 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged 
         a.ok = d_ok.p;
         a.scratch = scratch.p;
         HIPCHK(hipMemsetAsync(d_cnt.p + slots, 0, sizeof(int), s));
-        launches += batch_launch_jobs(kSolveElim, cls, lo, hi, items, d_items.p, a, ev.e[0], s);
+        launches += batch_launch_jobs(kern, cls, lo, hi, items, d_items.p, a, ev.e[0], s);
         const i64 total = batch_chunk_entries(d_cnt.p, slots, ents, rowstart, scan, s);
         launches++;
         if (total > 0) {
@@ -7460,16 +7452,33 @@ void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged 
     st[6] = entries;
 }
 
+// The LDS path of spasm_amd_solve_batch from the systems on: h_cnt / h_ok per slot, h_ent the rows of X back to back in slot order.
+void solve_fast(const std::vector<SolveSys> &sys, i64 nslots, const BatchStaged &A, const BatchStaged &B, std::vector<int> &h_cnt, std::vector<unsigned char> &h_ok,
+                std::vector<int2> &h_ent)
+{
+    i64 *st = g_solve_stats;
+    if (sys.empty()) return;
+    std::vector<SolveDesc> desc;
+    std::vector<unsigned char> cls;
+    std::vector<i64> ecap;
+    solve_jobs(sys, desc, cls, ecap);
+    st[3] = (i64)desc.size();
+    SolveBatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.P = A.P; a.J = A.J; a.X = A.X;
+    a.BP = B.P; a.BJ = B.J; a.BX = B.X;
+    solve_chunks(kSolveElim, desc, cls, ecap, a, nslots, h_cnt, h_ok, h_ent, st);
+}
+
 struct CsrList {
     std::vector<struct spasm_csr *> v;
     ~CsrList() { for (auto *x : v) spasm_csr_free(x); }
 };
 
-// One system through the general path: A echelonized with L, then do_gesv.  Rows without a solution are emptied; the others get
-// their columns in ascending order and lose their stored zeros.  ok[K].
-struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *B, unsigned char *ok)
+// One system through the general path from its factorization N (with L) on: do_gesv.  Rows without a solution are emptied; the
+// others get their columns in ascending order and lose their stored zeros.  n = the rows of A; ok[K].
+struct spasm_csr *solve_slow_with(const struct spasm_lu *N, int n, i64 prime, const struct spasm_csr *B, unsigned char *ok)
 {
-    const i64 prime = A->field->p;
     const ZpField F = zp_field_make(prime);
     const int K = B->n;
     // the right-hand side with reduced values
@@ -7478,11 +7487,6 @@ struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *
     std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Bguard(Bn, spasm_csr_free);
     for (int k = 0; k <= K; k++) Bn->p[k] = B->p[k];
     for (i64 e = 0; e < B->p[K]; e++) { Bn->j[e] = B->j[e]; Bn->x[e] = zp_reduce(F, (int64_t)B->x[e]); }
-    struct echelonize_opts o;
-    spasm_echelonize_init_opts(&o);
-    o.L = 1;
-    struct spasm_lu *N = do_echelonize(A, &o);
-    std::unique_ptr<struct spasm_lu, void (*)(struct spasm_lu *)> Nguard(N, spasm_lu_free);
     struct spasm_csr *Xs = do_gesv(N, Bn, ok);
     std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Xguard(Xs, spasm_csr_free);
     std::vector<std::pair<int, int>> row;
@@ -7490,7 +7494,7 @@ struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *
     for (int k = 0; k < K; k++)
         if (ok[k])
             for (i64 e = Xs->p[k]; e < Xs->p[k + 1]; e++) nz += Xs->x[e] != 0;
-    struct spasm_csr *X = spasm_csr_alloc(K, A->n, nz, prime, true);
+    struct spasm_csr *X = spasm_csr_alloc(K, n, nz, prime, true);
     if (!X) throw EngineError("out of host memory");
     i64 w = 0;
     for (int k = 0; k < K; k++) {
@@ -7504,6 +7508,23 @@ struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *
     }
     X->p[K] = w;
     return X;
+}
+
+// the factorization of the general path: A echelonized with L
+struct spasm_lu *solve_slow_factor(const struct spasm_csr *A)
+{
+    struct echelonize_opts o;
+    spasm_echelonize_init_opts(&o);
+    o.L = 1;
+    return do_echelonize(A, &o);
+}
+
+// One system through the general path: A echelonized with L, then solve_slow_with.
+struct spasm_csr *solve_slow(const struct spasm_csr *A, const struct spasm_csr *B, unsigned char *ok)
+{
+    struct spasm_lu *N = solve_slow_factor(A);
+    std::unique_ptr<struct spasm_lu, void (*)(struct spasm_lu *)> Nguard(N, spasm_lu_free);
+    return solve_slow_with(N, A->n, A->field->p, B, ok);
 }
 
 // Nothing is written to X / ok before all is done.
@@ -7601,6 +7622,82 @@ inline int solve_bits(i64 v)
     return bits;
 }
 
+// what solve_blocks_rows reads of a split: the maps on the device and the starts of the blocks on the host
+struct BlocksView {
+    int nb;
+    i64 prime;
+    const int *col_block, *col_pos, *block_rows;
+    const i64d *row_start;
+    const std::vector<i64> *h_row_start, *h_col_start;
+};
+
+// how the blocks that meet a right-hand side are solved
+struct BlocksSolveOps {
+    virtual ~BlocksSolveOps() {}
+    // does block b (rn x cn, rn > 0) take the LDS path?
+    virtual bool fits(int b, i64 rn, i64 cn) = 0;
+    // the jobs of the LDS-path blocks (sys[f] is block blk[f]; brow0 = slot0 = its first run): returns the words (int2) of entry
+    // scratch they need, slices laid out from 0, and their number
+    virtual i64 plan(const std::vector<SolveSys> &sys, const std::vector<int> &blk, int &njobs) = 0;
+    // a block over the limit against its runs Rb, on the general path
+    virtual struct spasm_csr *slow(int b, const struct spasm_csr *Rb, unsigned char *okb) = 0;
+    // the planned jobs: right-hand sides (run_start, sj, sx), outputs per run; returns the launches, with the stream drained
+    virtual i64 launch(const i64d *run_start, const int *sj, const int *sx, int *cnt, i64d *src, unsigned char *ok, int2 *scratch, hipStream_t s) = 0;
+};
+
+// spasm_amd_blocks_solve: every call eliminates the blocks it meets (k_solve_elim from the resident concatenated CSR)
+struct BlocksElimOps : BlocksSolveOps {
+    spasm_amd_blocks *B;
+    std::vector<SolveDesc> desc;
+    std::vector<unsigned char> cls;
+    explicit BlocksElimOps(spasm_amd_blocks *B_) : B(B_) {}
+    bool fits(int, i64 rn, i64 cn) override { return solve_fits(rn, cn); }
+    i64 plan(const std::vector<SolveSys> &sys, const std::vector<int> &, int &njobs) override
+    {
+        std::vector<i64> ecap;
+        desc.clear();
+        cls.clear();
+        solve_jobs(sys, desc, cls, ecap);
+        njobs = (int)desc.size();
+        i64 ents = 0;
+        for (int q = 0; q < njobs; q++) { desc[(size_t)q].slice = ents; ents += ecap[(size_t)q]; }
+        return ents;
+    }
+    struct spasm_csr *slow(int b, const struct spasm_csr *Rb, unsigned char *okb) override
+    {
+        struct spasm_csr *M = blocks_fetch(B, b);
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Mguard(M, spasm_csr_free);
+        return solve_slow(M, Rb, okb);
+    }
+    i64 launch(const i64d *run_start, const int *sj, const int *sx, int *cnt, i64d *src, unsigned char *ok, int2 *scratch, hipStream_t s) override
+    {
+        const int nj = (int)desc.size();
+        DevBuf<SolveDesc> d_desc;
+        DevBuf<int> d_items;
+        d_desc.alloc((size_t)nj);
+        d_items.alloc((size_t)nj);
+        HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
+        std::vector<int> items((size_t)nj);
+        SolveBatchArgs a;
+        memset(&a, 0, sizeof a);
+        a.desc = d_desc.p;
+        a.P = B->P.p; a.J = B->J.p; a.X = B->X.p;
+        a.BP = run_start; a.BJ = sj; a.BX = sx;
+        a.cnt = cnt;
+        a.src = src;
+        a.ok = ok;
+        a.scratch = scratch;
+        const i64 launches = batch_launch_jobs(kSolveElim, cls, 0, nj, items, d_items.p, a, nullptr, s);
+        HIPCHK(hipStreamSynchronize(s)); // (items and the buffers belong to this scope)
+        return launches;
+    }
+};
+
+inline BlocksView blocks_view(const spasm_amd_blocks *B)
+{
+    return BlocksView{B->nb, B->prime, B->col_block.p, B->col_pos.p, B->block_rows.p, B->row_start.p, &B->h_row_start, &B->h_col_start};
+}
+
 // Rows k0 .. k1 of Rhs (on the device as rp / rj / rx) against the blocks of the handle.  Appends to xp (row lengths become
 // pointers at the caller), xj, xx and writes ok[k0 .. k1).  The pipeline, every step on the device unless it says otherwise:
 //   keys      (block of the entry's column, row) per entry; a stable sort; the runs of equal keys = the right-hand sides of the blocks
@@ -7609,14 +7706,15 @@ inline int solve_bits(i64 v)
 //   solve     k_solve_elim from the resident concatenated CSR; a run of a block without rows is solvable iff it vanishes
 //   assemble  the runs by row (a second stable sort), ok[k] = AND over the runs of row k, the entries of the solvable rows as
 //             (row, row of A) keys through block_rows, one sort, row pointers by bisection, one download
-void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, const i64 *h_rp, const int *rj, const int *rx, std::vector<i64> &xlen,
-                       std::vector<int> &xj, std::vector<int> &xx, unsigned char *ok)
+// The maps of the split come as a BlocksView and the solve of the blocks as a BlocksSolveOps, so that the resident solver, which
+// holds copies of the maps and its own operators, runs the same pipeline.
+void solve_blocks_rows(const BlocksView &B, BlocksSolveOps &ops, i64 *st, int k0, int k1, const i64d *rp, const i64 *h_rp, const int *rj, const int *rx,
+                       std::vector<i64> &xlen, std::vector<int> &xj, std::vector<int> &xx, unsigned char *ok)
 {
-    i64 *st = g_solve_stats;
     hipStream_t s = nullptr;
-    const int K = k1 - k0, nb = B->nb;
+    const int K = k1 - k0, nb = B.nb;
     const i64 e0 = h_rp[k0], ne = h_rp[k1] - e0;
-    const ZpField F = zp_field_make(B->prime);
+    const ZpField F = zp_field_make(B.prime);
     if (ne == 0) {
         for (int k = 0; k < K; k++) { ok[k0 + k] = 1; xlen[(size_t)(k0 + k)] = 0; }
         return;
@@ -7635,7 +7733,7 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     sx.alloc((size_t)ne);
     SpgEvents ev;
     HIPCHK(hipEventRecord(ev.e[0], s));
-    hipLaunchKernelGGL(k_sv_keys, dim3(cdiv(ne, 256)), dim3(256), 0, s, K, (i64d)e0, (i64d)ne, rp + k0, rj, (const int *)B->col_block.p, key.p, val.p);
+    hipLaunchKernelGGL(k_sv_keys, dim3(cdiv(ne, 256)), dim3(256), 0, s, K, (i64d)e0, (i64d)ne, rp + k0, rj, B.col_block, key.p, val.p);
     HIPCHK(hipGetLastError());
     solve_sort(sort_tmp, key.p, skey.p, val.p, sval.p, ne, 32 + solve_bits(nb), s);
     hipLaunchKernelGGL(k_sv_heads, dim3(cdiv(ne + 1, 256)), dim3(256), 0, s, (i64d)ne, (const unsigned long long *)skey.p, head.p);
@@ -7657,9 +7755,9 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     d_ok.alloc((size_t)nruns);
     iota.alloc((size_t)nruns);
     hipLaunchKernelGGL(k_sv_runs, dim3(cdiv(ne + 1, 256)), dim3(256), 0, s, (i64d)e0, (i64d)ne, (const unsigned long long *)skey.p, (const int *)sval.p, (const int *)head.p,
-                       (const int *)runid.p, rj, rx, (const int *)B->col_pos.p, run_start.p, run_block.p, run_row.p, sj.p, sx.p);
+                       (const int *)runid.p, rj, rx, B.col_pos, run_start.p, run_block.p, run_row.p, sj.p, sx.p);
     hipLaunchKernelGGL(k_blk_starts, dim3(cdiv((i64)nb + 1, 256)), dim3(256), 0, s, nb, nruns, (const int *)run_block.p, brun.p);
-    hipLaunchKernelGGL(k_sv_init, dim3(cdiv(nruns, 256)), dim3(256), 0, s, nruns, F, (const i64d *)run_start.p, (const int *)run_block.p, (const i64d *)B->row_start.p,
+    hipLaunchKernelGGL(k_sv_init, dim3(cdiv(nruns, 256)), dim3(256), 0, s, nruns, F, (const i64d *)run_start.p, (const int *)run_block.p, B.row_start,
                        (const int *)sx.p, d_cnt.p, d_src.p, d_ok.p, iota.p);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(ev.e[1], s));
@@ -7668,29 +7766,25 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     HIPCHK(hipStreamSynchronize(s));
     // ---- plan (host: one step per block)
     std::vector<SolveSys> sys;
-    std::vector<int> slow;
+    std::vector<int> sysb, slow;
     for (int b = 0; b < nb; b++) {
         const i64 Kb = h_brun[(size_t)b + 1] - h_brun[(size_t)b];
         if (Kb == 0) continue;
-        const i64 rn = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], cn = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+        const i64 rn = (*B.h_row_start)[(size_t)b + 1] - (*B.h_row_start)[(size_t)b], cn = (*B.h_col_start)[(size_t)b + 1] - (*B.h_col_start)[(size_t)b];
         st[0]++;
         if (rn == 0) st[1]++;
-        else if (solve_fits(rn, cn)) {
+        else if (ops.fits(b, rn, cn)) {
             st[1]++;
-            sys.push_back(SolveSys{(int)rn, (int)cn, (int)Kb, B->h_row_start[(size_t)b] + b, h_brun[(size_t)b], h_brun[(size_t)b], B->prime});
+            sys.push_back(SolveSys{(int)rn, (int)cn, (int)Kb, (*B.h_row_start)[(size_t)b] + b, h_brun[(size_t)b], h_brun[(size_t)b], B.prime});
+            sysb.push_back(b);
         } else {
             st[2]++;
             slow.push_back(b);
         }
     }
-    std::vector<SolveDesc> desc;
-    std::vector<unsigned char> cls;
-    std::vector<i64> ecap;
-    solve_jobs(sys, desc, cls, ecap);
-    const int nj = (int)desc.size();
+    int nj = 0;
+    const i64 ents = ops.plan(sys, sysb, nj);
     st[3] += nj;
-    i64 ents = 0;
-    for (int q = 0; q < nj; q++) { desc[(size_t)q].slice = ents; ents += ecap[(size_t)q]; }
     // ---- the blocks over the limit, on the host; their rows of X go behind the slices
     std::vector<int2> slow_ent;
     std::vector<int> slow_cnt;
@@ -7698,12 +7792,11 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     std::vector<unsigned char> slow_ok;
     for (int b : slow) {
         const i64 q0 = h_brun[(size_t)b], Kb = h_brun[(size_t)b + 1] - q0;
-        struct spasm_csr *M = blocks_fetch(B, b);
-        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Mguard(M, spasm_csr_free);
+        const int cn = (int)((*B.h_col_start)[(size_t)b + 1] - (*B.h_col_start)[(size_t)b]);
         std::vector<i64> rs((size_t)Kb + 1);
         HIPCHK(hipMemcpy(rs.data(), run_start.p + q0, ((size_t)Kb + 1) * sizeof(i64d), hipMemcpyDeviceToHost));
         const i64 z0 = rs[0], z = rs[(size_t)Kb] - z0;
-        struct spasm_csr *Rb = spasm_csr_alloc((int)Kb, M->m, z, B->prime, true);
+        struct spasm_csr *Rb = spasm_csr_alloc((int)Kb, cn, z, B.prime, true);
         if (!Rb) throw EngineError("out of host memory");
         std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Rguard(Rb, spasm_csr_free);
         for (i64 t = 0; t <= Kb; t++) Rb->p[t] = rs[(size_t)t] - z0;
@@ -7712,7 +7805,7 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
             HIPCHK(hipMemcpy(Rb->x, sx.p + z0, (size_t)z * sizeof(int), hipMemcpyDeviceToHost));
         }
         std::vector<unsigned char> okb((size_t)Kb, 0);
-        struct spasm_csr *Xb = solve_slow(M, Rb, okb.data());
+        struct spasm_csr *Xb = ops.slow(b, Rb, okb.data());
         std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Xguard(Xb, spasm_csr_free);
         for (i64 t = 0; t < Kb; t++) {
             slow_run.push_back(q0 + t);
@@ -7732,26 +7825,8 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     }
     // ---- solve
     i64 launches = 0;
-    DevBuf<SolveDesc> d_desc;
-    DevBuf<int> d_items;
     HIPCHK(hipEventRecord(ev.e[2], s));
-    if (nj > 0) {
-        d_desc.alloc((size_t)nj);
-        d_items.alloc((size_t)nj);
-        HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolveDesc), hipMemcpyHostToDevice, s));
-        std::vector<int> items((size_t)nj);
-        SolveBatchArgs a;
-        memset(&a, 0, sizeof a);
-        a.desc = d_desc.p;
-        a.P = B->P.p; a.J = B->J.p; a.X = B->X.p;
-        a.BP = run_start.p; a.BJ = sj.p; a.BX = sx.p;
-        a.cnt = d_cnt.p;
-        a.src = d_src.p;
-        a.ok = d_ok.p;
-        a.scratch = scratch.p;
-        launches += batch_launch_jobs(kSolveElim, cls, 0, nj, items, d_items.p, a, nullptr, s);
-        HIPCHK(hipStreamSynchronize(s)); // (items and desc are host vectors of this scope)
-    }
+    if (nj > 0) launches += ops.launch(run_start.p, sj.p, sx.p, d_cnt.p, d_src.p, d_ok.p, scratch.p, s);
     // ---- assemble
     byrow.alloc((size_t)nruns);
     krow.alloc((size_t)nruns);
@@ -7785,7 +7860,7 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     outj.alloc((size_t)total);
     if (total > 0) {
         hipLaunchKernelGGL(k_sv_emit, dim3((unsigned)nruns), dim3(64), 0, s, (const int *)len.p, (const i64d *)off.p, (const i64d *)d_src.p, (const int *)run_block.p,
-                           (const int *)run_row.p, (const i64d *)B->row_start.p, (const int *)B->block_rows.p, (const int2 *)scratch.p, xkey.p, xval.p);
+                           (const int *)run_row.p, B.row_start, B.block_rows, (const int2 *)scratch.p, xkey.p, xval.p);
         HIPCHK(hipGetLastError());
         solve_sort(sort_tmp, xkey.p, xskey.p, xval.p, xsval.p, total, 32 + solve_bits(K), s);
     }
@@ -7806,17 +7881,17 @@ void solve_blocks_rows(spasm_amd_blocks *B, int k0, int k1, const i64d *rp, cons
     st[6] += total;
 }
 
-void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+// Rhs against the split (n x m, on device dev) that V views: the checks of Rhs, its upload, the rows in chunks, X and ok.
+void solve_blocks_apply(const BlocksView &V, int n, int m, int dev, BlocksSolveOps &ops, i64 *st, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
 {
-    memset(g_solve_stats, 0, sizeof g_solve_stats);
-    blocks_need(B);
+    const std::vector<i64> &h_row_start = *V.h_row_start, &h_col_start = *V.h_col_start;
     if (!Rhs) throw EngineError("NULL matrix");
-    if (Rhs->m != B->m) throw EngineError("Rhs->m differs from the columns of the handle's matrix");
-    if (Rhs->field->p != B->prime) throw EngineError("the prime of Rhs differs from the handle's");
+    if (Rhs->m != m) throw EngineError("Rhs->m differs from the columns of the handle's matrix");
+    if (Rhs->field->p != V.prime) throw EngineError("the prime of Rhs differs from the handle's");
     const char *bad = batch_check(Rhs);
     if (bad) throw EngineError(bad);
     if (!X || (Rhs->n > 0 && !ok)) throw EngineError("NULL array");
-    HIPCHK(hipSetDevice(B->dev));
+    HIPCHK(hipSetDevice(dev));
     hipStream_t s = nullptr;
     const int K = Rhs->n;
     const i64 nnz = Rhs->p[K];
@@ -7837,8 +7912,8 @@ void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct s
         // chunks of rows: an entry of Rhs opens at most one run, a run holds at most min(rows, cols) + 1 entries of its block, and
         // every such entry is held about five times on the way (scratch, key and value twice, column)
         i64 rmax = 1;
-        for (int b = 0; b < B->nb; b++)
-            rmax = std::max(rmax, std::min(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]) + 1);
+        for (int b = 0; b < V.nb; b++)
+            rmax = std::max(rmax, std::min(h_row_start[(size_t)b + 1] - h_row_start[(size_t)b], h_col_start[(size_t)b + 1] - h_col_start[(size_t)b]) + 1);
         const double per = 64.0 + 48.0 * (double)rmax;
         const i64 cap = std::min<i64>((i64)std::max(1.0, (double)batch_budget() / per), ((i64)1 << 31) - 2);
         int k0 = 0;
@@ -7846,11 +7921,11 @@ void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct s
             int k1 = k0 + 1;
             while (k1 < K && Rhs->p[k1 + 1] - Rhs->p[k0] <= cap) k1++;
             if (Rhs->p[k1] - Rhs->p[k0] > ((i64)1 << 31) - 2) throw EngineError("a row of Rhs holds 2^31 entries or more");
-            solve_blocks_rows(B, k0, k1, rp.p, Rhs->p, rj.p, rx.p, xlen, xj, xx, hok.data());
+            solve_blocks_rows(V, ops, st, k0, k1, rp.p, Rhs->p, rj.p, rx.p, xlen, xj, xx, hok.data());
             k0 = k1;
         }
     }
-    struct spasm_csr *R = spasm_csr_alloc(K, B->n, (i64)xj.size(), B->prime, true);
+    struct spasm_csr *R = spasm_csr_alloc(K, n, (i64)xj.size(), V.prime, true);
     if (!R) throw EngineError("out of host memory");
     R->p[0] = 0;
     for (int k = 0; k < K; k++) R->p[k + 1] = R->p[k] + xlen[(size_t)k];
@@ -7859,9 +7934,457 @@ void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct s
         memcpy(R->j, xj.data(), xj.size() * sizeof(int));
         memcpy(R->x, xx.data(), xx.size() * sizeof(int));
     }
-    for (int k = 0; k < K; k++) g_solve_stats[7] += hok[(size_t)k] ? 0 : 1;
+    for (int k = 0; k < K; k++) st[7] += hok[(size_t)k] ? 0 : 1;
     if (K > 0) memcpy(ok, hok.data(), (size_t)K);
     *X = R;
+}
+
+void solve_blocks_run(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+{
+    memset(g_solve_stats, 0, sizeof g_solve_stats);
+    blocks_need(B);
+    BlocksElimOps ops(B);
+    solve_blocks_apply(blocks_view(B), B->n, B->m, B->dev, ops, g_solve_stats, Rhs, X, ok);
+}
+
+} // namespace
+
+// ------------------------------------------------------------------------------------------------
+// X * A = B with A factored once (solver.hpp): spasm_amd_solver_*.  create eliminates every system of the LDS path once (one
+// workgroup of k_solver_factor per slab of identity columns) and keeps the operators G, the pivots and the ranks on the device;
+// a system over the limit keeps its factorization with L.  apply is solve_batch with k_solver_apply in place of k_solve_elim, on
+// the same chunk driver (solve_chunks), and apply_blocks is blocks_solve on the same pipeline (solve_blocks_rows).
+// ------------------------------------------------------------------------------------------------
+enum { SOLVER_LDS = 0, SOLVER_GENERAL = 1, SOLVER_EMPTY = 2 };
+
+struct SolverSys {
+    int n = 0, m = 0, kind = SOLVER_EMPTY, r = 0;
+    i64 prime = 0;
+    i64 goff = 0, pivoff = 0;        // SOLVER_LDS: its operator (room for min(n, m) columns of m words) and its pivots
+    int ldg = 1, cls = 0, q = 1;     // LDS layout of an apply job (solver_shape)
+    struct spasm_lu *lu = nullptr;   // SOLVER_GENERAL
+    std::vector<int> basis;          // the rows of A the solutions live on, ascending
+};
+
+struct spasm_amd_solver {
+    int dev = 0;
+    bool blocks = false;
+    std::vector<SolverSys> sys;
+    DevBuf<int> G, pivrow, pivcol;
+    i64 info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // a handle made from a split: system b = block b, and copies of the maps the assembly reads
+    int n = 0, m = 0, nb = 0;
+    i64 prime = 0;
+    DevBuf<int> col_block, col_pos, block_rows;
+    DevBuf<i64d> row_start;
+    std::vector<i64> h_row_start, h_col_start;
+    ~spasm_amd_solver()
+    {
+        for (SolverSys &Y : sys) spasm_lu_free(Y.lu);
+    }
+};
+
+namespace {
+
+thread_local i64 g_solver_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+const ElimKernels<SolverFactorArgs> kSolverFactor = {{k_solver_factor<64>, k_solver_factor<128>, k_solver_factor<256>, k_solver_factor<512>}};
+const ElimKernels<SolverApplyArgs> kSolverApply = {{k_solver_apply<64>, k_solver_apply<128>, k_solver_apply<256>, k_solver_apply<512>}};
+
+// rounds of q right-hand sides a job of k_solver_apply works through: what staging G once is spread over
+constexpr int kSolverRounds = 8;
+
+// Class, stride and right-hand sides in flight of an operator of m x r words (solver.hpp, "Row stride").  The smallest class that
+// holds G and one vector of m + r words; q = the vectors that fit beside G, at most one per group of whole waves that covers m.
+void solver_shape(int m, int r, int &cls, int &ldg, int &q)
+{
+    ldg = std::max(r, 1);
+    if (ldg % 2 == 0 && (i64)m * (ldg + 1) + m + r <= kBatchClass[BATCH_NCLASS - 1].cap) ldg++;
+    const i64 need = (i64)m * ldg + m + r;
+    int c = 0;
+    while (c < BATCH_NCLASS - 1 && need > kBatchClass[c].cap) c++;
+    if (need > kBatchClass[c].cap) throw EngineError("internal error: an operator does not fit the largest class");
+    const int mp = (m + 63) & ~63, bs = kBatchClass[c].bs;
+    const i64 room = (kBatchClass[c].cap - (i64)m * ldg) / (m + r);
+    q = mp <= bs ? (int)std::min<i64>(bs / mp, room) : 1;
+    cls = c;
+}
+
+// The operators of the LDS-path systems list[f] (places in S->sys; n, m > 0) from the concatenated CSR on the device; row0[f] =
+// where the n + 1 row pointers of list[f] start in P.  Adds to info[5 .. 7].
+void solver_factor(spasm_amd_solver *S, const std::vector<int> &list, const std::vector<i64> &row0, const i64d *dP, const int *dJ, const int *dX)
+{
+    const int nf = (int)list.size();
+    if (nf == 0) return;
+    hipStream_t s = nullptr;
+    i64 gwords = 0, pwords = 0;
+    for (int i : list) {
+        SolverSys &Y = S->sys[(size_t)i];
+        const i64 cap = std::min(Y.n, Y.m);
+        Y.goff = gwords;
+        Y.pivoff = pwords;
+        gwords += (i64)Y.m * cap;
+        pwords += cap;
+    }
+    S->G.alloc((size_t)gwords);
+    S->pivrow.alloc((size_t)pwords);
+    S->pivcol.alloc((size_t)pwords);
+    DevBuf<int> drank;
+    drank.alloc((size_t)nf);
+    // ---- jobs: one per slab of the m identity columns, by the rules of the right-hand sides (solve_shape)
+    std::vector<SolverFactorDesc> desc;
+    std::vector<unsigned char> cls;
+    for (int f = 0; f < nf; f++) {
+        const SolverSys &Y = S->sys[(size_t)list[(size_t)f]];
+        int c = 0, w = 0, ld = 0;
+        solve_shape(Y.n, Y.m, Y.m, c, w, ld);
+        for (int t0 = 0; t0 < Y.m; t0 += w) {
+            SolverFactorDesc d;
+            memset(&d, 0, sizeof d);
+            d.row0 = row0[(size_t)f];
+            d.goff = Y.goff;
+            d.pivoff = Y.pivoff;
+            d.sys = f;
+            d.n = Y.n;
+            d.m = Y.m;
+            d.ld = ld;
+            d.t0 = t0;
+            d.w = std::min(w, Y.m - t0);
+            d.F = zp_field_make(Y.prime);
+            desc.push_back(d);
+            cls.push_back((unsigned char)c);
+        }
+    }
+    const int nj = (int)desc.size();
+    DevBuf<SolverFactorDesc> d_desc;
+    DevBuf<int> d_items;
+    d_desc.alloc((size_t)nj);
+    d_items.alloc((size_t)nj);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolverFactorDesc), hipMemcpyHostToDevice, s));
+    std::vector<int> items((size_t)nj);
+    SolverFactorArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = d_desc.p;
+    a.P = dP; a.J = dJ; a.X = dX;
+    a.G = S->G.p;
+    a.pivrow = S->pivrow.p;
+    a.pivcol = S->pivcol.p;
+    a.rank = drank.p;
+    SpgEvents ev;
+    const i64 launches = batch_launch_jobs(kSolverFactor, cls, 0, nj, items, d_items.p, a, ev.e[0], s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> hrank((size_t)nf), hpivcol((size_t)std::max<i64>(pwords, 1));
+    HIPCHK(hipMemcpyAsync(hrank.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (pwords > 0) HIPCHK(hipMemcpyAsync(hpivcol.data(), S->pivcol.p, (size_t)pwords * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (int f = 0; f < nf; f++) {
+        SolverSys &Y = S->sys[(size_t)list[(size_t)f]];
+        const int r = hrank[(size_t)f];
+        if (r < 0 || r > std::min(Y.n, Y.m)) throw EngineError("internal error: rank outside its bounds");
+        Y.r = r;
+        Y.basis.assign(hpivcol.begin() + Y.pivoff, hpivcol.begin() + Y.pivoff + r);
+        for (int k = 0; k < r; k++)
+            if (Y.basis[(size_t)k] < 0 || Y.basis[(size_t)k] >= Y.n || (k > 0 && Y.basis[(size_t)k] <= Y.basis[(size_t)k - 1])) throw EngineError("internal error: the pivot columns do not ascend");
+        solver_shape(Y.m, r, Y.cls, Y.ldg, Y.q);
+    }
+    S->info[5] += nj;
+    S->info[6] += launches;
+    S->info[7] += (i64)(ev.ms(0, 1) * 1000.0);
+}
+
+// the general path of a system: its factorization with L, the pivotal rows of which carry the solutions
+void solver_factor_slow(SolverSys &Y, const struct spasm_csr *A)
+{
+    Y.lu = solve_slow_factor(A);
+    Y.r = (int)Y.lu->r;
+    Y.basis.assign(Y.lu->p, Y.lu->p + Y.r);
+    std::sort(Y.basis.begin(), Y.basis.end());
+}
+
+void solver_finish_info(spasm_amd_solver *S)
+{
+    i64 *v = S->info;
+    v[0] = (i64)S->sys.size();
+    for (const SolverSys &Y : S->sys) {
+        if (Y.kind == SOLVER_GENERAL) v[2]++;
+        else v[1]++;
+        if (Y.kind == SOLVER_LDS) v[3] += (i64)Y.m * Y.r;
+        v[4] += Y.r;
+    }
+}
+
+spasm_amd_solver *solver_create(int count, const struct spasm_csr *const *A)
+{
+    if (count < 0) throw EngineError("count < 0");
+    std::unique_ptr<spasm_amd_solver> S(new spasm_amd_solver());
+    if (count == 0) return S.release();
+    if (!A) throw EngineError("NULL array");
+    for (int i = 0; i < count; i++)
+        if (const char *bad = batch_check(A[i])) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
+            throw EngineError(msg);
+        }
+    S->sys.resize((size_t)count);
+    std::vector<int> fast, slow;
+    for (int i = 0; i < count; i++) {
+        SolverSys &Y = S->sys[(size_t)i];
+        Y.n = A[i]->n;
+        Y.m = A[i]->m;
+        Y.prime = A[i]->field->p;
+        if (Y.n == 0 || Y.m == 0) Y.kind = SOLVER_EMPTY;
+        else if (solve_fits(Y.n, Y.m)) { Y.kind = SOLVER_LDS; fast.push_back(i); }
+        else { Y.kind = SOLVER_GENERAL; slow.push_back(i); }
+    }
+    if (!fast.empty() || !slow.empty()) {
+        require_device();
+        HIPCHK(hipGetDevice(&S->dev));
+    }
+    if (!fast.empty()) {
+        std::vector<const struct spasm_csr *> la;
+        for (int i : fast) la.push_back(A[i]);
+        BatchStaged in;
+        batch_stage(la, in);
+        solver_factor(S.get(), fast, in.row0, in.P, in.J, in.X);
+    }
+    for (int i : slow) solver_factor_slow(S->sys[(size_t)i], A[i]);
+    solver_finish_info(S.get());
+    return S.release();
+}
+
+template <class T> void solver_copy_map(DevBuf<T> &dst, const DevBuf<T> &src, size_t cnt, hipStream_t s)
+{
+    dst.alloc(cnt);
+    if (cnt > 0) HIPCHK(hipMemcpyAsync(dst.p, src.p, cnt * sizeof(T), hipMemcpyDeviceToDevice, s));
+}
+
+// the operators of all blocks from the resident concatenated CSR; only a block over the limit is fetched
+spasm_amd_solver *solver_create_blocks(const spasm_amd_blocks *B)
+{
+    blocks_need(B);
+    HIPCHK(hipSetDevice(B->dev));
+    hipStream_t s = nullptr;
+    std::unique_ptr<spasm_amd_solver> S(new spasm_amd_solver());
+    S->blocks = true;
+    S->dev = B->dev;
+    S->n = B->n;
+    S->m = B->m;
+    S->nb = B->nb;
+    S->prime = B->prime;
+    S->h_row_start = B->h_row_start;
+    S->h_col_start = B->h_col_start;
+    solver_copy_map(S->col_block, B->col_block, (size_t)B->m, s);
+    solver_copy_map(S->col_pos, B->col_pos, (size_t)B->m, s);
+    solver_copy_map(S->block_rows, B->block_rows, (size_t)B->n, s);
+    solver_copy_map(S->row_start, B->row_start, (size_t)B->nb + 1, s);
+    HIPCHK(hipStreamSynchronize(s));
+    S->sys.resize((size_t)B->nb);
+    std::vector<int> fast, slow;
+    std::vector<i64> row0;
+    for (int b = 0; b < B->nb; b++) {
+        SolverSys &Y = S->sys[(size_t)b];
+        Y.n = (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]);
+        Y.m = (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]);
+        Y.prime = B->prime;
+        if (Y.n == 0 || Y.m == 0) Y.kind = SOLVER_EMPTY;
+        else if (solve_fits(Y.n, Y.m)) {
+            Y.kind = SOLVER_LDS;
+            fast.push_back(b);
+            row0.push_back(B->h_row_start[(size_t)b] + b);
+        } else {
+            Y.kind = SOLVER_GENERAL;
+            slow.push_back(b);
+        }
+    }
+    solver_factor(S.get(), fast, row0, B->P.p, B->J.p, B->X.p);
+    for (int b : slow) {
+        struct spasm_csr *M = blocks_fetch(B, b);
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Mguard(M, spasm_csr_free);
+        solver_factor_slow(S->sys[(size_t)b], M);
+    }
+    solver_finish_info(S.get());
+    return S.release();
+}
+
+// The apply jobs of the systems sys[f] (K right-hand sides each, from brow0 / slot0) of the handle's systems which[f]: slabs of
+// kSolverRounds * q right-hand sides.  A slot holds at most r + 1 entries.
+void solver_jobs(const spasm_amd_solver *S, const std::vector<SolveSys> &sys, const std::vector<int> &which, std::vector<SolverApplyDesc> &desc,
+                 std::vector<unsigned char> &cls, std::vector<i64> &ecap)
+{
+    for (size_t f = 0; f < sys.size(); f++) {
+        const SolverSys &Y = S->sys[(size_t)which[f]];
+        const int w = kSolverRounds * Y.q;
+        for (int t0 = 0; t0 < sys[f].K; t0 += w) {
+            SolverApplyDesc d;
+            memset(&d, 0, sizeof d);
+            d.goff = Y.goff;
+            d.pivoff = Y.pivoff;
+            d.brow0 = sys[f].brow0 + t0;
+            d.slot0 = sys[f].slot0 + t0;
+            d.m = Y.m;
+            d.r = Y.r;
+            d.ldg = Y.ldg;
+            d.w = std::min(w, sys[f].K - t0);
+            d.q = Y.q;
+            d.F = zp_field_make(Y.prime);
+            desc.push_back(d);
+            cls.push_back((unsigned char)Y.cls);
+            ecap.push_back((i64)d.w * (Y.r + 1));
+        }
+    }
+}
+
+SolverApplyArgs solver_args(const spasm_amd_solver *S, const i64d *BP, const int *BJ, const int *BX)
+{
+    SolverApplyArgs a;
+    memset(&a, 0, sizeof a);
+    a.G = S->G.p;
+    a.pivrow = S->pivrow.p;
+    a.pivcol = S->pivcol.p;
+    a.BP = BP; a.BJ = BJ; a.BX = BX;
+    return a;
+}
+
+void solver_need(const spasm_amd_solver *S, bool blocks)
+{
+    if (!S) throw EngineError("NULL handle");
+    if (S->blocks != blocks) throw EngineError(blocks ? "the handle was made by spasm_amd_solver_create: use spasm_amd_solver_apply" : "the handle was made by spasm_amd_solver_create_blocks: use spasm_amd_solver_apply_blocks");
+}
+
+// Nothing is written to X / ok before all is done, and the handle is only read.
+void solver_apply_run(spasm_amd_solver *S, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
+{
+    memset(g_solver_stats, 0, sizeof g_solver_stats);
+    solver_need(S, false);
+    const int count = (int)S->sys.size();
+    if (count == 0) return;
+    if (!B || !X || !ok) throw EngineError("NULL array");
+    char msg[200];
+    for (int i = 0; i < count; i++) {
+        const SolverSys &Y = S->sys[(size_t)i];
+        const char *bad = batch_check(B[i]);
+        if (!bad && Y.prime != B[i]->field->p) bad = "the primes of A and B differ";
+        if (!bad && B[i]->m != Y.m) bad = "B->m != A->m";
+        if (!bad && B[i]->n > 0 && !ok[i]) bad = "NULL array (ok)";
+        if (bad) {
+            snprintf(msg, sizeof msg, "matrix %d (B): %s", i, bad);
+            throw EngineError(msg);
+        }
+    }
+    i64 *st = g_solver_stats;
+    st[0] = count;
+    CsrList res;
+    res.v.assign((size_t)count, nullptr);
+    std::vector<std::vector<unsigned char>> oks((size_t)count);
+    std::vector<int> fast, slow;
+    for (int i = 0; i < count; i++) {
+        const SolverSys &Y = S->sys[(size_t)i];
+        const int K = B[i]->n;
+        oks[(size_t)i].assign((size_t)K, 1);
+        if (Y.kind == SOLVER_GENERAL && K > 0) { slow.push_back(i); continue; }
+        if (Y.kind == SOLVER_LDS && Y.r > 0 && K > 0) { fast.push_back(i); continue; }
+        // no launch: without rows, or with rows that vanish, only the zero row is reachable; without columns everything is
+        const ZpField F = zp_field_make(Y.prime);
+        for (int k = 0; k < K && Y.m > 0; k++)
+            for (i64 e = B[i]->p[k]; e < B[i]->p[k + 1]; e++)
+                if (zp_reduce(F, (int64_t)B[i]->x[e]) != 0) oks[(size_t)i][(size_t)k] = 0;
+        res.v[(size_t)i] = spasm_csr_alloc(K, Y.n, 0, Y.prime, true);
+        if (!res.v[(size_t)i]) throw EngineError("out of host memory");
+        for (int k = 0; k <= K; k++) res.v[(size_t)i]->p[k] = 0;
+        st[Y.kind == SOLVER_GENERAL ? 2 : 1]++;
+    }
+    if (!fast.empty() || !slow.empty()) HIPCHK(hipSetDevice(S->dev));
+    st[1] += (i64)fast.size();
+    st[2] += (i64)slow.size();
+    if (!fast.empty()) {
+        std::vector<const struct spasm_csr *> lb;
+        for (int i : fast) lb.push_back(B[i]);
+        BatchStaged inb;
+        batch_stage(lb, inb);
+        std::vector<SolveSys> sys;
+        i64 nslots = 0;
+        for (size_t f = 0; f < fast.size(); f++) {
+            const SolverSys &Y = S->sys[(size_t)fast[f]];
+            sys.push_back(SolveSys{Y.n, Y.m, B[fast[f]]->n, 0, inb.row0[f], nslots, Y.prime});
+            nslots += B[fast[f]]->n;
+        }
+        std::vector<SolverApplyDesc> desc;
+        std::vector<unsigned char> cls;
+        std::vector<i64> ecap;
+        solver_jobs(S, sys, fast, desc, cls, ecap);
+        st[3] = (i64)desc.size();
+        std::vector<int> h_cnt;
+        std::vector<unsigned char> h_ok;
+        std::vector<int2> h_ent;
+        solve_chunks(kSolverApply, desc, cls, ecap, solver_args(S, inb.P, inb.J, inb.X), nslots, h_cnt, h_ok, h_ent, st);
+        i64 at = 0;
+        for (size_t f = 0; f < fast.size(); f++) {
+            const int i = fast[f], K = sys[f].K;
+            res.v[(size_t)i] = batch_rows_to_csr(K, sys[f].n, sys[f].prime, h_cnt.data() + sys[f].slot0, h_ent.data(), (i64)h_ent.size(), at);
+            memcpy(oks[(size_t)i].data(), h_ok.data() + sys[f].slot0, (size_t)K);
+        }
+    }
+    for (int i : slow) res.v[(size_t)i] = solve_slow_with(S->sys[(size_t)i].lu, S->sys[(size_t)i].n, S->sys[(size_t)i].prime, B[i], oks[(size_t)i].data());
+    for (int i = 0; i < count; i++)
+        for (unsigned char v : oks[(size_t)i]) st[7] += v ? 0 : 1;
+    for (int i = 0; i < count; i++)
+        if (!oks[(size_t)i].empty()) memcpy(ok[i], oks[(size_t)i].data(), oks[(size_t)i].size());
+    memcpy(X, res.v.data(), sizeof(struct spasm_csr *) * (size_t)count);
+    res.v.clear();
+}
+
+// spasm_amd_solver_apply_blocks: the blocks a right-hand side meets are applied, not eliminated.  A block whose entries all vanish
+// mod p (rank 0) is launched like the others: its job is the zero test.
+struct BlocksApplyOps : BlocksSolveOps {
+    const spasm_amd_solver *S;
+    std::vector<SolverApplyDesc> desc;
+    std::vector<unsigned char> cls;
+    explicit BlocksApplyOps(const spasm_amd_solver *S_) : S(S_) {}
+    bool fits(int b, i64, i64) override { return S->sys[(size_t)b].kind == SOLVER_LDS; }
+    i64 plan(const std::vector<SolveSys> &sys, const std::vector<int> &blk, int &njobs) override
+    {
+        std::vector<i64> ecap;
+        desc.clear();
+        cls.clear();
+        solver_jobs(S, sys, blk, desc, cls, ecap);
+        njobs = (int)desc.size();
+        i64 ents = 0;
+        for (int q = 0; q < njobs; q++) { desc[(size_t)q].slice = ents; ents += ecap[(size_t)q]; }
+        return ents;
+    }
+    struct spasm_csr *slow(int b, const struct spasm_csr *Rb, unsigned char *okb) override
+    {
+        const SolverSys &Y = S->sys[(size_t)b];
+        return solve_slow_with(Y.lu, Y.n, Y.prime, Rb, okb);
+    }
+    i64 launch(const i64d *run_start, const int *sj, const int *sx, int *cnt, i64d *src, unsigned char *ok, int2 *scratch, hipStream_t s) override
+    {
+        const int nj = (int)desc.size();
+        DevBuf<SolverApplyDesc> d_desc;
+        DevBuf<int> d_items;
+        d_desc.alloc((size_t)nj);
+        d_items.alloc((size_t)nj);
+        HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nj * sizeof(SolverApplyDesc), hipMemcpyHostToDevice, s));
+        std::vector<int> items((size_t)nj);
+        SolverApplyArgs a = solver_args(S, run_start, sj, sx);
+        a.desc = d_desc.p;
+        a.cnt = cnt;
+        a.src = src;
+        a.ok = ok;
+        a.scratch = scratch;
+        const i64 launches = batch_launch_jobs(kSolverApply, cls, 0, nj, items, d_items.p, a, nullptr, s);
+        HIPCHK(hipStreamSynchronize(s)); // (items and the buffers belong to this scope)
+        return launches;
+    }
+};
+
+void solver_apply_blocks_run(spasm_amd_solver *S, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+{
+    memset(g_solver_stats, 0, sizeof g_solver_stats);
+    solver_need(S, true);
+    BlocksApplyOps ops(S);
+    const BlocksView V{S->nb, S->prime, S->col_block.p, S->col_pos.p, S->block_rows.p, S->row_start.p, &S->h_row_start, &S->h_col_start};
+    solve_blocks_apply(V, S->n, S->m, S->dev, ops, g_solver_stats, Rhs, X, ok);
 }
 
 } // namespace
@@ -8820,6 +9343,63 @@ SPASM_API int spasm_amd_blocks_solve(spasm_amd_blocks *B, const struct spasm_csr
 SPASM_API void spasm_amd_solve_stats(i64 *out)
 {
     if (out) memcpy(out, g_solve_stats, sizeof g_solve_stats);
+}
+
+// ---- X * A = B with A factored once (solver.hpp; engine extension) ----
+SPASM_API spasm_amd_solver *spasm_amd_solver_create(int count, const struct spasm_csr *const *A)
+{
+    BLOCKS_TRY("spasm_amd_solver_create", return solver_create(count, A);, nullptr)
+}
+
+SPASM_API spasm_amd_solver *spasm_amd_solver_create_blocks(const spasm_amd_blocks *Bk)
+{
+    BLOCKS_TRY("spasm_amd_solver_create_blocks", return solver_create_blocks(Bk);, nullptr)
+}
+
+SPASM_API int spasm_amd_solver_apply(spasm_amd_solver *S, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
+{
+    BATCH_TRY("spasm_amd_solver_apply", solver_apply_run(S, B, X, ok);)
+}
+
+SPASM_API int spasm_amd_solver_apply_blocks(spasm_amd_solver *S, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
+{
+    BLOCKS_TRY("spasm_amd_solver_apply_blocks", solver_apply_blocks_run(S, Rhs, X, ok); return 0;, -1)
+}
+
+SPASM_API void spasm_amd_solver_info(const spasm_amd_solver *S, i64 *out)
+{
+    if (S && out) memcpy(out, S->info, sizeof S->info);
+}
+
+SPASM_API int spasm_amd_solver_ranks(const spasm_amd_solver *S, i64 *rank)
+{
+    BLOCKS_TRY("spasm_amd_solver_ranks", if (!S) throw EngineError("NULL handle");
+               if (!S->sys.empty() && !rank) throw EngineError("NULL array");
+               for (size_t i = 0; i < S->sys.size(); i++) rank[i] = S->sys[i].r;
+               return 0;, -1)
+}
+
+SPASM_API int spasm_amd_solver_basis(const spasm_amd_solver *S, int i, int *rows)
+{
+    BLOCKS_TRY("spasm_amd_solver_basis", if (!S) throw EngineError("NULL handle");
+               if (i < 0 || (size_t)i >= S->sys.size()) throw EngineError("system index out of range");
+               const std::vector<int> &b = S->sys[(size_t)i].basis;
+               if (!b.empty() && !rows) throw EngineError("NULL array");
+               if (!b.empty()) memcpy(rows, b.data(), b.size() * sizeof(int));
+               return (int)b.size();, -1)
+}
+
+SPASM_API void spasm_amd_solver_stats(i64 *out)
+{
+    if (out) memcpy(out, g_solver_stats, sizeof g_solver_stats);
+}
+
+SPASM_API void spasm_amd_solver_free(spasm_amd_solver *S)
+{
+    if (!S) return;
+    DeviceGuard g;
+    (void)hipSetDevice(S->dev);
+    delete S;
 }
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
