@@ -687,6 +687,51 @@ int spasm_amd_solver_basis(const spasm_amd_solver *S, int i, int *rows);
 void spasm_amd_solver_stats(i64 *out);   /* of the last apply of this thread */
 void spasm_amd_solver_free(spasm_amd_solver *S);
 
+/* ---- Engine extension: the resident solver against dense right-hand sides that stay on the device (csrc/solver.hpp) ----
+ * spasm_amd_solver_apply takes and returns host CSR; this apply takes the right-hand sides as the COLUMNS of a dense row-major
+ * array and returns the solutions as columns, the layout of spasm_amd_spmv_apply_dev and spasm_amd_trsolve_apply_dev, so that a
+ * loop (solve, form the residual with the resident product, solve again) runs on one stream without a right-hand side on the host.
+ *   matrix        one per handle.  A handle of create_blocks: A, the matrix that was split (N = its rows, M = its columns), ok has
+ *                 K bytes.  A handle of create: diag(A_0 .. A_{count-1}), N = sum n_i, M = sum m_i; system i owns rows
+ *                 sum_{j<i} m_j .. of B and rows sum_{j<i} n_j .. of X; ok has count * K bytes, ok[i * K + v]; every system
+ *                 reduces by its own prime.
+ *   B, X          B is M x K with leading dimension ldb >= K, X is N x K with ldx >= K, int32; right-hand side v is column v of B
+ *                 and its solution column v of X: X[:, v]^T * A == B[:, v]^T.  Any int32 is accepted in B and reduced on load.
+ *   result        column v of X, restricted to a system, is entry for entry the dense image of the row spasm_amd_solver_apply /
+ *                 _apply_blocks return for the same right-hand side: the unique solution that is zero outside the canonical row
+ *                 basis, as balanced residues; all zero where ok = 0.  X is overwritten in its whole N x K window; the words
+ *                 outside it (ldx > K) and all of B are left as they were.
+ *   apply_dense   host arrays: upload, apply_dense_dev on the NULL stream, download.
+ *   _dev          device pointers for B, X and ok.  stream NULL: returns when X and ok are written; otherwise everything is
+ *                 enqueued on that hipStream_t and the call does not wait for it.  The job plan of the most recent K is kept in
+ *                 the handle: a second apply with the same K uploads and allocates nothing.  An apply with another K rebuilds
+ *                 the plan and, before it does, WAITS FOR THE DEVICE (hipDeviceSynchronize), so that applies enqueued earlier
+ *                 end on the plan they began with: applies of different K may follow each other on a stream without a
+ *                 synchronise by the caller, at the price of that wait; a loop that alternates between two K pays it at every
+ *                 call.  STREAM CAPTURE: an apply with the K of the plan only enqueues on `stream`; one that would
+ *                 have to rebuild the plan while `stream` is capturing is refused with -1 before anything is touched, and the
+ *                 capture stays valid: apply once with that K before the capture begins.
+ *   general path  a handle with a system over the limit of the LDS path is REFUSED (the factorization of such a system lives on
+ *                 the host and is not applied to dense device arrays): -1, nothing written, the error names the first such
+ *                 system.  dense_info out[3] tells beforehand.
+ *   dense_info    out[8] = N, M, rows of ok (count, or 1 for a handle of create_blocks), systems on the general path, K of the
+ *                 cached plan (0: none), jobs (system-slab workgroups) of that plan, kernel launches of one apply with that plan,
+ *                 plans built so far.
+ *   use           one host thread at a time per handle, as for the other applies.  Applies enqueued on ONE stream need nothing
+ *                 more.  Applies of a create_blocks handle enqueued on different streams share the flag words of the plan: the
+ *                 caller orders them (an event, or a synchronise).
+ *   errors        a NULL handle; K < 0; ldb < K or ldx < K; a NULL B, X or ok with K > 0 and a non-empty shape; B and X that
+ *                 overlap (windows that share a word, tested row by row: two windows side by side in one array, which
+ *                 interleave without sharing one, are accepted); a plan to rebuild on a capturing stream; no device.  -1, no output word written, spasm_amd_last_error() names the function and the cause, the
+ *                 handle stays usable; after success the error text is empty.  K == 0 succeeds (also on a handle with a system
+ *                 of the general path: there is nothing to refuse), and so does a handle of zero systems for any K; neither
+ *                 needs a device or writes anything.  The create_blocks handle of a matrix without rows and columns has no
+ *                 system either, but its ok has K bytes: they are set to 1 (apply_dense does that on the host and needs no
+ *                 device; apply_dense_dev is given a device pointer and writes it there). */
+int spasm_amd_solver_apply_dense(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok);
+int spasm_amd_solver_apply_dense_dev(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream);
+void spasm_amd_solver_dense_info(const spasm_amd_solver *S, i64 *out);
+
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 

@@ -295,6 +295,9 @@ SIGNATURES = {
     "spasm_amd_solver_basis": (C.c_int32, [C.c_void_p, C.c_int32, _P(C.c_int32)]),
     "spasm_amd_solver_stats": (None, [_P(C.c_int64)]),
     "spasm_amd_solver_free": (None, [C.c_void_p]),
+    "spasm_amd_solver_apply_dense": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_solver_apply_dense_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spasm_amd_solver_dense_info": (None, [C.c_void_p, _P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -1332,6 +1332,7 @@ def solve_stats():
 # X * A = B with A factored once  (spasm_amd_solver_*; csrc/solver.hpp)
 # ---------------------------------------------------------------------------------------------
 SOLVER_INFO = ("systems", "lds_path", "general_path", "operator_words", "rank_sum", "factor_jobs", "create_launches", "create_us")
+SOLVER_DENSE_INFO = ("rows", "cols", "ok_rows", "general_path", "plan_k", "plan_jobs", "plan_launches", "plans_built")
 
 
 class BatchSolver:
@@ -1341,7 +1342,15 @@ class BatchSolver:
 
     solve(rhs) -> (X, ok): for a solver made from a list, rhs is a list with one CSR per system and the result is what
     solve_batch(mats, rhs) returns, byte for byte on the LDS path; for one made from blocks, rhs is one CSR and the result is what
-    DeviceBlocks.solve(rhs) returns.  One solve at a time per solver."""
+    DeviceBlocks.solve(rhs) returns.  One solve at a time per solver.
+
+    solve_dense(B, X=None) -> (X, ok) (spasm_amd_solver_apply_dense / _dev): the right-hand sides are the COLUMNS of a dense B, the
+    layout of SpMV.apply and TriangularSolver.solve.  A solver made from blocks stands for the matrix A that was split: B is
+    m x k, X is n x k and ok has k flags.  A solver made from a list stands for diag(A[0], A[1], ...): system i owns the rows
+    sum(m_j, j < i) ... of B and sum(n_j, j < i) ... of X, and ok has shape (count, k).  Column v of X is the dense image of what
+    solve returns for that right-hand side, and zero where ok is False; B is left as it was.  B of shape (rows,) is one vector (X and
+    ok lose the axis too).  int32 numpy arrays, or int32 torch tensors on the current device (enqueued on the current stream; ok
+    is then a bool tensor, and nothing touches the host).  A solver with a system over the limit of the LDS path refuses."""
 
     def __init__(self, mats):
         mats = list(mats)
@@ -1456,6 +1465,92 @@ class BatchSolver:
         if rc != 0:
             raise SpasmError(_abi.last_error() or "spasm_amd_solver_apply failed")
         return [CSR(out[i]) for i in range(cnt)], [o[: B.n].astype(np.bool_) for o, B in zip(oks, rhs)]
+
+    def dense_info(self):
+        """The shape solve_dense works on and its cached plan (spasm_amd_solver_dense_info), keyed by SOLVER_DENSE_INFO."""
+        out = (C.c_int64 * 8)()
+        _abi.lib().spasm_amd_solver_dense_info(self._need(), out)
+        return {k: int(v) for k, v in zip(SOLVER_DENSE_INFO, out)}
+
+    def _dense_shape(self):
+        if self._blocks:
+            return self.shape[0], self.shape[1], 1
+        return sum(n for n, _ in self.shapes), sum(m for _, m in self.shapes), self._count
+
+    def solve_dense(self, B, X=None):
+        h = self._need()
+        n, m, okrows = self._dense_shape()
+        if type(B).__module__.startswith("torch"):
+            return self._solve_dense_torch(h, B, X, n, m, okrows)
+        if not isinstance(B, np.ndarray) or B.dtype != np.int32:
+            raise TypeError("B must be an int32 numpy array or torch tensor")
+        if B.ndim not in (1, 2) or B.shape[0] != m:
+            raise ValueError(f"B must have shape ({m},) or ({m}, k), not {B.shape}")
+        k = 1 if B.ndim == 1 else B.shape[1]
+        if X is None:
+            X = np.zeros((n,) + B.shape[1:], dtype=np.int32)
+        if not isinstance(X, np.ndarray) or X.dtype != np.int32:
+            raise TypeError("X must be an int32 numpy array")
+        if X.shape != (n,) + B.shape[1:]:
+            raise ValueError(f"X must have shape {(n,) + B.shape[1:]}, not {X.shape}")
+        if not X.flags["WRITEABLE"]:
+            raise ValueError("X must be writable")
+        Bc = _rows_view(B, "B") if B.size else B   # (an array without elements has no strides to speak of)
+        Xc = _rows_view(X, "X") if X.size else X
+        if n > 0 and m > 0 and k > 0 and np.shares_memory(Bc, Xc):
+            raise ValueError("B and X must not overlap")
+        ldb = k if B.ndim == 1 else max(Bc.strides[0] // 4, k)
+        ldx = k if X.ndim == 1 else max(Xc.strides[0] // 4, k)
+        ok = np.ones(max(okrows * k, 1), dtype=np.uint8)
+        rc = _abi.lib().spasm_amd_solver_apply_dense(h, int(k), Bc.ctypes.data, ldb, Xc.ctypes.data, ldx, ok.ctypes.data)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        ok = ok[: okrows * k].astype(bool)
+        ok = ok if self._blocks else ok.reshape(okrows, k)
+        return X, (ok[..., 0] if B.ndim == 1 else ok)
+
+    def _solve_dense_torch(self, h, B, X, n, m, okrows):
+        import torch
+
+        if B.dtype != torch.int32 or B.device.type != "cuda" or B.device.index != torch.cuda.current_device():
+            raise TypeError("B must be an int32 tensor on the current device")
+        if B.dim() not in (1, 2) or B.shape[0] != m:
+            raise ValueError(f"B must have shape ({m},) or ({m}, k), not {tuple(B.shape)}")
+        k = 1 if B.dim() == 1 else B.shape[1]
+        if X is None:
+            X = torch.zeros((n,) + tuple(B.shape[1:]), dtype=torch.int32, device=B.device)
+        if X.dtype != torch.int32 or X.device != B.device:
+            raise TypeError("X must be an int32 tensor on the device of B")
+        if tuple(X.shape) != (n,) + tuple(B.shape[1:]):
+            raise ValueError(f"X must have shape {(n,) + tuple(B.shape[1:])}, not {tuple(X.shape)}")
+        for t, name in ((B, "B"), (X, "X")):
+            if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < k):
+                raise ValueError(f"{name} must have unit stride along its rows")
+        ldb = k if B.dim() == 1 else max(B.stride(0), k)
+        ldx = k if X.dim() == 1 else max(X.stride(0), k)
+        if n > 0 and m > 0 and k > 0 and _windows_overlap(B.data_ptr(), m, ldb, X.data_ptr(), n, ldx, k):
+            raise ValueError("B and X must not overlap")
+        ok = torch.ones(max(okrows * k, 1), dtype=torch.uint8, device=B.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = _abi.lib().spasm_amd_solver_apply_dense_dev(h, int(k), C.c_void_p(B.data_ptr()), ldb, C.c_void_p(X.data_ptr()), ldx,
+                                                         C.c_void_p(ok.data_ptr()), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        ok = ok[: okrows * k].bool()
+        ok = ok if self._blocks else ok.reshape(okrows, k)
+        return X, (ok[..., 0] if B.dim() == 1 else ok)
+
+
+def _windows_overlap(b0, m, ldb, x0, n, ldx, k):
+    """Do the windows of m rows at b0 and n rows at x0 (k int32 words a row, ldb and ldx words apart) share a byte?  Row by row, as
+    the engine tests it: two windows side by side in one array interleave without sharing a word."""
+    length, rowb, rowx = 4 * k, 4 * ldb, 4 * ldx
+    if not (b0 < x0 + (n - 1) * rowx + length and x0 < b0 + (m - 1) * rowb + length):
+        return False
+    d = (b0 - x0) + rowb * np.arange(m, dtype=np.int64)    # row j of X meets a row of B iff |d - j * rowx| < length
+    lo = np.maximum((d - length) // rowx + 1, 0)
+    hi = np.minimum(-((-(d + length)) // rowx) - 1, n - 1)
+    return bool((lo <= hi).any())
 
 
 def solver_stats():

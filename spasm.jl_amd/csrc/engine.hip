@@ -7978,6 +7978,16 @@ struct spasm_amd_solver {
     DevBuf<int> col_block, col_pos, block_rows;
     DevBuf<i64d> row_start;
     std::vector<i64> h_row_start, h_col_start;
+    // the dense apply: the global columns of every block (a handle made from a split) and the job plan of the most recent K
+    DevBuf<int> block_cols;
+    struct DensePlan {
+        int K = 0, njobs = 0, launches = 0;
+        int hist[BATCH_NCLASS] = {0, 0, 0, 0};
+        DevBuf<SolverDenseDesc> desc;
+        DevBuf<int> items;
+        DevBuf<unsigned> flag;
+    } dense;
+    i64 dense_built = 0;
     ~spasm_amd_solver()
     {
         for (SolverSys &Y : sys) spasm_lu_free(Y.lu);
@@ -7990,6 +8000,7 @@ thread_local i64 g_solver_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 const ElimKernels<SolverFactorArgs> kSolverFactor = {{k_solver_factor<64>, k_solver_factor<128>, k_solver_factor<256>, k_solver_factor<512>}};
 const ElimKernels<SolverApplyArgs> kSolverApply = {{k_solver_apply<64>, k_solver_apply<128>, k_solver_apply<256>, k_solver_apply<512>}};
+const ElimKernels<SolverDenseArgs> kSolverDense = {{k_solver_apply_dense<64>, k_solver_apply_dense<128>, k_solver_apply_dense<256>, k_solver_apply_dense<512>}};
 
 // rounds of q right-hand sides a job of k_solver_apply works through: what staging G once is spread over
 constexpr int kSolverRounds = 8;
@@ -8177,6 +8188,12 @@ spasm_amd_solver *solver_create_blocks(const spasm_amd_blocks *B)
     solver_copy_map(S->col_pos, B->col_pos, (size_t)B->m, s);
     solver_copy_map(S->block_rows, B->block_rows, (size_t)B->n, s);
     solver_copy_map(S->row_start, B->row_start, (size_t)B->nb + 1, s);
+    // the dense apply reads B through the columns of a block in the block's order: the inverse of (col_block, col_pos)
+    S->block_cols.alloc((size_t)B->m);
+    if (B->m > 0) {
+        hipLaunchKernelGGL(k_solver_block_cols, dim3(cdiv(B->m, 256)), dim3(256), 0, s, B->m, S->col_block.p, S->col_pos.p, B->col_start.p, S->block_cols.p);
+        HIPCHK(hipGetLastError());
+    }
     HIPCHK(hipStreamSynchronize(s));
     S->sys.resize((size_t)B->nb);
     std::vector<int> fast, slow;
@@ -8385,6 +8402,223 @@ void solver_apply_blocks_run(spasm_amd_solver *S, const struct spasm_csr *Rhs, s
     BlocksApplyOps ops(S);
     const BlocksView V{S->nb, S->prime, S->col_block.p, S->col_pos.p, S->block_rows.p, S->row_start.p, &S->h_row_start, &S->h_col_start};
     solve_blocks_apply(V, S->n, S->m, S->dev, ops, g_solver_stats, Rhs, X, ok);
+}
+
+// ---- the dense apply (solver.hpp, "The dense apply"): spasm_amd_solver_apply_dense / _dev.  One matrix per handle: A of the split,
+// or diag(A_0 .. A_{count-1}) of a list, system i on rows sum_{j<i} m_j .. of B and sum_{j<i} n_j .. of X.
+void solver_dense_dims(const spasm_amd_solver *S, i64 &N, i64 &M)
+{
+    N = S->n;
+    M = S->m;
+    if (S->blocks) return;
+    for (const SolverSys &Y : S->sys) { N += Y.n; M += Y.m; }
+}
+
+// Class, stride and tiles in flight of the dense apply of an m x r operator: G, the m words of the order of the rows and q tiles
+// of r * T words, each part rounded up to 16 bytes.  The odd stride where it fits the largest class; q = at most one tile per group
+// of whole waves that covers m.  Without rank nothing lies in LDS.
+void solver_dense_shape(int m, int r, int &cls, int &ldg, int &q)
+{
+    constexpr int T = SOLVER_DENSE_T;
+    const int mp = m > 64 ? (m + 63) & ~63 : 64;
+    if (r == 0) {
+        cls = 0;
+        ldg = 1;
+        q = std::max(kBatchClass[0].bs / mp, 1);
+        return;
+    }
+    auto fixed = [&](int ld) { return (((i64)m * ld + 3) & ~(i64)3) + (((i64)m + 3) & ~(i64)3); };
+    const i64 tile = (i64)r * T;
+    ldg = r;
+    if (ldg % 2 == 0 && fixed(ldg + 1) + tile <= kBatchClass[BATCH_NCLASS - 1].cap) ldg++;
+    const i64 need = fixed(ldg) + tile;
+    int c = 0;
+    while (c < BATCH_NCLASS - 1 && need > kBatchClass[c].cap) c++;
+    if (need > kBatchClass[c].cap) throw EngineError("internal error: an operator and a tile of right-hand sides do not fit the largest class");
+    const int bs = kBatchClass[c].bs;
+    q = mp <= bs ? (int)std::min<i64>(bs / mp, (kBatchClass[c].cap - fixed(ldg)) / tile) : 1;
+    cls = c;
+}
+
+// The plan of an apply of K columns: one job per (system, slab of kSolverRounds * q tiles), sorted by class, on the device.  Kept in
+// the handle until another K comes: an apply with the K of the plan uploads and allocates nothing.  Another K overwrites the
+// buffers of the plan in place, and an earlier apply may still be queued on a stream that the copies below do not wait for (a
+// non-blocking stream): the rebuild therefore waits for the device first, so that an apply in flight ends on the plan it began with.
+void solver_dense_plan(spasm_amd_solver *S, int K, hipStream_t s)
+{
+    spasm_amd_solver::DensePlan &P = S->dense;
+    if (P.K == K) return;
+    // (a capture can neither wait for the device nor take the blocking copies below: refused before anything is touched)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "the stream is capturing and the handle holds no plan for K = %d: apply once with this K before the capture", K);
+        throw EngineError(msg);
+    }
+    P.K = 0;
+    if (S->dense_built > 0) HIPCHK(hipDeviceSynchronize());
+    std::vector<SolverDenseDesc> desc;
+    std::vector<unsigned char> cls;
+    i64 brow = 0, xrow = 0;
+    for (size_t i = 0; i < S->sys.size(); i++) {
+        const SolverSys &Y = S->sys[i];
+        if (S->blocks) {
+            brow = S->h_col_start[i];
+            xrow = S->h_row_start[i];
+        }
+        int c = 0, ldg = 1, q = 1;
+        solver_dense_shape(Y.m, Y.r, c, ldg, q);
+        const i64 w = (i64)kSolverRounds * q * SOLVER_DENSE_T;
+        for (i64 v0 = 0; v0 < K; v0 += w) {
+            SolverDenseDesc d;
+            memset(&d, 0, sizeof d);
+            d.goff = Y.goff;
+            d.pivoff = Y.pivoff;
+            d.brow = brow;
+            d.xrow = xrow;
+            d.okoff = (i64)i * K;
+            d.n = Y.n;
+            d.m = Y.m;
+            d.r = Y.r;
+            d.ldg = ldg;
+            d.v0 = (int)v0;
+            d.w = (int)std::min<i64>(w, K - v0);
+            d.q = q;
+            d.F = zp_field_make(Y.prime);
+            desc.push_back(d);
+            cls.push_back((unsigned char)c);
+        }
+        brow += Y.m;
+        xrow += Y.n;
+    }
+    const int nj = (int)desc.size();
+    int at[BATCH_NCLASS], sum = 0;
+    for (int k = 0; k < BATCH_NCLASS; k++) P.hist[k] = 0;
+    for (int j = 0; j < nj; j++) P.hist[cls[(size_t)j]]++;
+    for (int k = 0; k < BATCH_NCLASS; k++) { at[k] = sum; sum += P.hist[k]; }
+    std::vector<int> items((size_t)nj);
+    for (int j = 0; j < nj; j++) items[(size_t)at[cls[(size_t)j]]++] = j;
+    P.desc.ensure((size_t)nj);
+    P.items.ensure((size_t)nj);
+    if (S->blocks) P.flag.ensure((size_t)K);
+    if (nj > 0) {
+        HIPCHK(hipMemcpy(P.desc.p, desc.data(), (size_t)nj * sizeof(SolverDenseDesc), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(P.items.p, items.data(), (size_t)nj * sizeof(int), hipMemcpyHostToDevice));
+    }
+    P.njobs = nj;
+    P.launches = S->blocks ? 1 : 0; // (the finishing kernel)
+    for (int k = 0; k < BATCH_NCLASS; k++) P.launches += P.hist[k] > 0 ? 1 : 0;
+    P.K = K;
+    S->dense_built++;
+}
+
+// Do the windows of B (M rows of K words, ldb apart) and X (N rows, ldx apart) share a byte?  Row by row, not by their extents:
+// two windows side by side in one array (ldb, ldx > K) interleave without sharing a word.  The rows are walked only where the
+// extents meet.
+bool solver_dense_overlap(const void *B, i64 M, i64 ldb, const void *X, i64 N, i64 ldx, i64 K)
+{
+    const i64 len = K * (i64)sizeof(int), rowb = ldb * (i64)sizeof(int), rowx = ldx * (i64)sizeof(int);
+    const uintptr_t b0 = (uintptr_t)B, b1 = b0 + (uintptr_t)((M - 1) * rowb + len);
+    const uintptr_t x0 = (uintptr_t)X, x1 = x0 + (uintptr_t)((N - 1) * rowx + len);
+    if (!(b0 < x1 && x0 < b1)) return false;
+    auto floordiv = [](i64 a, i64 b) { return a / b - ((a % b != 0 && (a < 0) != (b < 0)) ? 1 : 0); };
+    for (i64 i = 0; i < M; i++) {
+        // row j of X meets row i of B iff |d - j * rowx| < len, d = the distance of row i of B from the first word of X
+        const i64 d = (i64)(b0 - x0) + i * rowb;
+        const i64 lo = std::max<i64>(floordiv(d - len, rowx) + 1, 0), hi = std::min<i64>(-floordiv(-(d + len), rowx) - 1, N - 1);
+        if (lo <= hi) return true;
+    }
+    return false;
+}
+
+// The checks that need no device, in the order of the header.  false: nothing to do (no system, or no column).
+bool solver_dense_check(const spasm_amd_solver *S, int K, const void *B, i64 ldb, const void *X, i64 ldx, const void *ok)
+{
+    if (!S) throw EngineError("NULL handle");
+    if (K < 0) throw EngineError("K < 0");
+    if (ldb < K) throw EngineError("ldb < K");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (K == 0 || (S->sys.empty() && !S->blocks)) return false;
+    for (size_t i = 0; i < S->sys.size(); i++)
+        if (S->sys[i].kind == SOLVER_GENERAL) {
+            char msg[200];
+            snprintf(msg, sizeof msg, "system %zu is over the limit of the LDS path (general path): the dense apply does not take it", i);
+            throw EngineError(msg);
+        }
+    i64 N = 0, M = 0;
+    solver_dense_dims(S, N, M);
+    if ((M > 0 && !B) || (N > 0 && !X) || !ok) throw EngineError("NULL array");
+    if (M > 0 && N > 0 && solver_dense_overlap(B, M, ldb, X, N, ldx, K)) throw EngineError("B and X overlap");
+    return true;
+}
+
+// everything on stream s: the flags (a blocks handle), one launch per class that occurs, the finishing kernel (a blocks handle)
+void solver_dense_enqueue(spasm_amd_solver *S, int K, const int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
+{
+    solver_dense_plan(S, K, s);
+    const spasm_amd_solver::DensePlan &P = S->dense;
+    SolverDenseArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = P.desc.p;
+    a.G = S->G.p;
+    a.pivrow = S->pivrow.p;
+    a.pivcol = S->pivcol.p;
+    a.B = B;
+    a.ldb = ldb;
+    a.X = X;
+    a.ldx = ldx;
+    if (S->blocks) {
+        a.colmap = S->block_cols.p;
+        a.rowmap = S->block_rows.p;
+        a.flag = P.flag.p;
+        HIPCHK(hipMemsetAsync(P.flag.p, 0, (size_t)K * sizeof(unsigned), s));
+    } else a.ok = ok;
+    int first = 0;
+    for (int k = 0; k < BATCH_NCLASS; k++) {
+        if (P.hist[k] > 0) batch_launch_class(kSolverDense, k, a, P.items.p + first, P.hist[k], s);
+        first += P.hist[k];
+    }
+    if (S->blocks) {
+        const i64 words = (i64)std::max(S->n, 1) * K;
+        hipLaunchKernelGGL(k_solver_dense_finish, dim3(cdiv(words, 256)), dim3(256), 0, s, S->n, K, P.flag.p, ok, X, (i64d)ldx);
+        HIPCHK(hipGetLastError());
+    }
+}
+
+void solver_apply_dense_dev(spasm_amd_solver *S, int K, const int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
+{
+    if (!solver_dense_check(S, K, B, ldb, X, ldx, ok)) return;
+    require_device();
+    HIPCHK(hipSetDevice(S->dev));
+    solver_dense_enqueue(S, K, B, ldb, X, ldx, ok, s);
+    if (!s) HIPCHK(hipStreamSynchronize(s));
+}
+
+// host arrays: upload the window of B, the apply on the NULL stream, download the window of X and ok
+void solver_apply_dense_host(spasm_amd_solver *S, int K, const int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok)
+{
+    if (!solver_dense_check(S, K, B, ldb, X, ldx, ok)) return;
+    if (S->sys.empty()) { // the split of a matrix without rows and columns: 0 = 0 holds for every column, and no device is needed
+        memset(ok, 1, (size_t)K);
+        return;
+    }
+    require_device();
+    HIPCHK(hipSetDevice(S->dev));
+    i64 N = 0, M = 0;
+    solver_dense_dims(S, N, M);
+    const size_t nok = S->blocks ? (size_t)K : S->sys.size() * (size_t)K, line = (size_t)K * sizeof(int);
+    DevBuf<int> dB, dX;
+    DevBuf<unsigned char> dok;
+    dB.alloc((size_t)M * K);
+    dX.alloc((size_t)N * K);
+    dok.alloc(nok);
+    if (M > 0) HIPCHK(hipMemcpy2D(dB.p, line, B, (size_t)ldb * sizeof(int), line, (size_t)M, hipMemcpyHostToDevice));
+    solver_dense_enqueue(S, K, dB.p, K, dX.p, K, dok.p, nullptr);
+    HIPCHK(hipStreamSynchronize(nullptr));
+    std::vector<unsigned char> hok(nok);
+    HIPCHK(hipMemcpy(hok.data(), dok.p, nok, hipMemcpyDeviceToHost));
+    if (N > 0) HIPCHK(hipMemcpy2D(X, (size_t)ldx * sizeof(int), dX.p, line, line, (size_t)N, hipMemcpyDeviceToHost));
+    memcpy(ok, hok.data(), nok);
 }
 
 } // namespace
@@ -9364,6 +9598,26 @@ SPASM_API int spasm_amd_solver_apply(spasm_amd_solver *S, const struct spasm_csr
 SPASM_API int spasm_amd_solver_apply_blocks(spasm_amd_solver *S, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
 {
     BLOCKS_TRY("spasm_amd_solver_apply_blocks", solver_apply_blocks_run(S, Rhs, X, ok); return 0;, -1)
+}
+
+SPASM_API int spasm_amd_solver_apply_dense(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok)
+{
+    BLOCKS_TRY("spasm_amd_solver_apply_dense", solver_apply_dense_host(S, K, B, ldb, X, ldx, ok); return 0;, -1)
+}
+
+SPASM_API int spasm_amd_solver_apply_dense_dev(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream)
+{
+    BLOCKS_TRY("spasm_amd_solver_apply_dense_dev", solver_apply_dense_dev(S, K, B, ldb, X, ldx, ok, (hipStream_t)stream); return 0;, -1)
+}
+
+SPASM_API void spasm_amd_solver_dense_info(const spasm_amd_solver *S, i64 *out)
+{
+    if (!S || !out) return;
+    i64 N = 0, M = 0, general = 0;
+    solver_dense_dims(S, N, M);
+    for (const SolverSys &Y : S->sys) general += Y.kind == SOLVER_GENERAL ? 1 : 0;
+    const i64 v[8] = {N, M, S->blocks ? 1 : (i64)S->sys.size(), general, S->dense.K, S->dense.K ? S->dense.njobs : 0, S->dense.K ? S->dense.launches : 0, S->dense_built};
+    memcpy(out, v, sizeof v);
 }
 
 SPASM_API void spasm_amd_solver_info(const spasm_amd_solver *S, i64 *out)
