@@ -301,6 +301,29 @@ spasm_amd_dcsr *spasm_amd_dcsr_lincomb(i64 a, const spasm_amd_dcsr *A, i64 b, co
 spasm_amd_dcsr *spasm_amd_dcsr_submatrix(const spasm_amd_dcsr *A, int r0, int r1, int c0, int c1);
 int spasm_amd_dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B);
 void spasm_amd_dcsr_stats(const spasm_amd_dcsr *D, i64 *out);
+/* Structural operations on resident matrices (csrc/reshape.hpp; engine extension): what SpaSM.jl offers on CSR as transpose
+ * (src/SpaSM.jl:589), vcat / hcat (:192-193, through the host there) and spasm_permute (:611), for matrices that stay on the device.
+ *   transpose  the m x n matrix with entry (j, i) = entry (i, j) of A
+ *   permute    p and qinv are HOST arrays of n and m ints, NULL = the identity.  Row i of the result is row p[i] of A, and an entry
+ *              on column j of A lands on column qinv[j].  (These are the argument names of spasm_permute(A, p, qinv, with_values);
+ *              libspasm's source was not at hand, so the semantics are stated here and the symbol spasm_permute is not claimed.)
+ *              Both arrays are checked to be bijections on the host, O(n + m), before anything is launched.
+ *   vcat       count >= 1 matrices with equal column counts, rows stacked in the order of the list, in one pass
+ *   hcat       count >= 1 matrices with equal row counts, side by side: the columns of D[k] are renumbered from the sum of the
+ *              widths before it
+ * Every result obeys the CONTRACT above word for word (exact: values are copied, never computed; canonical; deterministic;
+ * operands untouched) and is a new handle.  An operand that is not canonical yet (an upload) is first brought to canonical form,
+ * as equal does.  Errors -- a NULL argument, count < 1, a NULL element, shapes or primes that differ, p or qinv not a
+ * permutation, more than INT_MAX rows or columns in all, no device ("no HIP device"), out of device memory -- return NULL and
+ * spasm_amd_last_error() says why.
+ * spasm_amd_dcsr_stats of such a result: out[12] = entries moved, the same again, rows ordered by the one-wave / the workgroup /
+ * the long-row path (0 where no ordering was needed: vcat, hcat, a permutation of rows alone), 1, device microseconds of the
+ * count / move / order steps (HIP events), peak scratch bytes, operation (4 transpose, 5 permute, 6 vcat, 7 hcat), longest row of
+ * the result. */
+spasm_amd_dcsr *spasm_amd_dcsr_transpose(const spasm_amd_dcsr *A);                       /* m x n */
+spasm_amd_dcsr *spasm_amd_dcsr_permute(const spasm_amd_dcsr *A, const int *p, const int *qinv);
+spasm_amd_dcsr *spasm_amd_dcsr_vcat(int count, const spasm_amd_dcsr *const *D);          /* rows stacked */
+spasm_amd_dcsr *spasm_amd_dcsr_hcat(int count, const spasm_amd_dcsr *const *D);          /* side by side */
 /* one-shot forms on host matrices: upload, operate, download */
 struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B);
 struct spasm_csr *spasm_amd_csr_lincomb(i64 a, const struct spasm_csr *A, i64 b, const struct spasm_csr *B);

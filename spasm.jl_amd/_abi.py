@@ -260,6 +260,10 @@ SIGNATURES = {
     "spasm_amd_dcsr_submatrix": (C.c_void_p, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "spasm_amd_dcsr_equal": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "spasm_amd_dcsr_stats": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_dcsr_transpose": (C.c_void_p, [C.c_void_p]),
+    "spasm_amd_dcsr_permute": (C.c_void_p, [C.c_void_p, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_dcsr_vcat": (C.c_void_p, [C.c_int32, _P(C.c_void_p)]),
+    "spasm_amd_dcsr_hcat": (C.c_void_p, [C.c_int32, _P(C.c_void_p)]),
     "spasm_amd_csr_mul": (_P(CsrStruct), [_P(CsrStruct), _P(CsrStruct)]),
     "spasm_amd_csr_lincomb": (_P(CsrStruct), [C.c_int64, _P(CsrStruct), C.c_int64, _P(CsrStruct)]),
     "spasm_dense_forward_solve": (C.c_bool, [_P(CsrStruct), C.c_void_p, C.c_void_p, C.c_void_p]),

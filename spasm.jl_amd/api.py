@@ -535,7 +535,15 @@ class DeviceCSR:
     """An n x m matrix over GF(p) resident on the device (spasm_amd_dcsr_*; engine extension).  DeviceCSR(A) uploads the CSR A,
     which may be dropped afterwards.  D1 @ D2, D1 + D2, D1 - D2, -D, a * D, D * a (Python int), D[r0:r1, c0:c1] make new resident
     matrices in canonical form (columns ascending inside each row, no zero stored) without crossing the host; download() gives
-    a CSR; equals() compares as matrices; stats() describes the operation that made the matrix."""
+    a CSR; equals() compares as matrices; stats() describes the operation that made the matrix.
+
+    D.T / D.transpose(), D.permute(p, q) (what numpy's A[np.ix_(p, q)] gives; qinv= takes the inverse column map instead),
+    vcat(D1, D2, ..) / D1.vcat(D2, ..) (rows stacked) and hcat(D1, D2, ..) / D1.hcat(D2, ..) (side by side) move entries without
+    touching their values (spasm_amd_dcsr_transpose / _permute / _vcat / _hcat; csrc/reshape.hpp); the results are canonical too.
+    For these four, stats() reads: flops = entries = the entries moved; rows_tiny / rows_hash / rows_global = the rows whose
+    columns were put in order by the one-wave, the workgroup and the long-row path (0 where nothing had to be ordered: vcat,
+    hcat, a permutation of rows alone); chunks = 1; ms_size / ms_numeric / ms_compact = the count, move and order steps;
+    scratch_bytes = peak scratch; op = 4 transpose, 5 permute, 6 vcat, 7 hcat; max_bound = the longest row of the result."""
 
     STATS = ("flops", "entries", "rows_tiny", "rows_hash", "rows_global", "chunks", "ms_size", "ms_numeric", "ms_compact", "scratch_bytes", "op", "max_bound")
 
@@ -647,6 +655,78 @@ class DeviceCSR:
         if rc < 0:
             raise SpasmError(_abi.last_error() or "spasm_amd_dcsr_equal failed")
         return bool(rc)
+
+    def transpose(self):
+        """the transpose as a new resident matrix"""
+        return DeviceCSR._wrap(_abi.lib().spasm_amd_dcsr_transpose(self._need()), "spasm_amd_dcsr_transpose")
+
+    T = property(transpose)
+
+    def permute(self, p=None, q=None, *, qinv=None):
+        """Row i of the result is row p[i]; with q, column k of the result is column q[k] (numpy's A[np.ix_(p, q)]); with qinv,
+        an entry on column j lands on column qinv[j].  None is the identity."""
+        me = self._need()
+        if q is not None and qinv is not None:
+            raise ValueError("give q or qinv, not both")
+        n, m = self.shape
+        p = _permutation(p, n, "p")
+        if q is not None:
+            q = _permutation(q, m, "q")
+            qinv = np.empty(m, dtype=np.int32)
+            qinv[q] = np.arange(m, dtype=np.int32)
+        else:
+            qinv = _permutation(qinv, m, "qinv")
+        as_ptr = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
+        return DeviceCSR._wrap(_abi.lib().spasm_amd_dcsr_permute(me, as_ptr(p), as_ptr(qinv)), "spasm_amd_dcsr_permute")
+
+    def vcat(self, *others):
+        return vcat(self, *others)
+
+    def hcat(self, *others):
+        return hcat(self, *others)
+
+
+def _permutation(a, size, name):
+    """a as a contiguous int32 array after checking that it is a permutation of range(size); None stays None"""
+    if a is None:
+        return None
+    a = np.asarray(a)
+    if a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"{name} must be an array of integers")
+    if a.shape != (size,):
+        raise ValueError(f"{name} must have {size} entries, it has shape {a.shape}")
+    seen = np.zeros(size, dtype=bool)
+    if size and (a.min() < 0 or a.max() >= size):
+        raise ValueError(f"{name} is not a permutation: an index lies outside 0 .. {size - 1}")
+    seen[a] = True
+    if not seen.all():
+        raise ValueError(f"{name} is not a permutation: an index is repeated")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _cat(sym, axis, Ds):
+    if not Ds:
+        raise ValueError("at least one DeviceCSR is needed")
+    for D in Ds:
+        if not isinstance(D, DeviceCSR):
+            raise TypeError("a DeviceCSR expected")
+    hs = [D._need() for D in Ds]
+    for D in Ds[1:]:
+        if D.shape[axis] != Ds[0].shape[axis]:
+            raise ValueError(f"dimension mismatch: {Ds[0].shape} and {D.shape}")
+        _same_field(Ds[0], D)
+    arr = (C.c_void_p * len(hs))(*hs)
+    return DeviceCSR._wrap(getattr(_abi.lib(), sym)(len(hs), arr), sym)
+
+
+def vcat(*Ds):
+    """the resident matrices stacked, rows of the first on top (equal column counts), in one pass"""
+    return _cat("spasm_amd_dcsr_vcat", 1, Ds)
+
+
+def hcat(*Ds):
+    """the resident matrices side by side (equal row counts), in one pass"""
+    return _cat("spasm_amd_dcsr_hcat", 0, Ds)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "dense.hpp"
 #include "spmv.hpp"
 #include "spgemm.hpp"
+#include "reshape.hpp"
 #include "trsolve.hpp"
 #include "batch.hpp"
 #include "blocks.hpp"
@@ -20,6 +21,7 @@
 #include <cstring>
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_radix_sort.hpp>
+#include <rocprim/device/device_segmented_radix_sort.hpp>
 #include <vector>
 #include <memory>
 #include <stdexcept>
@@ -6017,6 +6019,282 @@ int dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B, const char *who
     return h ? 0 : 1;
 }
 
+// ---- transpose, permute, vcat, hcat (reshape.hpp) ----------------------------------------------------------------------------
+void rsh_launch_group(int cls, int nitems, const int *items, const i64d *Rp, int2 *ent, hipStream_t s)
+{
+    const size_t lds = (size_t)(cls == 2 ? 512 : (cls == 3 ? 2048 : RSH_GROUP_MAX)) * sizeof(int2);
+    static bool attr_done[kMaxDev] = {false};
+    bool &done = attr_done[current_device()];
+    if (!done) {
+        HIPCHK(hipFuncSetAttribute((const void *)k_rsh_sort_group, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)RSH_GROUP_MAX * sizeof(int2))));
+        done = true;
+    }
+    hipLaunchKernelGGL(k_rsh_sort_group, dim3(nitems), dim3(256), lds, s, nitems, items, Rp, ent);
+    HIPCHK(hipGetLastError());
+}
+
+// the long rows of the list: gathered back to back in batches, sorted by column as 64-bit words {column, value} on their low half,
+// copied back.  Returns the bytes of scratch it took.
+size_t rsh_sort_long(int nlong, const int *items, const i64d *Rp, int2 *ent, hipStream_t s)
+{
+    DevBuf<i64d> dlen;
+    dlen.alloc((size_t)nlong);
+    hipLaunchKernelGGL(k_rsh_long_lens, dim3(cdiv(nlong, 256)), dim3(256), 0, s, nlong, items, Rp, dlen.p);
+    HIPCHK(hipGetLastError());
+    std::vector<i64d> hlen((size_t)nlong);
+    HIPCHK(hipMemcpyAsync(hlen.data(), dlen.p, (size_t)nlong * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    const i64d batch_cap = (i64d)1 << 28;  // entries per batch (a row above it goes alone; a row holds below 2^31 entries)
+    DevBuf<int2> in, out;
+    DevBuf<unsigned> coff;
+    DevBuf<unsigned char> tmp;
+    std::vector<unsigned> hoff;
+    size_t peak = 0;
+    int lo = 0;
+    while (lo < nlong) {
+        int hi = lo;
+        i64d total = 0;
+        while (hi < nlong && (hi == lo || total + hlen[(size_t)hi] <= batch_cap)) total += hlen[(size_t)hi++];
+        const int nb = hi - lo;
+        hoff.assign((size_t)nb + 1, 0u);
+        for (int t = 0; t < nb; t++) hoff[(size_t)t + 1] = hoff[(size_t)t] + (unsigned)hlen[(size_t)(lo + t)];
+        in.ensure((size_t)total);
+        out.ensure((size_t)total);
+        coff.ensure((size_t)nb + 1);
+        HIPCHK(hipMemcpyAsync(coff.p, hoff.data(), ((size_t)nb + 1) * sizeof(unsigned), hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(k_rsh_long_copy, dim3(nb), dim3(256), 0, s, 0, items + lo, Rp, coff.p, ent, in.p);
+        HIPCHK(hipGetLastError());
+        size_t bytes = 0;
+        HIPCHK(rocprim::segmented_radix_sort_keys(nullptr, bytes, (unsigned long long *)in.p, (unsigned long long *)out.p, (unsigned)total, (unsigned)nb, coff.p,
+                                                  coff.p + 1, 0, 32, s));
+        tmp.ensure(bytes);
+        HIPCHK(rocprim::segmented_radix_sort_keys(tmp.p, bytes, (unsigned long long *)in.p, (unsigned long long *)out.p, (unsigned)total, (unsigned)nb, coff.p,
+                                                  coff.p + 1, 0, 32, s));
+        hipLaunchKernelGGL(k_rsh_long_copy, dim3(nb), dim3(256), 0, s, 1, items + lo, Rp, coff.p, ent, out.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));  // (hoff is reused by the next batch)
+        peak = std::max(peak, (in.n + out.n) * sizeof(int2) + tmp.n + coff.n * sizeof(unsigned) + dlen.n * sizeof(i64d));
+        lo = hi;
+    }
+    return peak;
+}
+
+// R = op(D[0 .. count - 1]): the driver of the three steps of reshape.hpp.  The operands are canonical, on one device, over one
+// prime, and their shapes fit (checked by the callers below); p and qinv are HOST arrays that have been checked, or null.
+std::unique_ptr<spasm_amd_dcsr> rsh_run(int op, int count, const spasm_amd_dcsr *const *D, const int *p, const int *qinv)
+{
+    hipStream_t s = nullptr;
+    const spasm_amd_dcsr &A = *D[0];
+    std::unique_ptr<spasm_amd_dcsr> R(new spasm_amd_dcsr());
+    R->dev = A.dev;
+    R->F = A.F;
+    R->canonical = true;
+    std::vector<RshOperand> hops((size_t)count);
+    i64 n = 0, m = 0, nnz = 0;
+    for (int k = 0; k < count; k++) {
+        hops[(size_t)k].p = D[k]->p.p;
+        hops[(size_t)k].ent = D[k]->ent.p;
+        hops[(size_t)k].n = D[k]->n;
+        hops[(size_t)k].off = op == RSH_VCAT ? (int)n : (op == RSH_HCAT ? (int)m : 0);
+        nnz += D[k]->nnz;
+        if (op == RSH_VCAT) n += D[k]->n;
+        if (op == RSH_HCAT) m += D[k]->m;
+    }
+    if (op == RSH_TRANSPOSE) { n = A.m; m = A.n; }
+    if (op == RSH_PERMUTE) { n = A.n; m = A.m; }
+    if (op == RSH_VCAT) m = A.m;
+    if (op == RSH_HCAT) n = A.n;
+    R->n = (int)n;
+    R->m = (int)m;
+    R->nnz = nnz;
+    R->stats[10] = op;
+    R->stats[5] = 1;
+    const size_t n1 = (size_t)n + 1;
+    R->p.alloc(n1);
+    R->ent.alloc((size_t)nnz + 1);
+    if (nnz == 0) {
+        HIPCHK(hipMemsetAsync(R->p.p, 0, n1 * sizeof(i64d), s));
+        HIPCHK(hipStreamSynchronize(s));
+        return R;
+    }
+    SpgEvents ev;
+    Scanner scan;
+    DevBuf<RshOperand> ops;
+    DevBuf<i64d> len;
+    DevBuf<int> rowmap, colmap;
+    ops.alloc((size_t)count);
+    len.alloc(n1);
+    HIPCHK(hipMemcpyAsync(ops.p, hops.data(), (size_t)count * sizeof(RshOperand), hipMemcpyHostToDevice, s));
+    if (p) {
+        rowmap.alloc((size_t)A.n);
+        HIPCHK(hipMemcpyAsync(rowmap.p, p, (size_t)A.n * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    if (qinv) {
+        colmap.alloc((size_t)A.m);
+        HIPCHK(hipMemcpyAsync(colmap.p, qinv, (size_t)A.m * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    len.zero(s);
+    RshArgs a;
+    memset(&a, 0, sizeof a);
+    a.op = op;
+    a.nitems = op == RSH_TRANSPOSE ? A.n : (int)n;
+    a.count = count;
+    a.ops = ops.p;
+    a.rowmap = p ? rowmap.p : nullptr;
+    a.colmap = qinv ? colmap.p : nullptr;
+    a.Rp = R->p.p;
+    a.out = R->ent.p;
+    a.cursor = (unsigned long long *)len.p;
+    size_t peak = ops.n * sizeof(RshOperand) + len.n * sizeof(i64d) + (rowmap.n + colmap.n) * sizeof(int);
+    // ---- count
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    if (op == RSH_TRANSPOSE) hipLaunchKernelGGL(k_rsh_hist, dim3((int)std::min<i64>(cdiv(nnz, 256), 65536)), dim3(256), 0, s, (i64d)nnz, A.ent.p, (unsigned long long *)len.p);
+    else hipLaunchKernelGGL(k_rsh_lens, dim3(cdiv(n, 256)), dim3(256), 0, s, a, (int)n, len.p);
+    HIPCHK(hipGetLastError());
+    scan.exclusive(len.p, R->p.p, n1, s);  // (len[n] is 0)
+    // ---- move
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    if (op == RSH_TRANSPOSE) len.zero(s);  // the counts become the cursors
+    if (nnz <= 16 * (i64)a.nitems) hipLaunchKernelGGL((k_rsh_move<8>), dim3(cdiv((i64)a.nitems * 8, 256)), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL((k_rsh_move<64>), dim3(cdiv((i64)a.nitems * 64, 256)), dim3(256), 0, s, a);
+    HIPCHK(hipGetLastError());
+    // ---- order
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    DevBuf<unsigned char> key, key2, sort_tmp;
+    DevBuf<int> rowid, rowid2, hist;
+    DevBuf<i64d> maxl;
+    hist.alloc(16);
+    maxl.alloc(1);
+    hist.zero(s);
+    maxl.zero(s);
+    key.alloc((size_t)n);
+    rowid.alloc((size_t)n);
+    hipLaunchKernelGGL(k_rsh_classify, dim3(cdiv(n, 256)), dim3(256), 0, s, (int)n, R->p.p, key.p, rowid.p, hist.p, maxl.p);
+    HIPCHK(hipGetLastError());
+    i64 rows_path[3] = {0, 0, 0};
+    if (op == RSH_TRANSPOSE || (op == RSH_PERMUTE && qinv)) {
+        key2.alloc((size_t)n);
+        rowid2.alloc((size_t)n);
+        size_t bytes = 0;
+        HIPCHK(rocprim::radix_sort_pairs(nullptr, bytes, key.p, key2.p, rowid.p, rowid2.p, (size_t)n, 0, 4, s));
+        sort_tmp.ensure(bytes);
+        HIPCHK(rocprim::radix_sort_pairs(sort_tmp.p, bytes, key.p, key2.p, rowid.p, rowid2.p, (size_t)n, 0, 4, s));
+        int h[16];
+        HIPCHK(hipMemcpyAsync(h, hist.p, sizeof h, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        peak += (key2.n + key.n) + (rowid.n + rowid2.n) * sizeof(int) + sort_tmp.n;
+        int first = h[0];
+        if (h[1] > 0) {
+            hipLaunchKernelGGL(k_rsh_sort_wave, dim3(cdiv(h[1], 4)), dim3(256), 0, s, h[1], rowid2.p + first, R->p.p, R->ent.p);
+            HIPCHK(hipGetLastError());
+            rows_path[0] = h[1];
+        }
+        first += h[1];
+        for (int cls = 2; cls < RSH_CLS_LONG; cls++) {
+            if (h[cls] > 0) rsh_launch_group(cls, h[cls], rowid2.p + first, R->p.p, R->ent.p, s);
+            rows_path[1] += h[cls];
+            first += h[cls];
+        }
+        if (h[RSH_CLS_LONG] > 0) {
+            peak += rsh_sort_long(h[RSH_CLS_LONG], rowid2.p + first, R->p.p, R->ent.p, s);
+            rows_path[2] = h[RSH_CLS_LONG];
+        }
+    }
+    HIPCHK(hipEventRecord(ev.e[3], s));
+    i64d hmax = 0;
+    HIPCHK(hipMemcpyAsync(&hmax, maxl.p, sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = R->stats;
+    st[0] = nnz;
+    st[1] = nnz;
+    st[2] = rows_path[0];
+    st[3] = rows_path[1];
+    st[4] = rows_path[2];
+    st[6] = (i64)(ev.ms(0, 1) * 1000.0);
+    st[7] = (i64)(ev.ms(1, 2) * 1000.0);
+    st[8] = (i64)(ev.ms(2, 3) * 1000.0);
+    st[9] = (i64)peak;
+    st[11] = hmax;
+    return R;
+}
+
+// the operands of a structural operation: not NULL, on one device, over one prime; what is not canonical yet is brought to
+// canonical form (own[] keeps those copies alive)
+void rsh_operands(int count, const spasm_amd_dcsr *const *D, std::vector<const spasm_amd_dcsr *> &use, std::vector<std::unique_ptr<spasm_amd_dcsr>> &own, const char *who)
+{
+    const std::string w(who);
+    if (count < 1) throw EngineError(w + ": at least one matrix is needed");
+    if (!D) throw EngineError(w + ": NULL list of matrices");
+    for (int k = 0; k < count; k++) {
+        dcsr_need(D[k], who);
+        if (D[k]->F.p != D[0]->F.p) throw EngineError(w + ": the matrices are over different primes");
+        if (D[k]->dev != D[0]->dev) throw EngineError(w + ": the matrices live on different devices");
+    }
+    use.assign(D, D + count);
+    for (int k = 0; k < count; k++)
+        if (!use[(size_t)k]->canonical) {
+            own.emplace_back(dcsr_lincomb(1, use[(size_t)k], 0, nullptr, who));
+            use[(size_t)k] = own.back().get();
+        }
+}
+
+// host check, O(len): map is a bijection of 0 .. len - 1
+void rsh_check_permutation(const int *map, int len, const char *name, const char *who)
+{
+    if (!map) return;
+    std::vector<unsigned char> seen((size_t)len, 0);
+    for (int i = 0; i < len; i++) {
+        const int v = map[i];
+        if (v < 0 || v >= len || seen[(size_t)v]) {
+            char b[160];
+            snprintf(b, sizeof b, "%s: %s is not a permutation (%s[%d] = %d is %s)", who, name, name, i, v, (v < 0 || v >= len) ? "out of range" : "repeated");
+            throw EngineError(b);
+        }
+        seen[(size_t)v] = 1;
+    }
+}
+
+spasm_amd_dcsr *dcsr_transpose(const spasm_amd_dcsr *A, const char *who)
+{
+    require_device();
+    std::vector<const spasm_amd_dcsr *> use;
+    std::vector<std::unique_ptr<spasm_amd_dcsr>> own;
+    rsh_operands(1, &A, use, own, who);
+    return rsh_run(RSH_TRANSPOSE, 1, use.data(), nullptr, nullptr).release();
+}
+
+spasm_amd_dcsr *dcsr_permute(const spasm_amd_dcsr *A, const int *p, const int *qinv, const char *who)
+{
+    require_device();
+    dcsr_need(A, who);
+    rsh_check_permutation(p, A->n, "p", who);
+    rsh_check_permutation(qinv, A->m, "qinv", who);
+    std::vector<const spasm_amd_dcsr *> use;
+    std::vector<std::unique_ptr<spasm_amd_dcsr>> own;
+    rsh_operands(1, &A, use, own, who);
+    return rsh_run(RSH_PERMUTE, 1, use.data(), p, qinv).release();
+}
+
+spasm_amd_dcsr *dcsr_cat(int op, int count, const spasm_amd_dcsr *const *D, const char *who)
+{
+    require_device();
+    std::vector<const spasm_amd_dcsr *> use;
+    std::vector<std::unique_ptr<spasm_amd_dcsr>> own;
+    const std::string w(who);
+    if (count < 1) throw EngineError(w + ": at least one matrix is needed");
+    if (!D) throw EngineError(w + ": NULL list of matrices");
+    i64 total = 0;
+    for (int k = 0; k < count; k++) {
+        dcsr_need(D[k], who);
+        if (op == RSH_VCAT && D[k]->m != D[0]->m) throw EngineError(w + ": dimension mismatch (the matrices must have the same number of columns)");
+        if (op == RSH_HCAT && D[k]->n != D[0]->n) throw EngineError(w + ": dimension mismatch (the matrices must have the same number of rows)");
+        total += op == RSH_VCAT ? D[k]->n : D[k]->m;
+    }
+    if (total > 0x7fffffff) throw EngineError(w + (op == RSH_VCAT ? ": more than INT_MAX rows in all" : ": more than INT_MAX columns in all"));
+    rsh_operands(count, D, use, own, who);
+    return rsh_run(op, count, use.data(), nullptr, nullptr).release();
+}
+
 struct spasm_csr *csr_mul_once(const struct spasm_csr *A, const struct spasm_csr *B)
 {
     require_device();
@@ -9377,6 +9655,23 @@ SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_submatrix(const spasm_amd_dcsr *A, int 
 SPASM_API int spasm_amd_dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B)
 {
     DCSR_TRY("spasm_amd_dcsr_equal", DCSR_ON(A) return dcsr_equal(A, B, "comparison");, -1)
+}
+// transpose, permutation, concatenation of resident matrices (reshape.hpp)
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_transpose(const spasm_amd_dcsr *A)
+{
+    DCSR_TRY("spasm_amd_dcsr_transpose", DCSR_ON(A) return dcsr_transpose(A, "transpose");, nullptr)
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_permute(const spasm_amd_dcsr *A, const int *p, const int *qinv)
+{
+    DCSR_TRY("spasm_amd_dcsr_permute", DCSR_ON(A) return dcsr_permute(A, p, qinv, "permutation");, nullptr)
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_vcat(int count, const spasm_amd_dcsr *const *D)
+{
+    DCSR_TRY("spasm_amd_dcsr_vcat", DCSR_ON((count > 0 && D) ? D[0] : nullptr) return dcsr_cat(RSH_VCAT, count, D, "vcat");, nullptr)
+}
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_hcat(int count, const spasm_amd_dcsr *const *D)
+{
+    DCSR_TRY("spasm_amd_dcsr_hcat", DCSR_ON((count > 0 && D) ? D[0] : nullptr) return dcsr_cat(RSH_HCAT, count, D, "hcat");, nullptr)
 }
 // one-shot forms on host matrices: upload, operate, download
 SPASM_API struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B) { DCSR_TRY("spasm_amd_csr_mul", return csr_mul_once(A, B);, nullptr) }
