@@ -90,6 +90,47 @@ template <class T> struct DevBuf {
     void zero(hipStream_t s) { if (p) HIPCHK(hipMemsetAsync(p, 0, n * sizeof(T), s)); }
 };
 
+// the calling thread's device, put back on scope exit; given a handle, that handle's device is selected in between
+struct DeviceGuard {
+    int prev = 0;
+    DeviceGuard() { (void)hipGetDevice(&prev); }
+    template <class H> explicit DeviceGuard(const H *h) : DeviceGuard() { if (h) HIPCHK(hipSetDevice(h->dev)); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    ~DeviceGuard() { (void)hipSetDevice(prev); }
+};
+
+// a handle that lives on a device is destroyed on that device
+template <class H> void handle_free(H *h)
+{
+    if (!h) return;
+    DeviceGuard g;
+    (void)hipSetDevice(h->dev);
+    delete h;
+}
+
+// The one error guard of the C ABI: every exported function that can fail is `return abi_call(name, failure value, [&] { body });`.
+// The thread's error text is cleared, the body runs, and a std::exception becomes the text "<who>: <what>" and the entry's failure
+// value.  ABI_NAMED_BELOW: the functions below put the entry's name in front of most of their messages themselves (the triangular
+// solves), so a <what> that begins with <who> is the text as it is.
+enum AbiText { ABI_PREFIX, ABI_NAMED_BELOW };
+
+template <class R, class F> R abi_call(const char *who, R fail, F &&body, AbiText text = ABI_PREFIX)
+{
+    spasm_clear_error();
+    try {
+        return body();
+    } catch (const std::exception &e) {
+        if (text == ABI_NAMED_BELOW && strncmp(e.what(), who, strlen(who)) == 0) spasm_set_error("%s", e.what());
+        else spasm_set_error("%s: %s", who, e.what());
+        return fail;
+    }
+}
+
+template <class F> void abi_call(const char *who, F &&body)
+{
+    (void)abi_call(who, 0, [&] { body(); return 0; });
+}
+
 inline int cdiv(i64 a, i64 b) { return (int)((a + b - 1) / b); }
 
 // device matrix: rows are slices (start,len) of ent; lead = leftmost column; orig = row of the input matrix
@@ -4816,12 +4857,6 @@ struct spasm_csr *plan_fetch(spasm_amd_schur_plan *P, int *p_out)
 // the number of shards.  When little is left, or the remainder is dense enough for the dense finish, the rows are gathered and
 // the single-device engine finishes them on device 0.
 // ------------------------------------------------------------------------------------------------
-struct DeviceGuard {
-    int prev = 0;
-    DeviceGuard() { (void)hipGetDevice(&prev); }
-    ~DeviceGuard() { (void)hipSetDevice(prev); }
-};
-
 struct spasm_lu *do_echelonize_multi(const struct spasm_csr *A, struct echelonize_opts *opts, int nshards)
 {
     struct echelonize_opts dflt;
@@ -5333,6 +5368,17 @@ struct spasm_amd_dshard {
 };
 
 namespace {
+
+// (a step called out of order -- no handle, or before dshard_build -- is an error, not a crash)
+void dshard_built(const spasm_amd_dshard *ds)
+{
+    if (!ds || !ds->impl) throw EngineError("no dense shard (spasm_amd_dshard_open / _density / _build come first)");
+}
+
+void dshard_opened(const spasm_amd_dshard *ds)
+{
+    if (!ds || (!ds->dw && !ds->fl)) throw EngineError("no dense shard (spasm_amd_dshard_open comes first)");
+}
 
 spasm_amd_dshard *dshard_open(spasm_amd_schur_plan *P, int me, int nshards)
 {
@@ -6770,28 +6816,16 @@ void trsolve_check(const spasm_amd_trsolve *op, int k, const void *B, i64 ldb, c
     if (k > 0 && ((op->m > 0 && !B) || (op->n > 0 && !X) || !ok)) throw EngineError(std::string(who) + ": NULL array");
 }
 
-// the error text names the entry point once
-void trsolve_error(const char *who, const std::exception &e)
-{
-    const size_t l = strlen(who);
-    if (strncmp(e.what(), who, l) == 0) spasm_set_error("%s", e.what());
-    else spasm_set_error("%s: %s", who, e.what());
-}
-
-// spasm_dense_forward_solve / spasm_dense_back_solve: a temporary operator, one right-hand side
+// spasm_dense_forward_solve / spasm_dense_back_solve (`who`): a temporary operator, one right-hand side
 bool trsolve_once(const struct spasm_csr *T, spasm_ZZp *b, spasm_ZZp *x, const int *piv, int kind, const char *who)
 {
-    spasm_clear_error();
-    try {
+    return abi_call(who, false, [&] {
         std::unique_ptr<spasm_amd_trsolve> op(trsolve_create(T, piv, kind, who));
         unsigned char ok = 0;
         trsolve_check(op.get(), 1, b, 1, x, 1, &ok, who);
         op->apply_host(1, b, 1, x, 1, &ok);
         return ok != 0;
-    } catch (const std::exception &e) {
-        trsolve_error(who, e);
-        return false;
-    }
+    }, ABI_NAMED_BELOW);
 }
 
 } // namespace
@@ -8902,7 +8936,7 @@ void solver_apply_dense_host(spasm_amd_solver *S, int K, const int *B, i64 ldb, 
 } // namespace
 
 // ================================================================================================
-// C ABI
+// C ABI: every entry point that can fail is one abi_call (above, beside HIPCHK)
 // ================================================================================================
 
 extern "C" {
@@ -8924,32 +8958,19 @@ SPASM_API int spasm_amd_set_device(int dev)
 // this process (include/spasm_amd.h)
 SPASM_API struct spasm_lu *spasm_amd_echelonize_multi(const struct spasm_csr *A, struct echelonize_opts *opts, int nshards)
 {
-    spasm_clear_error();
-    try {
-        return do_echelonize_multi(A, opts, nshards);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_echelonize_multi: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_lu *>("spasm_amd_echelonize_multi", nullptr, [&] { return do_echelonize_multi(A, opts, nshards); });
 }
 
 // reference src/SpaSM.jl:863
 SPASM_API struct spasm_lu *spasm_echelonize(const struct spasm_csr *A, struct echelonize_opts *opts)
 {
-    spasm_clear_error();
-    try {
-        return do_echelonize(A, opts);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_echelonize: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_lu *>("spasm_echelonize", nullptr, [&] { return do_echelonize(A, opts); });
 }
 
 // rank(A) = rank(echelonize(A)) (reference src/SpaSM.jl:1149) without the rows of U ever leaving the device; -1 on error
 SPASM_API i64 spasm_amd_rank(const struct spasm_csr *A, struct echelonize_opts *opts)
 {
-    spasm_clear_error();
-    try {
+    return abi_call<i64>("spasm_amd_rank", -1, [&] {
         struct echelonize_opts o;
         if (opts) o = *opts;
         else spasm_echelonize_init_opts(&o);
@@ -8957,33 +8978,18 @@ SPASM_API i64 spasm_amd_rank(const struct spasm_csr *A, struct echelonize_opts *
         i64 r = -1;
         (void)do_echelonize(A, &o, &r);
         return r;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_rank: %s", e.what());
-        return -1;
-    }
+    });
 }
 
 // reference src/SpaSM.jl:879
 SPASM_API struct spasm_csr *spasm_kernel(const struct spasm_lu *fact)
 {
-    spasm_clear_error();
-    try {
-        return do_kernel(fact);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_kernel: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_kernel", nullptr, [&] { return do_kernel(fact); });
 }
 
 SPASM_API struct spasm_csr *spasm_amd_kernel_strided(const struct spasm_lu *fact, int first, int step)
 {
-    spasm_clear_error();
-    try {
-        return do_kernel(fact, first, step);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_kernel_strided: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_amd_kernel_strided", nullptr, [&] { return do_kernel(fact, first, step); });
 }
 
 // reference src/SpaSM.jl:694-722: x * U = B[k] for ONE row.  The row goes through the batched device solve (do_trisolve: the Schur
@@ -8993,22 +8999,21 @@ SPASM_API struct spasm_csr *spasm_amd_kernel_strided(const struct spasm_lu *fact
 // DFS stacks and marks, "it remains OK", :700) are left as they are.  -1 on failure.
 SPASM_API int spasm_sparse_triangular_solve(const struct spasm_csr *U, const struct spasm_csr *B, int k, int *xj, spasm_ZZp *x, const int *qinv)
 {
-    spasm_clear_error();
-    struct spasm_csr *X = nullptr, *Rs = nullptr;
-    struct spasm_csr one;
-    try {
+    return abi_call("spasm_sparse_triangular_solve", -1, [&] {
         if (!U || !B || !xj || !x || !qinv) throw EngineError("spasm_sparse_triangular_solve: null argument");
         if (k < 0 || k >= B->n) throw EngineError("spasm_sparse_triangular_solve: row out of range");
         const int m = U->m;
         // row k of B as a matrix of its own (borrowed arrays)
         i64 rp[2] = {0, B->p[k + 1] - B->p[k]};
-        one = *B;
+        struct spasm_csr one = *B;
         one.n = 1;
         one.nzmax = rp[1];
         one.p = rp;
         one.j = B->j + B->p[k];
         one.x = B->x + B->p[k];
-        X = do_trisolve(U, qinv, &one, nullptr, &Rs);
+        struct spasm_csr *resid = nullptr; // (set by do_trisolve as its last step)
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> X(do_trisolve(U, qinv, &one, nullptr, &resid), spasm_csr_free);
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Rs(resid, spasm_csr_free);
         std::vector<int> colof((size_t)std::max(U->n, 1), -1);
         for (int j = 0; j < m; j++) if (qinv[j] >= 0 && qinv[j] < U->n) colof[(size_t)qinv[j]] = j;
         std::vector<int> pat;
@@ -9019,39 +9024,20 @@ SPASM_API int spasm_sparse_triangular_solve(const struct spasm_csr *U, const str
         std::sort(pat.begin() + (long)npiv_pat, pat.end());
         const int top = m - (int)pat.size();
         for (size_t t = 0; t < pat.size(); t++) xj[(size_t)top + t] = pat[t];
-        spasm_csr_free(X);
-        spasm_csr_free(Rs);
         return top;
-    } catch (const std::exception &e) {
-        if (X) spasm_csr_free(X);
-        if (Rs) spasm_csr_free(Rs);
-        spasm_set_error("%s", e.what());
-        return -1;
-    }
+    }, ABI_NAMED_BELOW);
 }
 
 SPASM_API struct spasm_csr *spasm_amd_triangular_solve(const struct spasm_csr *U, const int *qinv, const struct spasm_csr *B, unsigned char *ok)
 {
-    spasm_clear_error();
-    try {
-        return do_trisolve(U, qinv, B, ok);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_triangular_solve: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_amd_triangular_solve", nullptr, [&] { return do_trisolve(U, qinv, B, ok); });
 }
 
 // reference src/SpaSM.jl:915-923
 SPASM_API struct spasm_csr *spasm_gesv(const struct spasm_lu *fact, const struct spasm_csr *B, bool *ok)
 {
-    spasm_clear_error();
-    try {
-        static_assert(sizeof(bool) == 1, "ok is an array of bytes");
-        return do_gesv(fact, B, (unsigned char *)ok);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_gesv: %s", e.what());
-        return nullptr;
-    }
+    static_assert(sizeof(bool) == 1, "ok is an array of bytes");
+    return abi_call<struct spasm_csr *>("spasm_gesv", nullptr, [&] { return do_gesv(fact, B, (unsigned char *)ok); });
 }
 
 // reference src/SpaSM.jl:895-905: x (n = rows of A entries) with x * A == b (m entries); false when there is no solution
@@ -9060,16 +9046,16 @@ SPASM_API struct spasm_csr *spasm_gesv(const struct spasm_lu *fact, const struct
 // echelonized with L, then the two triangular solves of spasm_solve).  NULL on failure (e.g. when U is not of full rank r on A).
 SPASM_API struct spasm_rank_certificate *spasm_certificate_rank_create(const struct spasm_csr *A, const uint8_t *hash, const struct spasm_lu *fact)
 {
-    spasm_clear_error();
-    struct spasm_rank_certificate *P = nullptr;
-    struct spasm_csr *Cm = nullptr;
-    struct spasm_lu *fc = nullptr;
-    try {
+    return abi_call<struct spasm_rank_certificate *>("spasm_certificate_rank_create", nullptr, [&] {
+        // (the temporaries are freed while the exception unwinds, so the error text is set after spasm_solve and the frees)
+        std::unique_ptr<struct spasm_rank_certificate, void (*)(struct spasm_rank_certificate *)> P(nullptr, spasm_rank_certificate_free);
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> Cm(nullptr, spasm_csr_free);
+        std::unique_ptr<struct spasm_lu, void (*)(struct spasm_lu *)> fc(nullptr, spasm_lu_free);
         if (!A || !hash || !fact || !fact->U || !fact->qinv || !fact->p) throw EngineError("null argument");
         const int r = fact->r, n = A->n, m = A->m;
         const i64 prime = A->field->p;
         if (fact->U->m != m || r > n || r > m) throw EngineError("the factorization does not belong to this matrix");
-        P = (struct spasm_rank_certificate *)calloc(1, sizeof *P);
+        P.reset((struct spasm_rank_certificate *)calloc(1, sizeof *P));
         if (!P) throw EngineError("out of host memory");
         P->r = r;
         P->prime = prime;
@@ -9092,9 +9078,9 @@ SPASM_API struct spasm_rank_certificate *spasm_certificate_rank_create(const str
             for (i64 t = A->p[i]; t < A->p[i + 1]; t++) cz += pos[(size_t)A->j[t]] >= 0;
         }
         spasm_cert_challenge(hash, prime, r, P->i, P->j, P->x);
-        if (r == 0) return P;
+        if (r == 0) return P.release();
         // C = A[rows, columns], r x r
-        Cm = spasm_csr_alloc(r, r, cz, prime, true);
+        Cm.reset(spasm_csr_alloc(r, r, cz, prime, true));
         if (!Cm) throw EngineError("out of host memory");
         i64 w = 0;
         for (int k = 0; k < r; k++) {
@@ -9110,26 +9096,16 @@ SPASM_API struct spasm_rank_certificate *spasm_certificate_rank_create(const str
         spasm_echelonize_init_opts(&o);
         o.L = true;
         o.enable_greedy_pivot_search = false;
-        fc = do_echelonize(Cm, &o);
+        fc.reset(do_echelonize(Cm.get(), &o));
         if (!fc || fc->r != r) throw EngineError("the pivotal rows and pivot columns do not span a non-singular submatrix");
-        if (!spasm_solve(fc, P->x, P->y)) throw EngineError("the challenge has no solution (singular submatrix)");
-        spasm_lu_free(fc);
-        spasm_csr_free(Cm);
-        return P;
-    } catch (const std::exception &e) {
-        std::string msg = e.what(); // (spasm_solve / spasm_lu_free below reset the error text)
-        if (fc) spasm_lu_free(fc);
-        if (Cm) spasm_csr_free(Cm);
-        spasm_rank_certificate_free(P);
-        spasm_set_error("spasm_certificate_rank_create: %s", msg.c_str());
-        return nullptr;
-    }
+        if (!spasm_solve(fc.get(), P->x, P->y)) throw EngineError("the challenge has no solution (singular submatrix)");
+        return P.release();
+    });
 }
 
 SPASM_API bool spasm_solve(const struct spasm_lu *fact, const spasm_ZZp *b, spasm_ZZp *x)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_solve", false, [&] {
         if (!fact || !fact->U || !fact->L || !b || !x) throw EngineError("null argument (a factorization with L is needed)");
         const int m = fact->U->m, n = fact->L->n;
         const i64 prime = fact->U->field->p;
@@ -9152,77 +9128,38 @@ SPASM_API bool spasm_solve(const struct spasm_lu *fact, const spasm_ZZp *b, spas
         for (i64 q = X->p[0]; q < X->p[1]; q++) x[X->j[q]] = X->x[q];
         spasm_csr_free(X);
         return ok != 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_solve: %s", e.what());
-        return false;
-    }
+    });
 }
 
 SPASM_API struct spasm_csr *spasm_rref(const struct spasm_lu *fact, int *Rqinv)
 {
-    spasm_clear_error();
-    try {
-        return do_rref(fact, Rqinv);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_rref: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_rref", nullptr, [&] { return do_rref(fact, Rqinv); });
 }
 
 // reference src/SpaSM.jl:589
 SPASM_API struct spasm_csr *spasm_transpose(const struct spasm_csr *A)
 {
-    spasm_clear_error();
-    try {
-        return do_transpose(A);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_transpose: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_transpose", nullptr, [&] { return do_transpose(A); });
 }
 
 SPASM_API spasm_amd_schur_plan *spasm_amd_schur_plan_create(const struct spasm_csr *A, int row_lo, int row_hi)
 {
-    spasm_clear_error();
-    try {
-        return plan_create(A, row_lo, row_hi);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_create: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_schur_plan *>("spasm_amd_schur_plan_create", nullptr, [&] { return plan_create(A, row_lo, row_hi); });
 }
 
 SPASM_API spasm_amd_schur_plan *spasm_amd_schur_plan_create_strided(const struct spasm_csr *A, int row_lo, int row_hi, int stride)
 {
-    spasm_clear_error();
-    try {
-        return plan_create(A, row_lo, row_hi, stride);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_create_strided: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_schur_plan *>("spasm_amd_schur_plan_create_strided", nullptr, [&] { return plan_create(A, row_lo, row_hi, stride); });
 }
 
 SPASM_API spasm_amd_shard *spasm_amd_shard_create_strided(const struct spasm_csr *A, int row_lo, int row_hi, int stride)
 {
-    spasm_clear_error();
-    try {
-        return shard_create(A, row_lo, row_hi, stride);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_create_strided: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_shard *>("spasm_amd_shard_create_strided", nullptr, [&] { return shard_create(A, row_lo, row_hi, stride); });
 }
 
 SPASM_API int spasm_amd_schur_plan_run(spasm_amd_schur_plan *plan, void *stream)
 {
-    try {
-        plan_run(plan, (hipStream_t)stream);
-        return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_run: %s", e.what());
-        return 1;
-    }
+    return abi_call("spasm_amd_schur_plan_run", 1, [&] { plan_run(plan, (hipStream_t)stream); return 0; });
 }
 
 SPASM_API void spasm_amd_schur_plan_class_timing(spasm_amd_schur_plan *plan, int on)
@@ -9232,7 +9169,7 @@ SPASM_API void spasm_amd_schur_plan_class_timing(spasm_amd_schur_plan *plan, int
 
 SPASM_API int spasm_amd_schur_plan_stats(spasm_amd_schur_plan *plan, struct spasm_amd_round_stats *stats)
 {
-    try {
+    return abi_call("spasm_amd_schur_plan_stats", 1, [&] {
         if (!plan->ran) throw EngineError("run the plan first");
         plan->R.fetch_counters();
         plan->R.hctr.applications = plan->exact_applications;
@@ -9240,141 +9177,72 @@ SPASM_API int spasm_amd_schur_plan_stats(spasm_amd_schur_plan *plan, struct spas
         plan->R.hctr.segments = plan->exact_segments;
         fill_stats(*stats, plan->R, 0, plan->hi > plan->lo ? (plan->hi - plan->lo + plan->stride - 1) / plan->stride : 0, plan->nnz_in);
         return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_stats: %s", e.what());
-        return 1;
-    }
+    });
 }
 
 SPASM_API struct spasm_csr *spasm_amd_schur_plan_fetch(spasm_amd_schur_plan *plan, int *p_out)
 {
-    spasm_clear_error();
-    try {
-        return plan_fetch(plan, p_out);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_fetch: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_amd_schur_plan_fetch", nullptr, [&] { return plan_fetch(plan, p_out); });
 }
 
 SPASM_API struct spasm_csr *spasm_amd_schur_plan_fetch_U(spasm_amd_schur_plan *plan, int *pivcol_out, int *row_out)
 {
-    spasm_clear_error();
-    try {
+    return abi_call<struct spasm_csr *>("spasm_amd_schur_plan_fetch_U", nullptr, [&] {
         if (!plan) throw EngineError("null plan");
         return plan_fetch_U(plan, pivcol_out, row_out);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_fetch_U: %s", e.what());
-        return nullptr;
-    }
+    });
 }
 
 SPASM_API void spasm_amd_schur_plan_free(spasm_amd_schur_plan *plan) { delete plan; }
 
 SPASM_API spasm_amd_shard *spasm_amd_shard_create(const struct spasm_csr *A, int row_lo, int row_hi)
 {
-    spasm_clear_error();
-    try {
-        return shard_create(A, row_lo, row_hi);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_create: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_shard *>("spasm_amd_shard_create", nullptr, [&] { return shard_create(A, row_lo, row_hi); });
 }
 
 SPASM_API int spasm_amd_shard_elect(spasm_amd_shard *sh, int64_t *keys_dev)
 {
-    try {
-        shard_elect(sh, keys_dev);
-        return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_elect: %s", e.what());
-        return 1;
-    }
+    return abi_call("spasm_amd_shard_elect", 1, [&] { shard_elect(sh, keys_dev); return 0; });
 }
 
 SPASM_API int spasm_amd_shard_set_keys(spasm_amd_shard *sh, const int64_t *keys_dev, int *n_owned, i64 *nnz_owned)
 {
-    try {
-        return shard_set_keys(sh, keys_dev, n_owned, nnz_owned);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_set_keys: %s", e.what());
-        return -1;
-    }
+    return abi_call("spasm_amd_shard_set_keys", -1, [&] { return shard_set_keys(sh, keys_dev, n_owned, nnz_owned); });
 }
 
 SPASM_API int spasm_amd_shard_assign(spasm_amd_shard *sh, const int64_t *keys_dev)
 {
-    try {
-        return shard_assign(sh, keys_dev);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_assign: %s", e.what());
-        return -1;
-    }
+    return abi_call("spasm_amd_shard_assign", -1, [&] { return shard_assign(sh, keys_dev); });
 }
 
 SPASM_API int spasm_amd_shard_open_step(spasm_amd_shard *sh, int step, int pass, const void *in_dev, void *out_dev)
 {
-    try {
-        return shard_open_step(sh, step, pass, in_dev, out_dev);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_open_step: %s", e.what());
-        return -1;
-    }
+    return abi_call("spasm_amd_shard_open_step", -1, [&] { return shard_open_step(sh, step, pass, in_dev, out_dev); });
 }
 
 SPASM_API int spasm_amd_shard_finish_keys(spasm_amd_shard *sh, int *n_owned, i64 *nnz_owned)
 {
-    try {
-        return shard_finish_keys(sh, n_owned, nnz_owned);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_finish_keys: %s", e.what());
-        return -1;
-    }
+    return abi_call("spasm_amd_shard_finish_keys", -1, [&] { return shard_finish_keys(sh, n_owned, nnz_owned); });
 }
 
 SPASM_API int spasm_amd_shard_export(spasm_amd_shard *sh, int *hdr_dev, int *ent_dev)
 {
-    try {
-        shard_export(sh, hdr_dev, ent_dev);
-        return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_export: %s", e.what());
-        return 1;
-    }
+    return abi_call("spasm_amd_shard_export", 1, [&] { shard_export(sh, hdr_dev, ent_dev); return 0; });
 }
 
 SPASM_API spasm_amd_schur_plan *spasm_amd_shard_import(spasm_amd_shard *sh, int n_rows, i64 n_entries, const int *hdr_dev, const int *ent_dev)
 {
-    spasm_clear_error();
-    try {
-        return shard_import(sh, n_rows, n_entries, hdr_dev, ent_dev);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_import: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_schur_plan *>("spasm_amd_shard_import", nullptr, [&] { return shard_import(sh, n_rows, n_entries, hdr_dev, ent_dev); });
 }
 
 SPASM_API spasm_amd_shard *spasm_amd_schur_plan_advance(spasm_amd_schur_plan *plan, int *rows_out, i64 *nnz_out)
 {
-    spasm_clear_error();
-    try {
-        return plan_advance(plan, rows_out, nnz_out);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_schur_plan_advance: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_shard *>("spasm_amd_schur_plan_advance", nullptr, [&] { return plan_advance(plan, rows_out, nnz_out); });
 }
 
 SPASM_API struct spasm_csr *spasm_amd_shard_fetch(spasm_amd_shard *sh)
 {
-    spasm_clear_error();
-    try {
-        return shard_fetch(sh);
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_shard_fetch: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<struct spasm_csr *>("spasm_amd_shard_fetch", nullptr, [&] { return shard_fetch(sh); });
 }
 
 SPASM_API void spasm_amd_shard_free(spasm_amd_shard *sh)
@@ -9387,8 +9255,7 @@ SPASM_API void spasm_amd_shard_free(spasm_amd_shard *sh)
 // the device's field arithmetic on n test vectors (canonical residues a, b, c in; 8 results per vector out): see k_zp_probe
 SPASM_API int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, const int *c, int *out)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_zp_probe", 1, [&] {
         require_device();
         if (prime <= 2 || prime > 0xfffffffbLL || n < 0) throw EngineError("bad arguments");
         const ZpField F = zp_field_make(prime);
@@ -9406,17 +9273,13 @@ SPASM_API int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, c
         }
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_zp_probe: %s", e.what());
-        return 1;
-    }
+    });
 }
 
 // count[i] lazy products a[i] * b[i] summed and reduced as the kernels do it (one result per triple): see k_zp_sum_probe
 SPASM_API int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *b, const int *count, int *out)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_zp_sum_probe", 1, [&] {
         require_device();
         if (prime <= 2 || prime > 0xfffffffbLL || n < 0) throw EngineError("bad arguments");
         for (int i = 0; i < n; i++)
@@ -9436,189 +9299,174 @@ SPASM_API int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *
         }
         HIPCHK(hipStreamSynchronize(s));
         return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_zp_sum_probe: %s", e.what());
-        return 1;
-    }
+    });
 }
 
 SPASM_API int spasm_amd_multi_last_finish(void) { return g_multi_finish; }
 
-// ---- the dense finish over row shards, one process per shard (include/spasm_amd.h)
-#define DSHARD_TRY(name, body, fail)                                   \
-    spasm_clear_error();                                               \
-    try { body }                                                       \
-    catch (const std::exception &e) { spasm_set_error(name ": %s", e.what()); return fail; }
-// (a step called out of order -- no handle, or before dshard_build -- is an error, not a crash)
-#define DSHARD_BUILT(ds) do { if (!(ds) || !(ds)->impl) throw EngineError("no dense shard (spasm_amd_dshard_open / _density / _build come first)"); } while (0)
-#define DSHARD_OPEN(ds) do { if (!(ds) || (!(ds)->dw && !(ds)->fl)) throw EngineError("no dense shard (spasm_amd_dshard_open comes first)"); } while (0)
-
+// ---- the dense finish over row shards, one process per shard (include/spasm_amd.h); no entry here switches the device
 SPASM_API spasm_amd_schur_plan *spasm_amd_shard_import_U(spasm_amd_shard *sh, int n_rows, i64 n_entries, const int *hdr_dev, const int *ent_dev)
 {
-    DSHARD_TRY("spasm_amd_shard_import_U", return shard_import(sh, n_rows, n_entries, hdr_dev, ent_dev, false);, nullptr)
+    return abi_call<spasm_amd_schur_plan *>("spasm_amd_shard_import_U", nullptr, [&] { return shard_import(sh, n_rows, n_entries, hdr_dev, ent_dev, false); });
 }
 SPASM_API int spasm_amd_schur_plan_prepare(spasm_amd_schur_plan *plan)
 {
-    DSHARD_TRY("spasm_amd_schur_plan_prepare", if (!plan) throw EngineError("null plan"); shard_import_finish(plan); return 0;, -1)
+    return abi_call("spasm_amd_schur_plan_prepare", -1, [&] {
+        if (!plan) throw EngineError("null plan");
+        shard_import_finish(plan);
+        return 0;
+    });
 }
 SPASM_API spasm_amd_dshard *spasm_amd_dshard_open(spasm_amd_schur_plan *plan, int me, int nshards)
 {
-    DSHARD_TRY("spasm_amd_dshard_open", return dshard_open(plan, me, nshards);, nullptr)
+    return abi_call<spasm_amd_dshard *>("spasm_amd_dshard_open", nullptr, [&] { return dshard_open(plan, me, nshards); });
 }
 SPASM_API spasm_amd_dshard *spasm_amd_dshard_open_rows(spasm_amd_shard *sh, int me, int nshards)
 {
-    DSHARD_TRY("spasm_amd_dshard_open_rows", return dshard_open_rows(sh, me, nshards);, nullptr)
+    return abi_call<spasm_amd_dshard *>("spasm_amd_dshard_open_rows", nullptr, [&] { return dshard_open_rows(sh, me, nshards); });
 }
 SPASM_API int spasm_amd_dshard_flags(spasm_amd_dshard *ds, int *flags_dev)
 {
-    DSHARD_TRY("spasm_amd_dshard_flags", DSHARD_OPEN(ds);
-               HIPCHK(hipMemcpy(flags_dev, ds->cflag(), ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice)); return 0;, -1)
+    return abi_call("spasm_amd_dshard_flags", -1, [&] {
+        dshard_opened(ds);
+        HIPCHK(hipMemcpy(flags_dev, ds->cflag(), ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice));
+        return 0;
+    });
 }
 SPASM_API double spasm_amd_dshard_density(spasm_amd_dshard *ds, const int *flags_dev, int free_cols, int *C_out)
 {
-    DSHARD_TRY("spasm_amd_dshard_density", DSHARD_OPEN(ds);
-               if (ds->fl) { // the rows as they are: the density is the matrix's own, which the caller knows; 1.0 = "dense, as you said"
-                   HIPCHK(hipMemcpy(ds->fl->cflag.p, flags_dev, ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice));
-                   ds->C = ds->fl->finish_columns();
-                   if (C_out) *C_out = ds->C;
-                   return 1.0;
-               }
-               HIPCHK(hipMemcpy(ds->dw->cflag.p, flags_dev, ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice));
-               ds->C = ds->dw->finish_columns();
-               if (C_out) *C_out = ds->C;
-               Round &R = ds->plan->R;
-               return ds->dw->estimate_density(R.np_rows.p, R.nnp, free_cols);, -1.0)
+    return abi_call("spasm_amd_dshard_density", -1.0, [&] {
+        dshard_opened(ds);
+        if (ds->fl) { // the rows as they are: the density is the matrix's own, which the caller knows; 1.0 = "dense, as you said"
+            HIPCHK(hipMemcpy(ds->fl->cflag.p, flags_dev, ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice));
+            ds->C = ds->fl->finish_columns();
+            if (C_out) *C_out = ds->C;
+            return 1.0;
+        }
+        HIPCHK(hipMemcpy(ds->dw->cflag.p, flags_dev, ((size_t)ds->plan->A.m + 1) * sizeof(int), hipMemcpyDeviceToDevice));
+        ds->C = ds->dw->finish_columns();
+        if (C_out) *C_out = ds->C;
+        Round &R = ds->plan->R;
+        return ds->dw->estimate_density(R.np_rows.p, R.nnp, free_cols);
+    });
 }
 SPASM_API int spasm_amd_dshard_build(spasm_amd_dshard *ds)
 {
-    DSHARD_TRY("spasm_amd_dshard_build", DSHARD_OPEN(ds);
-               if (ds->C <= 0) throw EngineError("no column left (call spasm_amd_dshard_density first)");
-               if (ds->plan->R.F.p <= 255) ds->impl.reset(new DShardT<signed char>());
-               else ds->impl.reset(new DShardT<short>());
-               if (ds->fl) ds->impl->build_rows(ds->plan, *ds->fl, ds->me, ds->nshards, ds->C);
-               else ds->impl->build(ds->plan, *ds->dw, ds->me, ds->nshards, ds->C);
-               return 0;, -1)
+    return abi_call("spasm_amd_dshard_build", -1, [&] {
+        dshard_opened(ds);
+        if (ds->C <= 0) throw EngineError("no column left (call spasm_amd_dshard_density first)");
+        if (ds->plan->R.F.p <= 255) ds->impl.reset(new DShardT<signed char>());
+        else ds->impl.reset(new DShardT<short>());
+        if (ds->fl) ds->impl->build_rows(ds->plan, *ds->fl, ds->me, ds->nshards, ds->C);
+        else ds->impl->build(ds->plan, *ds->dw, ds->me, ds->nshards, ds->C);
+        return 0;
+    });
 }
 SPASM_API int spasm_amd_dshard_info(spasm_amd_dshard *ds, int *C_out, int *KB, i64 *ldc, int *elem, int *nd, int *cand_bytes)
 {
-    DSHARD_TRY("spasm_amd_dshard_info", DSHARD_BUILT(ds); if (C_out) *C_out = ds->C; ds->impl->info(KB, ldc, elem, nd);
-               if (cand_bytes) *cand_bytes = (int)sizeof(CandRec); return 0;, -1)
+    return abi_call("spasm_amd_dshard_info", -1, [&] {
+        dshard_built(ds);
+        if (C_out) *C_out = ds->C;
+        ds->impl->info(KB, ldc, elem, nd);
+        if (cand_bytes) *cand_bytes = (int)sizeof(CandRec);
+        return 0;
+    });
 }
-SPASM_API int spasm_amd_dshard_block_begin(spasm_amd_dshard *ds) { DSHARD_TRY("spasm_amd_dshard_block_begin", DSHARD_BUILT(ds); ds->impl->block_begin(); return 0;, -1) }
+SPASM_API int spasm_amd_dshard_block_begin(spasm_amd_dshard *ds)
+{
+    return abi_call("spasm_amd_dshard_block_begin", -1, [&] { dshard_built(ds); ds->impl->block_begin(); return 0; });
+}
 SPASM_API int spasm_amd_dshard_candidates(spasm_amd_dshard *ds, int c0, int w, void *cand_dev)
 {
-    DSHARD_TRY("spasm_amd_dshard_candidates", DSHARD_BUILT(ds); ds->impl->candidates(c0, w, cand_dev); return 0;, -1)
+    return abi_call("spasm_amd_dshard_candidates", -1, [&] { dshard_built(ds); ds->impl->candidates(c0, w, cand_dev); return 0; });
 }
 SPASM_API int spasm_amd_dshard_elect(spasm_amd_dshard *ds, const void *stack_dev, int w, int *npp, int *cnt, int *first)
 {
-    DSHARD_TRY("spasm_amd_dshard_elect", DSHARD_BUILT(ds); ds->impl->elect(stack_dev, w); if (npp) *npp = ds->impl->hglob.npp;
-               for (int k = 0; k < ds->nshards; k++) { if (cnt) cnt[k] = ds->impl->hglob.cnt[k]; if (first) first[k] = ds->impl->hglob.first[k]; }
-               return 0;, -1)
+    return abi_call("spasm_amd_dshard_elect", -1, [&] {
+        dshard_built(ds);
+        ds->impl->elect(stack_dev, w);
+        if (npp) *npp = ds->impl->hglob.npp;
+        for (int k = 0; k < ds->nshards; k++) {
+            if (cnt) cnt[k] = ds->impl->hglob.cnt[k];
+            if (first) first[k] = ds->impl->hglob.first[k];
+        }
+        return 0;
+    });
 }
-SPASM_API i64 spasm_amd_dshard_pack(spasm_amd_dshard *ds, int c0, void *buf_dev) { DSHARD_TRY("spasm_amd_dshard_pack", DSHARD_BUILT(ds); return ds->impl->pack(c0, buf_dev);, -1) }
+SPASM_API i64 spasm_amd_dshard_pack(spasm_amd_dshard *ds, int c0, void *buf_dev)
+{
+    return abi_call<i64>("spasm_amd_dshard_pack", -1, [&] { dshard_built(ds); return ds->impl->pack(c0, buf_dev); });
+}
 SPASM_API int spasm_amd_dshard_unpack(spasm_amd_dshard *ds, int q, int c0, int owner, const void *buf_dev)
 {
-    DSHARD_TRY("spasm_amd_dshard_unpack", DSHARD_BUILT(ds); ds->impl->unpack(q, c0, owner, buf_dev); return 0;, -1)
+    return abi_call("spasm_amd_dshard_unpack", -1, [&] { dshard_built(ds); ds->impl->unpack(q, c0, owner, buf_dev); return 0; });
 }
-SPASM_API int spasm_amd_dshard_apply(spasm_amd_dshard *ds, int q, int c0, int w, int b1) { DSHARD_TRY("spasm_amd_dshard_apply", DSHARD_BUILT(ds); ds->impl->apply(q, c0, w, b1); return 0;, -1) }
+SPASM_API int spasm_amd_dshard_apply(spasm_amd_dshard *ds, int q, int c0, int w, int b1)
+{
+    return abi_call("spasm_amd_dshard_apply", -1, [&] { dshard_built(ds); ds->impl->apply(q, c0, w, b1); return 0; });
+}
 SPASM_API int spasm_amd_dshard_block_end(spasm_amd_dshard *ds, int b0, int b1, int npan)
 {
-    DSHARD_TRY("spasm_amd_dshard_block_end", DSHARD_BUILT(ds); ds->impl->block_end(b0, b1, npan); return 0;, -1)
+    return abi_call("spasm_amd_dshard_block_end", -1, [&] { dshard_built(ds); ds->impl->block_end(b0, b1, npan); return 0; });
 }
-SPASM_API int spasm_amd_dshard_finish(spasm_amd_dshard *ds) { DSHARD_TRY("spasm_amd_dshard_finish", DSHARD_BUILT(ds); return ds->impl->finish();, -1) }
+SPASM_API int spasm_amd_dshard_finish(spasm_amd_dshard *ds)
+{
+    return abi_call("spasm_amd_dshard_finish", -1, [&] { dshard_built(ds); return ds->impl->finish(); });
+}
 SPASM_API struct spasm_csr *spasm_amd_dshard_fetch_U(spasm_amd_dshard *ds, int *pivcol_out, int *row_out, int *n_out)
 {
-    DSHARD_TRY("spasm_amd_dshard_fetch_U", DSHARD_BUILT(ds); return dshard_fetch_U(ds, pivcol_out, row_out, n_out);, nullptr)
+    return abi_call<struct spasm_csr *>("spasm_amd_dshard_fetch_U", nullptr, [&] { dshard_built(ds); return dshard_fetch_U(ds, pivcol_out, row_out, n_out); });
 }
 SPASM_API void spasm_amd_dshard_close(spasm_amd_dshard *ds) { delete ds; }
 
 // reference src/SpaSM.jl:640-658 (axpy!, xapy!, A * x, x * A): host arrays; on failure y is left as it was
 SPASM_API void spasm_Axpy(const struct spasm_csr *A, const spasm_ZZp *x, spasm_ZZp *y)
 {
-    spasm_clear_error();
-    try {
-        spmv_once(A, 0, x, y, "spasm_Axpy");
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_Axpy: %s", e.what());
-    }
+    abi_call("spasm_Axpy", [&] { spmv_once(A, 0, x, y, "spasm_Axpy"); });
 }
 
 SPASM_API void spasm_xApy(const spasm_ZZp *x, const struct spasm_csr *A, spasm_ZZp *y)
 {
-    spasm_clear_error();
-    try {
-        spmv_once(A, 1, x, y, "spasm_xApy");
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_xApy: %s", e.what());
-    }
+    abi_call("spasm_xApy", [&] { spmv_once(A, 1, x, y, "spasm_xApy"); });
 }
 
 SPASM_API spasm_amd_spmv *spasm_amd_spmv_create(const struct spasm_csr *A)
 {
-    spasm_clear_error();
-    try {
-        return spmv_create(A, "spasm_amd_spmv_create");
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_spmv_create: %s", e.what());
-        return nullptr;
-    }
+    return abi_call<spasm_amd_spmv *>("spasm_amd_spmv_create", nullptr, [&] { return spmv_create(A, "spasm_amd_spmv_create"); });
 }
 
 SPASM_API int spasm_amd_spmv_apply(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_spmv_apply", -1, [&] {
         spmv_check(op, trans, k, X, ldx, Y, ldy, "spasm_amd_spmv_apply");
-        DeviceGuard g;
-        HIPCHK(hipSetDevice(op->dev));
+        DeviceGuard g(op);
         op->apply_host(trans, k, X, ldx, Y, ldy);
         return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_spmv_apply: %s", e.what());
-        return -1;
-    }
+    });
 }
 
 SPASM_API int spasm_amd_spmv_apply_dev(spasm_amd_spmv *op, int trans, int k, const spasm_ZZp *X, i64 ldx, spasm_ZZp *Y, i64 ldy, void *stream)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_spmv_apply_dev", -1, [&] {
         spmv_check(op, trans, k, X, ldx, Y, ldy, "spasm_amd_spmv_apply_dev");
-        DeviceGuard g;
-        HIPCHK(hipSetDevice(op->dev));
+        DeviceGuard g(op);
         hipStream_t s = (hipStream_t)stream;
         if (k > 0) op->apply_dev(trans, k, X, ldx, Y, ldy, s);
         if (!stream) HIPCHK(hipStreamSynchronize(s));
         return 0;
-    } catch (const std::exception &e) {
-        spasm_set_error("spasm_amd_spmv_apply_dev: %s", e.what());
-        return -1;
-    }
+    });
 }
 
-SPASM_API void spasm_amd_spmv_free(spasm_amd_spmv *op)
-{
-    if (!op) return;
-    DeviceGuard g;
-    (void)hipSetDevice(op->dev);
-    delete op;
-}
+SPASM_API void spasm_amd_spmv_free(spasm_amd_spmv *op) { handle_free(op); }
 
 // ---- sparse matrix algebra on resident matrices (spgemm.hpp; engine extension) ----
-#define DCSR_TRY(who, body, fail)                          \
-    spasm_clear_error();                                   \
-    try {                                                  \
-        body                                               \
-    } catch (const std::exception &e) {                    \
-        spasm_set_error("%s: %s", who, e.what());          \
-        return fail;                                       \
-    }
-#define DCSR_ON(D) DeviceGuard g; if (D) HIPCHK(hipSetDevice((D)->dev));
-
-SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_upload(const struct spasm_csr *A) { DCSR_TRY("spasm_amd_dcsr_upload", return dcsr_upload(A, "upload");, nullptr) }
+SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_upload(const struct spasm_csr *A)
+{
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_upload", nullptr, [&] { return dcsr_upload(A, "upload"); });
+}
 SPASM_API struct spasm_csr *spasm_amd_dcsr_download(const spasm_amd_dcsr *D)
 {
-    DCSR_TRY("spasm_amd_dcsr_download", dcsr_need(D, "download"); DCSR_ON(D) return dcsr_download(D);, nullptr)
+    return abi_call<struct spasm_csr *>("spasm_amd_dcsr_download", nullptr, [&] { dcsr_need(D, "download"); DeviceGuard g(D); return dcsr_download(D); });
 }
 SPASM_API void spasm_amd_dcsr_info(const spasm_amd_dcsr *D, i64 *out)
 {
@@ -9633,51 +9481,48 @@ SPASM_API void spasm_amd_dcsr_stats(const spasm_amd_dcsr *D, i64 *out)
     if (!D || !out) return;
     memcpy(out, D->stats, sizeof D->stats);
 }
-SPASM_API void spasm_amd_dcsr_free(spasm_amd_dcsr *D)
-{
-    if (!D) return;
-    DeviceGuard g;
-    (void)hipSetDevice(D->dev);
-    delete D;
-}
+SPASM_API void spasm_amd_dcsr_free(spasm_amd_dcsr *D) { handle_free(D); }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_mul(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B)
 {
-    DCSR_TRY("spasm_amd_dcsr_mul", DCSR_ON(A) return dcsr_mul(A, B, "product");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_mul", nullptr, [&] { DeviceGuard g(A); return dcsr_mul(A, B, "product"); });
 }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_lincomb(i64 a, const spasm_amd_dcsr *A, i64 b, const spasm_amd_dcsr *B)
 {
-    DCSR_TRY("spasm_amd_dcsr_lincomb", DCSR_ON(A) return dcsr_lincomb(a, A, b, B, "combination");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_lincomb", nullptr, [&] { DeviceGuard g(A); return dcsr_lincomb(a, A, b, B, "combination"); });
 }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_submatrix(const spasm_amd_dcsr *A, int r0, int r1, int c0, int c1)
 {
-    DCSR_TRY("spasm_amd_dcsr_submatrix", DCSR_ON(A) return dcsr_submatrix(A, r0, r1, c0, c1, "submatrix");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_submatrix", nullptr, [&] { DeviceGuard g(A); return dcsr_submatrix(A, r0, r1, c0, c1, "submatrix"); });
 }
 SPASM_API int spasm_amd_dcsr_equal(const spasm_amd_dcsr *A, const spasm_amd_dcsr *B)
 {
-    DCSR_TRY("spasm_amd_dcsr_equal", DCSR_ON(A) return dcsr_equal(A, B, "comparison");, -1)
+    return abi_call("spasm_amd_dcsr_equal", -1, [&] { DeviceGuard g(A); return dcsr_equal(A, B, "comparison"); });
 }
 // transpose, permutation, concatenation of resident matrices (reshape.hpp)
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_transpose(const spasm_amd_dcsr *A)
 {
-    DCSR_TRY("spasm_amd_dcsr_transpose", DCSR_ON(A) return dcsr_transpose(A, "transpose");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_transpose", nullptr, [&] { DeviceGuard g(A); return dcsr_transpose(A, "transpose"); });
 }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_permute(const spasm_amd_dcsr *A, const int *p, const int *qinv)
 {
-    DCSR_TRY("spasm_amd_dcsr_permute", DCSR_ON(A) return dcsr_permute(A, p, qinv, "permutation");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_permute", nullptr, [&] { DeviceGuard g(A); return dcsr_permute(A, p, qinv, "permutation"); });
 }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_vcat(int count, const spasm_amd_dcsr *const *D)
 {
-    DCSR_TRY("spasm_amd_dcsr_vcat", DCSR_ON((count > 0 && D) ? D[0] : nullptr) return dcsr_cat(RSH_VCAT, count, D, "vcat");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_vcat", nullptr, [&] { DeviceGuard g((count > 0 && D) ? D[0] : nullptr); return dcsr_cat(RSH_VCAT, count, D, "vcat"); });
 }
 SPASM_API spasm_amd_dcsr *spasm_amd_dcsr_hcat(int count, const spasm_amd_dcsr *const *D)
 {
-    DCSR_TRY("spasm_amd_dcsr_hcat", DCSR_ON((count > 0 && D) ? D[0] : nullptr) return dcsr_cat(RSH_HCAT, count, D, "hcat");, nullptr)
+    return abi_call<spasm_amd_dcsr *>("spasm_amd_dcsr_hcat", nullptr, [&] { DeviceGuard g((count > 0 && D) ? D[0] : nullptr); return dcsr_cat(RSH_HCAT, count, D, "hcat"); });
 }
 // one-shot forms on host matrices: upload, operate, download
-SPASM_API struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B) { DCSR_TRY("spasm_amd_csr_mul", return csr_mul_once(A, B);, nullptr) }
+SPASM_API struct spasm_csr *spasm_amd_csr_mul(const struct spasm_csr *A, const struct spasm_csr *B)
+{
+    return abi_call<struct spasm_csr *>("spasm_amd_csr_mul", nullptr, [&] { return csr_mul_once(A, B); });
+}
 SPASM_API struct spasm_csr *spasm_amd_csr_lincomb(i64 a, const struct spasm_csr *A, i64 b, const struct spasm_csr *B)
 {
-    DCSR_TRY("spasm_amd_csr_lincomb", return csr_lincomb_once(a, A, b, B);, nullptr)
+    return abi_call<struct spasm_csr *>("spasm_amd_csr_lincomb", nullptr, [&] { return csr_lincomb_once(a, A, b, B); });
 }
 
 // reference src/SpaSM.jl:663-692 (dense_back_solve, dense_forward_solve): host arrays; on an error b and x are left as they were
@@ -9693,45 +9538,29 @@ SPASM_API bool spasm_dense_back_solve(const struct spasm_csr *L, spasm_ZZp *b, s
 
 SPASM_API spasm_amd_trsolve *spasm_amd_trsolve_create(const struct spasm_csr *T, const int *piv, int kind)
 {
-    spasm_clear_error();
-    try {
-        return trsolve_create(T, piv, kind, "spasm_amd_trsolve_create");
-    } catch (const std::exception &e) {
-        trsolve_error("spasm_amd_trsolve_create", e);
-        return nullptr;
-    }
+    return abi_call<spasm_amd_trsolve *>("spasm_amd_trsolve_create", nullptr, [&] { return trsolve_create(T, piv, kind, "spasm_amd_trsolve_create"); }, ABI_NAMED_BELOW);
 }
 
 SPASM_API int spasm_amd_trsolve_apply(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_trsolve_apply", -1, [&] {
         trsolve_check(op, k, B, ldb, X, ldx, ok, "spasm_amd_trsolve_apply");
-        DeviceGuard g;
-        HIPCHK(hipSetDevice(op->dev));
+        DeviceGuard g(op);
         op->apply_host(k, B, ldb, X, ldx, ok);
         return 0;
-    } catch (const std::exception &e) {
-        trsolve_error("spasm_amd_trsolve_apply", e);
-        return -1;
-    }
+    }, ABI_NAMED_BELOW);
 }
 
 SPASM_API int spasm_amd_trsolve_apply_dev(spasm_amd_trsolve *op, int k, spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream)
 {
-    spasm_clear_error();
-    try {
+    return abi_call("spasm_amd_trsolve_apply_dev", -1, [&] {
         trsolve_check(op, k, B, ldb, X, ldx, ok, "spasm_amd_trsolve_apply_dev");
-        DeviceGuard g;
-        HIPCHK(hipSetDevice(op->dev));
+        DeviceGuard g(op);
         hipStream_t s = (hipStream_t)stream;
         if (k > 0) op->apply_dev(k, B, ldb, X, ldx, ok, s);
         if (!stream) HIPCHK(hipStreamSynchronize(s));
         return 0;
-    } catch (const std::exception &e) {
-        trsolve_error("spasm_amd_trsolve_apply_dev", e);
-        return -1;
-    }
+    }, ABI_NAMED_BELOW);
 }
 
 SPASM_API void spasm_amd_trsolve_stats(const spasm_amd_trsolve *op, i64 *out)
@@ -9741,39 +9570,22 @@ SPASM_API void spasm_amd_trsolve_stats(const spasm_amd_trsolve *op, i64 *out)
     memcpy(out, v, sizeof v);
 }
 
-SPASM_API void spasm_amd_trsolve_free(spasm_amd_trsolve *op)
-{
-    if (!op) return;
-    DeviceGuard g;
-    (void)hipSetDevice(op->dev);
-    delete op;
-}
+SPASM_API void spasm_amd_trsolve_free(spasm_amd_trsolve *op) { handle_free(op); }
 
-// ---- many small matrices in one call (batch.hpp; engine extension) ----
-#define BATCH_TRY(who, body)                               \
-    spasm_clear_error();                                   \
-    try {                                                  \
-        DeviceGuard g;                                     \
-        body                                               \
-        return 0;                                          \
-    } catch (const std::exception &e) {                    \
-        spasm_set_error("%s: %s", who, e.what());          \
-        return -1;                                         \
-    }
-
+// ---- many small matrices in one call (batch.hpp; engine extension): the caller's device is put back, none is selected ----
 SPASM_API int spasm_amd_echelonize_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_lu **out)
 {
-    BATCH_TRY("spasm_amd_echelonize_batch", batch_run(BATCH_LU, count, A, opts, out, nullptr, nullptr);)
+    return abi_call("spasm_amd_echelonize_batch", -1, [&] { DeviceGuard g; batch_run(BATCH_LU, count, A, opts, out, nullptr, nullptr); return 0; });
 }
 
 SPASM_API int spasm_amd_rank_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, i64 *rank)
 {
-    BATCH_TRY("spasm_amd_rank_batch", batch_run(BATCH_RANK, count, A, opts, nullptr, nullptr, rank);)
+    return abi_call("spasm_amd_rank_batch", -1, [&] { DeviceGuard g; batch_run(BATCH_RANK, count, A, opts, nullptr, nullptr, rank); return 0; });
 }
 
 SPASM_API int spasm_amd_kernel_batch(int count, const struct spasm_csr *const *A, struct echelonize_opts *opts, struct spasm_csr **K)
 {
-    BATCH_TRY("spasm_amd_kernel_batch", batch_run(BATCH_KERNEL, count, A, opts, nullptr, K, nullptr);)
+    return abi_call("spasm_amd_kernel_batch", -1, [&] { DeviceGuard g; batch_run(BATCH_KERNEL, count, A, opts, nullptr, K, nullptr); return 0; });
 }
 
 SPASM_API void spasm_amd_batch_stats(i64 *out)
@@ -9782,22 +9594,14 @@ SPASM_API void spasm_amd_batch_stats(i64 *out)
 }
 
 // ---- a matrix split into its connected components on the device (blocks.hpp; engine extension) ----
-#define BLOCKS_TRY(who, body, fail)                        \
-    spasm_clear_error();                                   \
-    try {                                                  \
-        DeviceGuard g;                                     \
-        body                                               \
-    } catch (const std::exception &e) {                    \
-        spasm_set_error("%s: %s", who, e.what());          \
-        return fail;                                       \
-    }
-#define BLOCKS_ON(B) if (B) HIPCHK(hipSetDevice((B)->dev));
-
-SPASM_API spasm_amd_blocks *spasm_amd_blocks_create(const struct spasm_csr *A) { BLOCKS_TRY("spasm_amd_blocks_create", return blocks_create(A);, nullptr) }
+SPASM_API spasm_amd_blocks *spasm_amd_blocks_create(const struct spasm_csr *A)
+{
+    return abi_call<spasm_amd_blocks *>("spasm_amd_blocks_create", nullptr, [&] { DeviceGuard g; return blocks_create(A); });
+}
 
 SPASM_API spasm_amd_blocks *spasm_amd_blocks_create_dcsr(const spasm_amd_dcsr *D)
 {
-    BLOCKS_TRY("spasm_amd_blocks_create_dcsr", BLOCKS_ON(D) return blocks_create_dcsr(D);, nullptr)
+    return abi_call<spasm_amd_blocks *>("spasm_amd_blocks_create_dcsr", nullptr, [&] { DeviceGuard g(D); return blocks_create_dcsr(D); });
 }
 
 SPASM_API void spasm_amd_blocks_info(const spasm_amd_blocks *B, i64 *out)
@@ -9809,64 +9613,66 @@ SPASM_API void spasm_amd_blocks_info(const spasm_amd_blocks *B, i64 *out)
 
 SPASM_API int spasm_amd_blocks_shapes(const spasm_amd_blocks *B, int *rows, int *cols, i64 *nnz)
 {
-    BLOCKS_TRY("spasm_amd_blocks_shapes", blocks_need(B);
-               for (int b = 0; b < B->nb; b++) {
-                   if (rows) rows[b] = (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]);
-                   if (cols) cols[b] = (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]);
-                   if (nnz) nnz[b] = B->h_nnz[(size_t)b];
-               } return 0;, -1)
+    return abi_call("spasm_amd_blocks_shapes", -1, [&] {
+        DeviceGuard g;
+        blocks_need(B);
+        for (int b = 0; b < B->nb; b++) {
+            if (rows) rows[b] = (int)(B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b]);
+            if (cols) cols[b] = (int)(B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b]);
+            if (nnz) nnz[b] = B->h_nnz[(size_t)b];
+        }
+        return 0;
+    });
 }
 
 SPASM_API int spasm_amd_blocks_maps(const spasm_amd_blocks *B, int *row_block, int *row_pos, int *col_block, int *col_pos, int *block_rows, i64 *row_start,
                                     int *block_cols, i64 *col_start)
 {
-    BLOCKS_TRY("spasm_amd_blocks_maps", blocks_need(B); BLOCKS_ON(B) hipStream_t s = nullptr;
-               blocks_copy_out(row_block, B->row_block, (size_t)B->n, s); blocks_copy_out(row_pos, B->row_pos, (size_t)B->n, s);
-               blocks_copy_out(col_block, B->col_block, (size_t)B->m, s); blocks_copy_out(col_pos, B->col_pos, (size_t)B->m, s);
-               blocks_copy_out(block_rows, B->block_rows, (size_t)B->n, s); blocks_copy_out(block_cols, B->block_cols, (size_t)B->m, s);
-               HIPCHK(hipStreamSynchronize(s));
-               if (row_start) memcpy(row_start, B->h_row_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
-               if (col_start) memcpy(col_start, B->h_col_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
-               return 0;, -1)
+    return abi_call("spasm_amd_blocks_maps", -1, [&] {
+        DeviceGuard g(B);
+        blocks_need(B);
+        hipStream_t s = nullptr;
+        blocks_copy_out(row_block, B->row_block, (size_t)B->n, s); blocks_copy_out(row_pos, B->row_pos, (size_t)B->n, s);
+        blocks_copy_out(col_block, B->col_block, (size_t)B->m, s); blocks_copy_out(col_pos, B->col_pos, (size_t)B->m, s);
+        blocks_copy_out(block_rows, B->block_rows, (size_t)B->n, s); blocks_copy_out(block_cols, B->block_cols, (size_t)B->m, s);
+        HIPCHK(hipStreamSynchronize(s));
+        if (row_start) memcpy(row_start, B->h_row_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
+        if (col_start) memcpy(col_start, B->h_col_start.data(), sizeof(i64) * ((size_t)B->nb + 1));
+        return 0;
+    });
 }
 
 SPASM_API struct spasm_csr *spasm_amd_blocks_fetch(const spasm_amd_blocks *B, int b)
 {
-    BLOCKS_TRY("spasm_amd_blocks_fetch", blocks_need(B); BLOCKS_ON(B) return blocks_fetch(B, b);, nullptr)
+    return abi_call<struct spasm_csr *>("spasm_amd_blocks_fetch", nullptr, [&] { DeviceGuard g(B); blocks_need(B); return blocks_fetch(B, b); });
 }
 
 SPASM_API int spasm_amd_blocks_rank(spasm_amd_blocks *B, struct echelonize_opts *opts, i64 *rank)
 {
-    BLOCKS_TRY("spasm_amd_blocks_rank", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_RANK, B, opts, nullptr, nullptr, rank); return 0;, -1)
+    return abi_call("spasm_amd_blocks_rank", -1, [&] { DeviceGuard g(B); blocks_need(B); blocks_run(BATCH_RANK, B, opts, nullptr, nullptr, rank); return 0; });
 }
 
 SPASM_API int spasm_amd_blocks_echelonize(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_lu **out)
 {
-    BLOCKS_TRY("spasm_amd_blocks_echelonize", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_LU, B, opts, out, nullptr, nullptr); return 0;, -1)
+    return abi_call("spasm_amd_blocks_echelonize", -1, [&] { DeviceGuard g(B); blocks_need(B); blocks_run(BATCH_LU, B, opts, out, nullptr, nullptr); return 0; });
 }
 
 SPASM_API int spasm_amd_blocks_kernel(spasm_amd_blocks *B, struct echelonize_opts *opts, struct spasm_csr **K)
 {
-    BLOCKS_TRY("spasm_amd_blocks_kernel", blocks_need(B); BLOCKS_ON(B) blocks_run(BATCH_KERNEL, B, opts, nullptr, K, nullptr); return 0;, -1)
+    return abi_call("spasm_amd_blocks_kernel", -1, [&] { DeviceGuard g(B); blocks_need(B); blocks_run(BATCH_KERNEL, B, opts, nullptr, K, nullptr); return 0; });
 }
 
-SPASM_API void spasm_amd_blocks_free(spasm_amd_blocks *B)
-{
-    if (!B) return;
-    DeviceGuard g;
-    (void)hipSetDevice(B->dev);
-    delete B;
-}
+SPASM_API void spasm_amd_blocks_free(spasm_amd_blocks *B) { handle_free(B); }
 
 // ---- X * A = B for many small matrices, and block by block (solve_batch.hpp; engine extension) ----
 SPASM_API int spasm_amd_solve_batch(int count, const struct spasm_csr *const *A, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
 {
-    BATCH_TRY("spasm_amd_solve_batch", solve_batch_run(count, A, B, X, ok);)
+    return abi_call("spasm_amd_solve_batch", -1, [&] { DeviceGuard g; solve_batch_run(count, A, B, X, ok); return 0; });
 }
 
 SPASM_API int spasm_amd_blocks_solve(spasm_amd_blocks *B, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
 {
-    BLOCKS_TRY("spasm_amd_blocks_solve", solve_blocks_run(B, Rhs, X, ok); return 0;, -1)
+    return abi_call("spasm_amd_blocks_solve", -1, [&] { DeviceGuard g; solve_blocks_run(B, Rhs, X, ok); return 0; });
 }
 
 SPASM_API void spasm_amd_solve_stats(i64 *out)
@@ -9874,35 +9680,35 @@ SPASM_API void spasm_amd_solve_stats(i64 *out)
     if (out) memcpy(out, g_solve_stats, sizeof g_solve_stats);
 }
 
-// ---- X * A = B with A factored once (solver.hpp; engine extension) ----
+// ---- X * A = B with A factored once (solver.hpp; engine extension): the functions called select the solver's device ----
 SPASM_API spasm_amd_solver *spasm_amd_solver_create(int count, const struct spasm_csr *const *A)
 {
-    BLOCKS_TRY("spasm_amd_solver_create", return solver_create(count, A);, nullptr)
+    return abi_call<spasm_amd_solver *>("spasm_amd_solver_create", nullptr, [&] { DeviceGuard g; return solver_create(count, A); });
 }
 
 SPASM_API spasm_amd_solver *spasm_amd_solver_create_blocks(const spasm_amd_blocks *Bk)
 {
-    BLOCKS_TRY("spasm_amd_solver_create_blocks", return solver_create_blocks(Bk);, nullptr)
+    return abi_call<spasm_amd_solver *>("spasm_amd_solver_create_blocks", nullptr, [&] { DeviceGuard g; return solver_create_blocks(Bk); });
 }
 
 SPASM_API int spasm_amd_solver_apply(spasm_amd_solver *S, const struct spasm_csr *const *B, struct spasm_csr **X, unsigned char *const *ok)
 {
-    BATCH_TRY("spasm_amd_solver_apply", solver_apply_run(S, B, X, ok);)
+    return abi_call("spasm_amd_solver_apply", -1, [&] { DeviceGuard g; solver_apply_run(S, B, X, ok); return 0; });
 }
 
 SPASM_API int spasm_amd_solver_apply_blocks(spasm_amd_solver *S, const struct spasm_csr *Rhs, struct spasm_csr **X, unsigned char *ok)
 {
-    BLOCKS_TRY("spasm_amd_solver_apply_blocks", solver_apply_blocks_run(S, Rhs, X, ok); return 0;, -1)
+    return abi_call("spasm_amd_solver_apply_blocks", -1, [&] { DeviceGuard g; solver_apply_blocks_run(S, Rhs, X, ok); return 0; });
 }
 
 SPASM_API int spasm_amd_solver_apply_dense(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok)
 {
-    BLOCKS_TRY("spasm_amd_solver_apply_dense", solver_apply_dense_host(S, K, B, ldb, X, ldx, ok); return 0;, -1)
+    return abi_call("spasm_amd_solver_apply_dense", -1, [&] { DeviceGuard g; solver_apply_dense_host(S, K, B, ldb, X, ldx, ok); return 0; });
 }
 
 SPASM_API int spasm_amd_solver_apply_dense_dev(spasm_amd_solver *S, int K, const spasm_ZZp *B, i64 ldb, spasm_ZZp *X, i64 ldx, unsigned char *ok, void *stream)
 {
-    BLOCKS_TRY("spasm_amd_solver_apply_dense_dev", solver_apply_dense_dev(S, K, B, ldb, X, ldx, ok, (hipStream_t)stream); return 0;, -1)
+    return abi_call("spasm_amd_solver_apply_dense_dev", -1, [&] { DeviceGuard g; solver_apply_dense_dev(S, K, B, ldb, X, ldx, ok, (hipStream_t)stream); return 0; });
 }
 
 SPASM_API void spasm_amd_solver_dense_info(const spasm_amd_solver *S, i64 *out)
@@ -9922,20 +9728,26 @@ SPASM_API void spasm_amd_solver_info(const spasm_amd_solver *S, i64 *out)
 
 SPASM_API int spasm_amd_solver_ranks(const spasm_amd_solver *S, i64 *rank)
 {
-    BLOCKS_TRY("spasm_amd_solver_ranks", if (!S) throw EngineError("NULL handle");
-               if (!S->sys.empty() && !rank) throw EngineError("NULL array");
-               for (size_t i = 0; i < S->sys.size(); i++) rank[i] = S->sys[i].r;
-               return 0;, -1)
+    return abi_call("spasm_amd_solver_ranks", -1, [&] {
+        DeviceGuard g;
+        if (!S) throw EngineError("NULL handle");
+        if (!S->sys.empty() && !rank) throw EngineError("NULL array");
+        for (size_t i = 0; i < S->sys.size(); i++) rank[i] = S->sys[i].r;
+        return 0;
+    });
 }
 
 SPASM_API int spasm_amd_solver_basis(const spasm_amd_solver *S, int i, int *rows)
 {
-    BLOCKS_TRY("spasm_amd_solver_basis", if (!S) throw EngineError("NULL handle");
-               if (i < 0 || (size_t)i >= S->sys.size()) throw EngineError("system index out of range");
-               const std::vector<int> &b = S->sys[(size_t)i].basis;
-               if (!b.empty() && !rows) throw EngineError("NULL array");
-               if (!b.empty()) memcpy(rows, b.data(), b.size() * sizeof(int));
-               return (int)b.size();, -1)
+    return abi_call("spasm_amd_solver_basis", -1, [&] {
+        DeviceGuard g;
+        if (!S) throw EngineError("NULL handle");
+        if (i < 0 || (size_t)i >= S->sys.size()) throw EngineError("system index out of range");
+        const std::vector<int> &b = S->sys[(size_t)i].basis;
+        if (!b.empty() && !rows) throw EngineError("NULL array");
+        if (!b.empty()) memcpy(rows, b.data(), b.size() * sizeof(int));
+        return (int)b.size();
+    });
 }
 
 SPASM_API void spasm_amd_solver_stats(i64 *out)
@@ -9943,13 +9755,7 @@ SPASM_API void spasm_amd_solver_stats(i64 *out)
     if (out) memcpy(out, g_solver_stats, sizeof g_solver_stats);
 }
 
-SPASM_API void spasm_amd_solver_free(spasm_amd_solver *S)
-{
-    if (!S) return;
-    DeviceGuard g;
-    (void)hipSetDevice(S->dev);
-    delete S;
-}
+SPASM_API void spasm_amd_solver_free(spasm_amd_solver *S) { handle_free(S); }
 
 SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds)
 {
