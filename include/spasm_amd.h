@@ -771,6 +771,42 @@ int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, const int *
  * ("no HIP device") or with bad arguments 1, and out is not written. */
 int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *b, const int *count, int *out);
 
+/* ---- Engine extension: determinants mod p (csrc/det.hpp) ----
+ * The elimination computes every pivot and then keeps only their number; these entries return the determinant of a square matrix
+ * as a balanced residue, at the three scales of the engine: many small matrices in one call, a split matrix block by block, a
+ * whole matrix.  The matrices of one batch may differ in size and in prime.
+ *   LDS path      a matrix with n * n <= 32768 (n <= 181) is eliminated by ONE workgroup in LDS, as spasm_amd_rank_batch does it;
+ *                 det = sgn(k -> row of the k-th pivot) * product of the pivots, the product taken over the inverses the
+ *                 elimination keeps and inverted once.  All such matrices of a call in at most four launches; one int per matrix
+ *                 comes back.
+ *   general path  every other matrix goes through spasm_echelonize with L, one at a time: 0 when the rank is below n, otherwise
+ *                 sgn(p) * sgn(pivot columns) * product of the diagonal of L; the two parities are counted on the host.
+ *   det_batch     det[i] for A[0 .. count)
+ *   blocks_det    the matrix behind the handle: when a block is not square (a row or a column without entry is such a block) the
+ *                 determinant is 0 and nothing is eliminated; otherwise it is the product of the blocks' determinants, the blocks
+ *                 inside the LDS limit straight from the handle, the others fetched and sent through the general path, times the
+ *                 parities of the row and of the column permutation that bring A to block-diagonal form.  Those are counted on the
+ *                 host from row_block / row_pos / col_block / col_pos: 16 bytes per row are downloaded (not when the product is 0).
+ *   det           spasm_amd_blocks_create + blocks_det; dcsr_det: spasm_amd_blocks_create_dcsr + blocks_det on the resident
+ *                 matrix's device, no entry crosses the host
+ *   values        any int32 is accepted and reduced on load; a row must not hold a column twice.  The determinant of the 0 x 0
+ *                 matrix is 1.
+ *   stats         of the last det call of this thread: out[8] = matrices (det_batch) or blocks, of them through the LDS path,
+ *                 through the general path, blocks that make the determinant 0 by their shape, launches of the LDS path, its
+ *                 device microseconds (HIP events), host microseconds spent on parities (the download of the maps included), 0.
+ *                 The split of det / dcsr_det is not part of them.
+ *   deterministic two runs give the same values
+ *   errors        count < 0, a NULL array or result pointer, a NULL matrix or handle, A->x == NULL, a malformed matrix, a prime
+ *                 outside 3 .. 0xFFFFFFFB, a column index outside the matrix, a matrix that is not square ("matrix 3: not square
+ *                 (3 x 2)"), no device ("no HIP device"), out of memory: -1, NO output slot is written, spasm_amd_last_error()
+ *                 names the cause (and the index of the matrix).  All but the last two are found before a device is looked for.
+ *                 count == 0 succeeds (and needs no device).  After success the error text is empty. */
+int spasm_amd_det_batch(int count, const struct spasm_csr *const *A, spasm_ZZp *det);
+int spasm_amd_det(const struct spasm_csr *A, spasm_ZZp *det);
+int spasm_amd_blocks_det(spasm_amd_blocks *B, spasm_ZZp *det);
+int spasm_amd_dcsr_det(const spasm_amd_dcsr *D, spasm_ZZp *det);
+void spasm_amd_det_stats(i64 *out);   /* of the last det call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

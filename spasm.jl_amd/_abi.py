@@ -302,6 +302,11 @@ SIGNATURES = {
     "spasm_amd_solver_apply_dense": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_solver_apply_dense_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
     "spasm_amd_solver_dense_info": (None, [C.c_void_p, _P(C.c_int64)]),
+    "spasm_amd_det_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(C.c_int32)]),
+    "spasm_amd_det": (C.c_int32, [_P(CsrStruct), _P(C.c_int32)]),
+    "spasm_amd_blocks_det": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_dcsr_det": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_det_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -1840,3 +1840,58 @@ def rank_certificate_load(path):
         _abi.lib().spasm_rank_certificate_free(ptr)
         return None
     return RankCertificate(ptr)
+
+
+# ---------------------------------------------------------------------------------------------
+# Determinants mod p  (spasm_amd_det*; csrc/det.hpp; engine extension)
+# ---------------------------------------------------------------------------------------------
+DET_STATS = ("items", "lds_path", "general_path", "zero_by_structure", "launches", "device_us", "host_parity_us", "spare")
+
+
+def det_batch(mats):
+    """det_batch([A, ...]) -> numpy int64 array of the determinants mod p as balanced residues (spasm_amd_det_batch): square
+    matrices with n * n <= 32768 are eliminated inside LDS, one workgroup each, and one int per matrix comes back; the others
+    take the path of echelonize with L one at a time.  The matrices may differ in size and in prime."""
+    mats = list(mats)
+    for A in mats:
+        if not isinstance(A, CSR):
+            raise TypeError("a list of CSR expected")
+    arr = (C.POINTER(_abi.CsrStruct) * max(len(mats), 1))(*[A.data for A in mats])
+    out = (C.c_int32 * max(len(mats), 1))()
+    with _quiet(True):
+        rc = _abi.lib().spasm_amd_det_batch(len(mats), arr, out)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_det_batch failed")
+    return np.array(out[: len(mats)], dtype=np.int64)
+
+
+def det(A):
+    """det(A) -> int, the determinant mod p as a balanced residue.  A CSR (spasm_amd_det) or a DeviceCSR (spasm_amd_dcsr_det) is
+    split into its blocks on the device first; a DeviceBlocks (spasm_amd_blocks_det) is split already.  The value is the product
+    of the blocks' determinants times the parities of the two permutations that bring A to block-diagonal form; 0 without any
+    elimination when a block is not square."""
+    lib = _abi.lib()
+    out = C.c_int32(0)
+    with _quiet(True):
+        if isinstance(A, CSR):
+            who, rc = "spasm_amd_det", lib.spasm_amd_det(A.data, C.byref(out))
+        elif isinstance(A, DeviceCSR):
+            who, rc = "spasm_amd_dcsr_det", lib.spasm_amd_dcsr_det(A._need(), C.byref(out))
+        elif isinstance(A, DeviceBlocks):
+            who, rc = "spasm_amd_blocks_det", lib.spasm_amd_blocks_det(A._need(), C.byref(out))
+        else:
+            raise TypeError("a CSR, a DeviceCSR or a DeviceBlocks expected")
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return int(out.value)
+
+
+def det_stats():
+    """Counters of the last det call of this thread (spasm_amd_det_stats), as a dict keyed by DET_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_det_stats(out)
+    return {k: int(v) for k, v in zip(DET_STATS, out)}
+
+
+DeviceCSR.det = det
+DeviceBlocks.det = det

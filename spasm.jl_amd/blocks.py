@@ -209,3 +209,38 @@ def _kernel_block(ks, col2block, block2col):
         row2block += [(b, i) for i in range(kn)]
         r += kn
     return Block(ks, row2block, col2block, block2row, block2col)
+
+
+def det(block):
+    """The determinant mod p of the matrix the block was split from, as a balanced residue.  A DeviceBlocks goes to the device entry
+    (api.DeviceBlocks.det).  A host Block of matrices: 0 when a block is not square, otherwise ONE api.det_batch call for the
+    blocks, their product, and the parities of the row and the column permutation that put the blocks on the diagonal."""
+    if isinstance(block, api.DeviceBlocks):
+        return block.det()
+    n, m = block.shape
+    if n != m:
+        raise ValueError("a square matrix expected")
+    for X in block.blocks:
+        if not isinstance(X, api.CSR):
+            raise TypeError("a Block of CSR expected")
+    if any(X.n != X.m for X in block.blocks):
+        return 0
+    if not block.blocks:
+        return 1
+    p = block.blocks[0].prime
+    value = 1
+    for d in api.det_batch(block.blocks).tolist():
+        value = value * d % p
+    start = np.concatenate(([0], np.cumsum([X.n for X in block.blocks])))
+    for to_block in (block.row2block, block.col2block):
+        perm = [int(start[b]) + pos for b, pos in to_block]
+        seen, cycles = [False] * n, 0
+        for i in range(n):
+            if not seen[i]:
+                cycles += 1
+                while not seen[i]:
+                    seen[i] = True
+                    i = perm[i]
+        if (n - cycles) % 2:
+            value = -value % p
+    return int(api.balanced(value, p))

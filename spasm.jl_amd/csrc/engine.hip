@@ -9765,3 +9765,292 @@ SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_r
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Determinants mod p (det.hpp): of many small matrices in one call, of a split matrix block by block, of a whole matrix.  A
+// matrix whose image fits LDS (n * n <= BATCH_LIMIT) is one workgroup of k_batch_det, staged, classed and launched by the batch's
+// driver; the others go through do_echelonize with L one at a time, where
+//   det = sgn(k -> p[k]) * sgn(k -> column with qinv == k) * prod_k L[p[k]][k]:
+// A = L * U; the rows p[0 .. n) of L form a lower triangle whose diagonal holds the unscaled pivots (what
+// spasm_factorization_verify checks under (d)), and U, with a 1 on column pivcol[k] of row k and no cycle among its other entries,
+// has that one transversal.  Both parities are counted on the host, cycle by cycle.
+// ------------------------------------------------------------------------------------------------
+#include "det.hpp"
+
+namespace {
+
+// count, LDS items, general-path items, items zero by structure, launches, device us, host-parity us, spare
+thread_local i64 g_det_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+const ElimKernels<DetArgs> kBatchDet = {{k_batch_det<64>, k_batch_det<128>, k_batch_det<256>, k_batch_det<512>}};
+
+// 0 for an even permutation of 0 .. n - 1, 1 for an odd one: n - cycles mod 2
+int det_perm_parity(const std::vector<i64> &perm)
+{
+    const size_t n = perm.size();
+    std::vector<char> seen(n, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (perm[i] < 0 || (size_t)perm[i] >= n || seen[(size_t)perm[i]]) throw EngineError("internal error: a map of the determinant is no permutation");
+        seen[(size_t)perm[i]] = 1;
+    }
+    size_t cycles = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (seen[i] == 2) continue;
+        cycles++;
+        for (size_t k = i; seen[k] != 2; k = (size_t)perm[k]) seen[k] = 2;
+    }
+    return (int)((n - cycles) & 1);
+}
+
+// The LDS path from the descriptors on, as batch_fast runs BATCH_RANK: item[f] describes the f-th matrix of the concatenated CSR on
+// the device; out[f] = its determinant.  g_det_stats[4], [5] are added to.
+void det_fast(const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, std::vector<int> &out)
+{
+    const int nf = (int)item.size();
+    out.assign((size_t)nf, 0);
+    if (nf == 0) return;
+    hipStream_t s = nullptr;
+    std::vector<BatchDesc> desc((size_t)nf);
+    std::vector<unsigned char> cls((size_t)nf);
+    for (int f = 0; f < nf; f++) {
+        const BatchItem *M = &item[(size_t)f];
+        BatchDesc &d = desc[(size_t)f];
+        memset(&d, 0, sizeof d);
+        d.n = M->n;
+        d.m = M->m;
+        d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
+        d.F = zp_field_make(M->prime);
+        d.row0 = M->row0;
+        const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
+        int c = 0;
+        while (key > kBatchClass[c].cap) c++;
+        cls[(size_t)f] = (unsigned char)c;
+    }
+    DevBuf<BatchDesc> d_desc;
+    DevBuf<int> d_items, d_det;
+    d_desc.alloc((size_t)nf);
+    d_items.alloc((size_t)nf);
+    d_det.alloc((size_t)nf);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+    std::vector<int> items((size_t)nf);
+    DetArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = d_desc.p;
+    a.P = dP;
+    a.J = dJ;
+    a.X = dX;
+    a.mode = BATCH_RANK;
+    a.rank = d_det.p;
+    SpgEvents ev;
+    const int launches = batch_launch_jobs(kBatchDet, cls, 0, nf, items, d_items.p, a, ev.e[0], s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    HIPCHK(hipMemcpyAsync(out.data(), d_det.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    g_det_stats[4] += launches;
+    g_det_stats[5] += (i64)(ev.ms(0, 1) * 1000.0);
+}
+
+// one square matrix through the general path
+int det_general(const struct spasm_csr *M)
+{
+    const int n = M->n;
+    const ZpField F = zp_field_make(M->field->p);
+    std::unique_ptr<struct spasm_lu, void (*)(struct spasm_lu *)> N(solve_slow_factor(M), spasm_lu_free);
+    if (N->r < n) return 0;
+    const struct spasm_csr *Lf = N->L;
+    if (N->r != n || !Lf || !N->p || !N->qinv || Lf->n != n || Lf->m != n) throw EngineError("internal error: the factorization of a determinant has no square L");
+    const double t0 = spasm_wtime();
+    int prod = 1;
+    std::vector<i64> rows((size_t)n), cols((size_t)n, -1);
+    for (int k = 0; k < n; k++) {
+        const int i = N->p[k];
+        if (i < 0 || i >= n) throw EngineError("internal error: a map of the determinant is no permutation");
+        rows[(size_t)k] = i;
+        int diag = 0;
+        for (i64 q = Lf->p[i]; q < Lf->p[i + 1]; q++)
+            if (Lf->j[q] == k) diag = zp_add(F, diag, zp_reduce(F, (int64_t)Lf->x[q]));
+        if (diag == 0) throw EngineError("internal error: L without a pivot on its diagonal");
+        prod = zp_mul(F, prod, diag);
+    }
+    for (int j = 0; j < n; j++) {
+        const int k = N->qinv[j];
+        if (k < 0 || k >= n || cols[(size_t)k] != -1) throw EngineError("internal error: a map of the determinant is no permutation");
+        cols[(size_t)k] = j;
+    }
+    const int odd = det_perm_parity(rows) ^ det_perm_parity(cols);
+    g_det_stats[6] += (i64)((spasm_wtime() - t0) * 1e6);
+    return odd ? zp_neg(F, prod) : prod;
+}
+
+void det_stats_reset() { memset(g_det_stats, 0, sizeof g_det_stats); }
+
+// det[i] of every A[i].  Nothing is written before all is done.
+void det_run(int count, const struct spasm_csr *const *A, spasm_ZZp *det)
+{
+    det_stats_reset();
+    if (count < 0) throw EngineError("count < 0");
+    if (count == 0) return;
+    if (!A || !det) throw EngineError("NULL array");
+    for (int i = 0; i < count; i++) {
+        char msg[160];
+        if (const char *bad = batch_check(A[i])) {
+            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
+            throw EngineError(msg);
+        }
+        if (A[i]->n != A[i]->m) {
+            snprintf(msg, sizeof msg, "matrix %d: not square (%d x %d)", i, A[i]->n, A[i]->m);
+            throw EngineError(msg);
+        }
+    }
+    require_device();
+    std::vector<int> fast, slow;
+    for (int i = 0; i < count; i++) {
+        if ((i64)A[i]->n * A[i]->n <= BATCH_LIMIT) fast.push_back(i);
+        else slow.push_back(i);
+    }
+    i64 *st = g_det_stats;
+    st[0] = count;
+    st[1] = (i64)fast.size();
+    st[2] = (i64)slow.size();
+    std::vector<int> res((size_t)count, 0);
+    if (!fast.empty()) {
+        std::vector<const struct spasm_csr *> list;
+        for (int i : fast) list.push_back(A[i]);
+        BatchStaged in;
+        batch_stage(list, in);
+        std::vector<BatchItem> item;
+        for (size_t f = 0; f < list.size(); f++) item.push_back(BatchItem{list[f]->n, list[f]->m, in.row0[f], list[f]->field->p});
+        std::vector<int> d;
+        det_fast(item, in.P, in.J, in.X, d);
+        for (size_t f = 0; f < fast.size(); f++) res[(size_t)fast[f]] = d[f];
+    }
+    for (int i : slow) res[(size_t)i] = det_general(A[i]);
+    for (int i = 0; i < count; i++) det[i] = res[(size_t)i];
+}
+
+// The determinant of the matrix behind the handle: the product of its blocks' determinants times the parities of the row and the
+// column permutation that bring it to block-diagonal form (row i to row_start[row_block[i]] + row_pos[i], columns alike).  A block
+// that is not square, or a row or column without entry (a block of its own, 1 x 0 or 0 x 1), makes it 0 and nothing is eliminated.
+void blocks_det(spasm_amd_blocks *B, spasm_ZZp *det)
+{
+    det_stats_reset();
+    blocks_need(B);
+    if (!det) throw EngineError("NULL array");
+    if (B->n != B->m) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "not square (%d x %d)", B->n, B->m);
+        throw EngineError(msg);
+    }
+    i64 *st = g_det_stats;
+    const int count = B->nb;
+    const ZpField F = zp_field_make(B->prime);
+    st[0] = count;
+    std::vector<int> fast, slow;
+    std::vector<BatchItem> item;
+    for (int b = 0; b < count; b++) {
+        const i64 rn = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b], cn = B->h_col_start[(size_t)b + 1] - B->h_col_start[(size_t)b];
+        if (rn != cn || B->h_nnz[(size_t)b] == 0) st[3]++;
+        else if (rn * rn <= BATCH_LIMIT) {
+            fast.push_back(b);
+            item.push_back(BatchItem{(int)rn, (int)cn, B->h_row_start[(size_t)b] + b, B->prime});
+        } else slow.push_back(b);
+    }
+    if (st[3] > 0) { *det = 0; return; }
+    st[1] = (i64)fast.size();
+    st[2] = (i64)slow.size();
+    int prod = 1;
+    std::vector<int> d;
+    det_fast(item, B->P.p, B->J.p, B->X.p, d);
+    for (int v : d) prod = zp_mul(F, prod, v);
+    for (int b : slow) {
+        if (prod == 0) break;
+        std::unique_ptr<struct spasm_csr, void (*)(struct spasm_csr *)> M(blocks_fetch(B, b), spasm_csr_free);
+        prod = zp_mul(F, prod, det_general(M.get()));
+    }
+    if (prod != 0 && B->n > 0) {
+        // the four maps come to the host for the two parities: 16 bytes per row of A
+        const double t0 = spasm_wtime();
+        hipStream_t s = nullptr;
+        const size_t n = (size_t)B->n;
+        std::vector<int> blk(n), pos(n);
+        std::vector<i64> perm(n);
+        int odd = 0;
+        for (int side = 0; side < 2; side++) {
+            blocks_copy_out(blk.data(), side ? B->col_block : B->row_block, n, s);
+            blocks_copy_out(pos.data(), side ? B->col_pos : B->row_pos, n, s);
+            HIPCHK(hipStreamSynchronize(s));
+            const std::vector<i64> &start = side ? B->h_col_start : B->h_row_start;
+            for (size_t i = 0; i < n; i++) {
+                if (blk[i] < 0 || blk[i] >= count) throw EngineError("internal error: a map of the determinant is no permutation");
+                perm[i] = start[(size_t)blk[i]] + pos[i];
+            }
+            odd ^= det_perm_parity(perm);
+        }
+        if (odd) prod = zp_neg(F, prod);
+        st[6] += (i64)((spasm_wtime() - t0) * 1e6);
+    }
+    *det = prod;
+}
+
+// split, then blocks_det on a handle that lives for the call (the split is not part of the stats; the handle's info has it)
+template <class Make> void det_split(Make &&make, spasm_ZZp *det)
+{
+    std::unique_ptr<spasm_amd_blocks> B(make());
+    blocks_det(B.get(), det);
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- determinants mod p (det.hpp; engine extension): the caller's device is put back, none is selected ----
+SPASM_API int spasm_amd_det_batch(int count, const struct spasm_csr *const *A, spasm_ZZp *det)
+{
+    return abi_call("spasm_amd_det_batch", -1, [&] { DeviceGuard g; det_run(count, A, det); return 0; });
+}
+
+SPASM_API int spasm_amd_det(const struct spasm_csr *A, spasm_ZZp *det)
+{
+    return abi_call("spasm_amd_det", -1, [&] {
+        DeviceGuard g;
+        det_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        if (!det) throw EngineError("NULL array");
+        if (A->n != A->m) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "not square (%d x %d)", A->n, A->m);
+            throw EngineError(msg);
+        }
+        det_split([&] { return blocks_create(A); }, det);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_blocks_det(spasm_amd_blocks *B, spasm_ZZp *det)
+{
+    return abi_call("spasm_amd_blocks_det", -1, [&] { DeviceGuard g(B); blocks_det(B, det); return 0; });
+}
+
+SPASM_API int spasm_amd_dcsr_det(const spasm_amd_dcsr *D, spasm_ZZp *det)
+{
+    return abi_call("spasm_amd_dcsr_det", -1, [&] {
+        DeviceGuard g(D);
+        det_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        if (!det) throw EngineError("NULL array");
+        if (D->n != D->m) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "not square (%d x %d)", D->n, D->m);
+            throw EngineError(msg);
+        }
+        det_split([&] { return blocks_create_dcsr(D); }, det);
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_det_stats(i64 *out)
+{
+    if (out) memcpy(out, g_det_stats, sizeof g_det_stats);
+}
+
+} // extern "C"
