@@ -807,6 +807,34 @@ int spasm_amd_blocks_det(spasm_amd_blocks *B, spasm_ZZp *det);
 int spasm_amd_dcsr_det(const spasm_amd_dcsr *D, spasm_ZZp *det);
 void spasm_amd_det_stats(i64 *out);   /* of the last det call of this thread */
 
+/* ---- Engine extension: characteristic polynomials mod p (csrc/charpoly.hpp) ----
+ * chi_A(x) = det(x * I - A) of a square matrix: monic of degree n, returned as n + 1 balanced residues, low degree first, the last
+ * one 1 (the 0 x 0 matrix: {1}).  The matrix is brought to upper Hessenberg form by similarity (first non-zero below the diagonal
+ * as pivot, row operations followed by the inverse column operations) and chi is read off by the recurrence over the leading
+ * principal minors.  Field operations only: every prime 2 < p <= 0xFFFFFFFB works, p <= n included.  The matrices of one batch may
+ * differ in size and in prime.
+ *   LDS path      a matrix with n * n <= 32768 (n <= 181) is ONE workgroup in LDS, classed and launched like spasm_amd_rank_batch;
+ *                 all such matrices of a call in at most four launches
+ *   global path   a larger matrix, n <= 1024, is one workgroup of 512 on a dense image of its own in device memory (4 MiB at most),
+ *                 all of them in one launch: exact, not fast.  There is no multi-workgroup reduction for large n and no split by
+ *                 components.
+ *   charpoly_batch  coef[i][0 .. A[i]->n] for A[0 .. count); every coef[i] has room for A[i]->n + 1 words, owned by the caller
+ *   charpoly        one matrix; dcsr_charpoly: a resident matrix, on its device, no entry crosses the host
+ *   values        any int32 is accepted and reduced on load; a row must not hold a column twice
+ *   stats         of the last charpoly call of this thread: out[8] = matrices, of them through the LDS path, through the global
+ *                 path, launches, device microseconds of the LDS path (HIP events), of the global path, 0, 0
+ *   deterministic two runs give the same values
+ *   errors        count < 0, a NULL array, a NULL matrix, A->x == NULL, a malformed matrix, a prime outside 3 .. 0xFFFFFFFB, a
+ *                 column index outside the matrix, a matrix that is not square ("matrix 3: not square (3 x 2)"), a NULL coef[i],
+ *                 n > 1024 ("matrix 3: characteristic polynomial limited to n <= 1024 (n = 1025)"), no device ("no HIP device"),
+ *                 out of memory: -1, NO output slot is written, spasm_amd_last_error() names the cause (and the index of the
+ *                 matrix).  All but the last two are found before a device is looked for.  count == 0 succeeds (and needs no
+ *                 device).  After success the error text is empty. */
+int spasm_amd_charpoly_batch(int count, const struct spasm_csr *const *A, spasm_ZZp *const *coef);
+int spasm_amd_charpoly(const struct spasm_csr *A, spasm_ZZp *coef);
+int spasm_amd_dcsr_charpoly(const spasm_amd_dcsr *D, spasm_ZZp *coef);
+void spasm_amd_charpoly_stats(i64 *out);   /* of the last charpoly call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -307,6 +307,10 @@ SIGNATURES = {
     "spasm_amd_blocks_det": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
     "spasm_amd_dcsr_det": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
     "spasm_amd_det_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_charpoly_batch": (C.c_int32, [C.c_int32, _P(_P(CsrStruct)), _P(_P(C.c_int32))]),
+    "spasm_amd_charpoly": (C.c_int32, [_P(CsrStruct), _P(C.c_int32)]),
+    "spasm_amd_dcsr_charpoly": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_charpoly_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

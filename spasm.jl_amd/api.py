@@ -1895,3 +1895,62 @@ def det_stats():
 
 DeviceCSR.det = det
 DeviceBlocks.det = det
+
+
+# ---------------------------------------------------------------------------------------------
+# Characteristic polynomials mod p  (spasm_amd_charpoly*; csrc/charpoly.hpp; engine extension)
+# ---------------------------------------------------------------------------------------------
+CHARPOLY_STATS = ("items", "lds_path", "global_path", "launches", "lds_device_us", "global_device_us", "spare0", "spare1")
+
+
+def charpoly_batch(mats):
+    """charpoly_batch([A, ...]) -> list of numpy int32 arrays: the n + 1 coefficients of det(x * I - A) mod p as balanced residues,
+    low degree first, the last one 1 (spasm_amd_charpoly_batch).  Square matrices with n * n <= 32768 are reduced to Hessenberg form
+    inside LDS, one workgroup each; larger ones (n <= 1024) by one workgroup on an image in device memory.  The matrices may differ
+    in size and in prime."""
+    mats = list(mats)
+    for A in mats:
+        if not isinstance(A, CSR):
+            raise TypeError("a list of CSR expected")
+    arr = (C.POINTER(_abi.CsrStruct) * max(len(mats), 1))(*[A.data for A in mats])
+    # (a matrix the entry will refuse still gets a slot, so that the refusal is the entry's)
+    outs = [np.zeros(max(A.n, 0) + 1, dtype=np.int32) for A in mats]
+    ptrs = (C.POINTER(C.c_int32) * max(len(mats), 1))(*[o.ctypes.data_as(C.POINTER(C.c_int32)) for o in outs])
+    with _quiet(True):
+        rc = _abi.lib().spasm_amd_charpoly_batch(len(mats), arr, ptrs)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_charpoly_batch failed")
+    return outs
+
+
+def charpoly(A):
+    """charpoly(A) -> numpy int32 array of the n + 1 coefficients of det(x * I - A) mod p as balanced residues, low degree first.
+    A CSR (spasm_amd_charpoly) or a DeviceCSR (spasm_amd_dcsr_charpoly: on its device, no entry crosses the host)."""
+    lib = _abi.lib()
+    if isinstance(A, CSR):
+        n = A.n
+    elif isinstance(A, DeviceCSR):
+        A._need()
+        n = A.shape[0]
+    else:
+        raise TypeError("a CSR or a DeviceCSR expected")
+    out = np.zeros(max(n, 0) + 1, dtype=np.int32)
+    ptr = out.ctypes.data_as(C.POINTER(C.c_int32))
+    with _quiet(True):
+        if isinstance(A, CSR):
+            who, rc = "spasm_amd_charpoly", lib.spasm_amd_charpoly(A.data, ptr)
+        else:
+            who, rc = "spasm_amd_dcsr_charpoly", lib.spasm_amd_dcsr_charpoly(A._need(), ptr)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return out
+
+
+def charpoly_stats():
+    """Counters of the last charpoly call of this thread (spasm_amd_charpoly_stats), as a dict keyed by CHARPOLY_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_charpoly_stats(out)
+    return {k: int(v) for k, v in zip(CHARPOLY_STATS, out)}
+
+
+DeviceCSR.charpoly = charpoly

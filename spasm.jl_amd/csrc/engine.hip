@@ -10054,3 +10054,213 @@ SPASM_API void spasm_amd_det_stats(i64 *out)
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Characteristic polynomials mod p (charpoly.hpp): chi_A(x) = det(x * I - A) of many small matrices in one call, of one matrix, of
+// a resident matrix.  A matrix whose image fits LDS (n * n <= BATCH_LIMIT) is one workgroup of k_batch_charpoly, staged, classed
+// and launched by the batch's driver; a larger one (n <= CHARPOLY_NMAX) is one workgroup of k_charpoly_global on an image of its
+// own in device memory, all of them in one launch.  The n + 1 coefficients of every matrix come back in one download.
+// ------------------------------------------------------------------------------------------------
+#include "charpoly.hpp"
+
+namespace {
+
+// matrices, of them LDS path, of them global path, launches, device us of the LDS path, of the global path, 0, 0
+thread_local i64 g_charpoly_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+const ElimKernels<CharpolyArgs> kBatchCharpoly = {{k_batch_charpoly<64>, k_batch_charpoly<128>, k_batch_charpoly<256>, k_batch_charpoly<512>}};
+
+void charpoly_stats_reset() { memset(g_charpoly_stats, 0, sizeof g_charpoly_stats); }
+
+void charpoly_check_size(int i, int n)
+{
+    if (n <= CHARPOLY_NMAX) return;
+    char msg[160];
+    if (i >= 0) snprintf(msg, sizeof msg, "matrix %d: characteristic polynomial limited to n <= %d (n = %d)", i, CHARPOLY_NMAX, n);
+    else snprintf(msg, sizeof msg, "characteristic polynomial limited to n <= %d (n = %d)", CHARPOLY_NMAX, n);
+    throw EngineError(msg);
+}
+
+// item[f] describes the f-th matrix (m = n) of a concatenated CSR on the device, its entries as columns dJ and values dX or packed
+// as dE; out[f] = its n + 1 coefficients.  The counters are set here.
+void charpoly_device(const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, const int2 *dE, std::vector<std::vector<int>> &out)
+{
+    const int nf = (int)item.size();
+    out.assign((size_t)nf, std::vector<int>());
+    i64 *st = g_charpoly_stats;
+    st[0] = nf;
+    if (nf == 0) return;
+    for (int c = 0; c < BATCH_NCLASS; c++) {
+        int bw, rmax;
+        batch_layout(c, bw, rmax);
+        if (rmax > 2 * bw) throw EngineError("internal error: the work words of a characteristic polynomial do not fit a class");
+    }
+    hipStream_t s = nullptr;
+    // the LDS items first, then the global ones
+    std::vector<int> order;
+    for (int f = 0; f < nf; f++)
+        if ((i64)item[(size_t)f].n * item[(size_t)f].n <= BATCH_LIMIT) order.push_back(f);
+    const int nl = (int)order.size();
+    for (int f = 0; f < nf; f++)
+        if ((i64)item[(size_t)f].n * item[(size_t)f].n > BATCH_LIMIT) order.push_back(f);
+    std::vector<BatchDesc> desc((size_t)nf);
+    std::vector<unsigned char> cls((size_t)nf, 0);
+    std::vector<int> items((size_t)nf);
+    i64 words = 0, image = 0;
+    for (int q = 0; q < nf; q++) {
+        const BatchItem *M = &item[(size_t)order[(size_t)q]];
+        BatchDesc &d = desc[(size_t)q];
+        memset(&d, 0, sizeof d);
+        const int n = M->n;
+        d.n = d.m = n;
+        d.F = zp_field_make(M->prime);
+        d.row0 = M->row0;
+        d.rec = words;
+        words += (i64)n + 1;
+        if (q < nl) {
+            d.ld = (n % 2 == 0 && (i64)n * (n + 1) <= BATCH_PAD_CAP) ? n + 1 : n;
+            const i64 key = std::max<i64>((i64)n * d.ld, n);
+            int c = 0;
+            while (key > kBatchClass[c].cap) c++;
+            cls[(size_t)q] = (unsigned char)c;
+        } else {
+            d.ld = n | 1;
+            d.slice = image;
+            image += (i64)n * d.ld;
+            items[(size_t)q] = q;
+        }
+    }
+    DevBuf<BatchDesc> d_desc;
+    DevBuf<int> d_items, d_coef, d_img;
+    d_desc.alloc((size_t)nf);
+    d_items.alloc((size_t)nf);
+    d_coef.alloc((size_t)words);
+    if (image > 0) d_img.alloc((size_t)image);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+    CharpolyArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = d_desc.p;
+    a.P = dP;
+    a.J = dJ;
+    a.X = dX;
+    a.E = dE;
+    a.coef = d_coef.p;
+    a.gimg = d_img.p;
+    SpgEvents ev;
+    int launches = 0;
+    if (nl > 0) {
+        launches += batch_launch_jobs(kBatchCharpoly, cls, 0, nl, items, d_items.p, a, ev.e[0], s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+    }
+    if (nf > nl) {
+        HIPCHK(hipMemcpyAsync(d_items.p + nl, items.data() + nl, (size_t)(nf - nl) * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        a.items = d_items.p + nl;
+        hipLaunchKernelGGL(k_charpoly_global, dim3(nf - nl), dim3(512), 0, s, a);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(ev.e[3], s));
+        launches++;
+    }
+    std::vector<int> coef((size_t)words);
+    HIPCHK(hipMemcpyAsync(coef.data(), d_coef.p, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    st[1] = nl;
+    st[2] = nf - nl;
+    st[3] = launches;
+    if (nl > 0) st[4] = (i64)(ev.ms(0, 1) * 1000.0);
+    if (nf > nl) st[5] = (i64)(ev.ms(2, 3) * 1000.0);
+    for (int q = 0; q < nf; q++) {
+        const BatchDesc &d = desc[(size_t)q];
+        out[(size_t)order[(size_t)q]].assign(coef.begin() + d.rec, coef.begin() + d.rec + d.n + 1);
+    }
+}
+
+// coef[i][0 .. n_i] of every A[i].  Nothing is written before all is done.
+void charpoly_run(int count, const struct spasm_csr *const *A, spasm_ZZp *const *coef)
+{
+    charpoly_stats_reset();
+    if (count < 0) throw EngineError("count < 0");
+    if (count == 0) return;
+    if (!A || !coef) throw EngineError("NULL array");
+    for (int i = 0; i < count; i++) {
+        char msg[160];
+        if (const char *bad = batch_check(A[i])) {
+            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
+            throw EngineError(msg);
+        }
+        if (A[i]->n != A[i]->m) {
+            snprintf(msg, sizeof msg, "matrix %d: not square (%d x %d)", i, A[i]->n, A[i]->m);
+            throw EngineError(msg);
+        }
+        if (!coef[i]) {
+            snprintf(msg, sizeof msg, "matrix %d: NULL array", i);
+            throw EngineError(msg);
+        }
+        charpoly_check_size(i, A[i]->n);
+    }
+    require_device();
+    std::vector<const struct spasm_csr *> list(A, A + count);
+    BatchStaged in;
+    batch_stage(list, in);
+    std::vector<BatchItem> item;
+    for (int i = 0; i < count; i++) item.push_back(BatchItem{A[i]->n, A[i]->m, in.row0[(size_t)i], A[i]->field->p});
+    std::vector<std::vector<int>> res;
+    charpoly_device(item, in.P, in.J, in.X, nullptr, res);
+    for (int i = 0; i < count; i++) memcpy(coef[i], res[(size_t)i].data(), res[(size_t)i].size() * sizeof(int));
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- characteristic polynomials mod p (charpoly.hpp; engine extension): the caller's device is put back, none is selected ----
+SPASM_API int spasm_amd_charpoly_batch(int count, const struct spasm_csr *const *A, spasm_ZZp *const *coef)
+{
+    return abi_call("spasm_amd_charpoly_batch", -1, [&] { DeviceGuard g; charpoly_run(count, A, coef); return 0; });
+}
+
+SPASM_API int spasm_amd_charpoly(const struct spasm_csr *A, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_charpoly", -1, [&] {
+        DeviceGuard g;
+        charpoly_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        if (!coef) throw EngineError("NULL array");
+        if (A->n != A->m) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "not square (%d x %d)", A->n, A->m);
+            throw EngineError(msg);
+        }
+        charpoly_check_size(-1, A->n);
+        charpoly_run(1, &A, &coef);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_charpoly(const spasm_amd_dcsr *D, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_dcsr_charpoly", -1, [&] {
+        DeviceGuard g(D);
+        charpoly_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        if (!coef) throw EngineError("NULL array");
+        if (D->n != D->m) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "not square (%d x %d)", D->n, D->m);
+            throw EngineError(msg);
+        }
+        charpoly_check_size(-1, D->n);
+        std::vector<BatchItem> item(1, BatchItem{D->n, D->m, 0, D->F.p});
+        std::vector<std::vector<int>> res;
+        charpoly_device(item, D->p.p, nullptr, nullptr, D->ent.p, res);
+        memcpy(coef, res[0].data(), res[0].size() * sizeof(int));
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_charpoly_stats(i64 *out)
+{
+    if (out) memcpy(out, g_charpoly_stats, sizeof g_charpoly_stats);
+}
+
+} // extern "C"
