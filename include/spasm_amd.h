@@ -835,6 +835,54 @@ int spasm_amd_charpoly(const struct spasm_csr *A, spasm_ZZp *coef);
 int spasm_amd_dcsr_charpoly(const spasm_amd_dcsr *D, spasm_ZZp *coef);
 void spasm_amd_charpoly_stats(i64 *out);   /* of the last charpoly call of this thread */
 
+/* ---- Engine extension: characteristic polynomials by components (csrc/blocks.hpp, csrc/polyprod.hpp) ----
+ * The split of spasm_amd_blocks_create pairs rows with columns freely: rank and determinant (up to sign) survive it, the spectrum
+ * does not.  The INDEX split takes row i and column i as one vertex: the graph of spasm_amd_blocks_create (every stored entry
+ * (i, j), explicit zeros included, joins row i and column j) plus the edge row i - column i for every i.  Its components are sets
+ * S_b of indices, A is diag(A[S_0,S_0], A[S_1,S_1], ..) up to a simultaneous permutation of rows and columns, and
+ * chi_A = prod_b chi_{A[S_b,S_b]}.
+ *   create_index  same arguments and handle type as spasm_amd_blocks_create / _create_dcsr; n == m is required ("not square
+ *                 (3 x 2)", found before a device is looked for).  Every block is square; block_rows and block_cols hold the same
+ *                 indices block for block; row_pos[i] == col_pos[i] and row_block[i] == col_block[i]; blocks ascend by smallest
+ *                 index; there is no 1 x 0 or 0 x 1 block (an index with neither row nor column entries is a 1 x 1 zero block);
+ *                 two handles of one matrix are byte-identical.  An index handle is an ordinary handle: rank, echelonize, kernel,
+ *                 solve, det, fetch, maps, shapes and spasm_amd_solver_create_blocks work on it unchanged (for det the two
+ *                 parities coincide).
+ *   is_index      1 for such a handle, 0 for a handle of spasm_amd_blocks_create / _create_dcsr, -1 for NULL
+ *   poly_product  out[0 .. sum(len) - count] = the product of `count` polynomials mod prime as balanced residues, low degree
+ *                 first.  Polynomial k is len[k] >= 1 words f[k][..]; any int32 is reduced on load; it need not be monic and a
+ *                 zero leading word is allowed.  count == 0 gives {1} (and needs no device).  A product tree on the device:
+ *                 ceil(log2 count) levels, one launch each, every term reduced (no lazy accumulator: every accepted prime works).
+ *   blocks_charpoly_factors
+ *                 coef[n + nblocks]: the polynomial of block b (rows_b + 1 words, monic) at row_start[b] + b
+ *   blocks_charpoly
+ *                 coef[n + 1] = chi_A.  The blocks go to the kernels of spasm_amd_charpoly_batch straight from the handle (LDS path
+ *                 for rows^2 <= 32768, global path up to 1024 rows, one launch); the factors are multiplied on the device; only
+ *                 the result is downloaded.  n == 0 gives {1} with no launch.
+ *   charpoly_split, dcsr_charpoly_split
+ *                 create_index followed by blocks_charpoly; the resident matrix on its device, no entry crosses the host.  Unlike
+ *                 spasm_amd_charpoly there is no limit on n, only on the rows of a block.
+ *   stats         of the last call of this thread: out[8] = blocks, of them on the LDS path, on the global path, launches of the
+ *                 charpoly kernels, their device microseconds (HIP events), product levels, product device microseconds, 0.  The
+ *                 split's own time is in spasm_amd_blocks_info.
+ *   deterministic two runs give the same values
+ *   errors        poly_product: count < 0, a NULL array, a NULL f[k] ("polynomial 3: NULL array"), len[k] < 1, a prime outside
+ *                 3 .. 0xFFFFFFFB, a total length >= 2^31, no device, out of memory.  charpoly: a NULL handle, a NULL coef, a handle
+ *                 that is not an index split ("spasm_amd_blocks_charpoly: the handle is not an index split
+ *                 (spasm_amd_blocks_create_index)"), a block with more than 1024 rows ("block 3: characteristic polynomial limited
+ *                 to n <= 1024 (n = 1025)"): both found from the handle before any elimination.  -1 (NULL for the creators), NO
+ *                 output word is written, spasm_amd_last_error() names the cause and the index.  All but "no device" and "out of
+ *                 memory" are found before a device is looked for. */
+spasm_amd_blocks *spasm_amd_blocks_create_index(const struct spasm_csr *A);
+spasm_amd_blocks *spasm_amd_blocks_create_index_dcsr(const spasm_amd_dcsr *D);
+int spasm_amd_blocks_is_index(const spasm_amd_blocks *B);
+int spasm_amd_poly_product(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out);
+int spasm_amd_blocks_charpoly(spasm_amd_blocks *B, spasm_ZZp *coef);
+int spasm_amd_blocks_charpoly_factors(spasm_amd_blocks *B, spasm_ZZp *coef);
+int spasm_amd_charpoly_split(const struct spasm_csr *A, spasm_ZZp *coef);
+int spasm_amd_dcsr_charpoly_split(const spasm_amd_dcsr *D, spasm_ZZp *coef);
+void spasm_amd_charpoly_split_stats(i64 *out);   /* of the last split charpoly call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -311,6 +311,15 @@ SIGNATURES = {
     "spasm_amd_charpoly": (C.c_int32, [_P(CsrStruct), _P(C.c_int32)]),
     "spasm_amd_dcsr_charpoly": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
     "spasm_amd_charpoly_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_blocks_create_index": (C.c_void_p, [_P(CsrStruct)]),
+    "spasm_amd_blocks_create_index_dcsr": (C.c_void_p, [C.c_void_p]),
+    "spasm_amd_blocks_is_index": (C.c_int32, [C.c_void_p]),
+    "spasm_amd_poly_product": (C.c_int32, [C.c_int32, _P(C.c_int32), _P(_P(C.c_int32)), C.c_int64, _P(C.c_int32)]),
+    "spasm_amd_blocks_charpoly": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_blocks_charpoly_factors": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_charpoly_split": (C.c_int32, [_P(CsrStruct), _P(C.c_int32)]),
+    "spasm_amd_dcsr_charpoly_split": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_charpoly_split_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -1214,14 +1214,16 @@ class DeviceBlocks:
     DeviceBlocks(A) takes a CSR (uploaded; it may be dropped afterwards) or a DeviceCSR (no upload).  The blocks stay on the device
     as one concatenated CSR in the batch's layout: rank(), echelonize(), kernel() give what rank_batch, echelonize_batch,
     kernel_batch give for the list of blocks, without the entries crossing the host.  to_block() builds the Block that
-    Block.from_csr(A) builds; maps(), shapes(), fetch(b), info() read the handle."""
+    Block.from_csr(A) builds; maps(), shapes(), fetch(b), info() read the handle.
+    index=True (a square A): the index split (spasm_amd_blocks_create_index), where row i and column i are one vertex, so that A is
+    block diagonal up to a SIMULTANEOUS permutation; only such a handle has charpoly() and charpoly_factors()."""
 
-    def __init__(self, A):
+    def __init__(self, A, index=False):
         lib = _abi.lib()
         if isinstance(A, CSR):
-            self._h = lib.spasm_amd_blocks_create(A.data)
+            self._h = (lib.spasm_amd_blocks_create_index if index else lib.spasm_amd_blocks_create)(A.data)
         elif isinstance(A, DeviceCSR):
-            self._h = lib.spasm_amd_blocks_create_dcsr(A._need())
+            self._h = (lib.spasm_amd_blocks_create_index_dcsr if index else lib.spasm_amd_blocks_create_dcsr)(A._need())
         else:
             raise TypeError("a CSR or a DeviceCSR expected")
         if not self._h:
@@ -1257,6 +1259,33 @@ class DeviceBlocks:
 
     def __len__(self):
         return self._nb
+
+    @property
+    def index(self):
+        """True for the index split (spasm_amd_blocks_is_index)"""
+        return _abi.lib().spasm_amd_blocks_is_index(self._need()) == 1
+
+    def charpoly(self):
+        """The n + 1 coefficients of det(x * I - A) mod p of the matrix behind an index handle (spasm_amd_blocks_charpoly): the
+        product of the blocks' characteristic polynomials, formed on the device."""
+        out = np.zeros(self.shape[0] + 1, dtype=np.int32)
+        with _quiet(True):
+            rc = _abi.lib().spasm_amd_blocks_charpoly(self._need(), out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_charpoly failed")
+        return out
+
+    def charpoly_factors(self):
+        """[characteristic polynomial of block b, ...] as int32 arrays of rows_b + 1 words (spasm_amd_blocks_charpoly_factors)"""
+        n, nb = self.shape[0], self._nb
+        out = np.zeros(max(n + nb, 1), dtype=np.int32)
+        with _quiet(True):
+            rc = _abi.lib().spasm_amd_blocks_charpoly_factors(self._need(), out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or "spasm_amd_blocks_charpoly_factors failed")
+        rows = self.shapes()[0].tolist()
+        start = np.concatenate(([0], np.cumsum(rows))).astype(np.int64)
+        return [out[int(start[b]) + b: int(start[b]) + b + rows[b] + 1].copy() for b in range(nb)]
 
     def info(self):
         out = (C.c_int64 * 11)()
@@ -1923,10 +1952,25 @@ def charpoly_batch(mats):
     return outs
 
 
-def charpoly(A):
+def charpoly(A, split=False):
     """charpoly(A) -> numpy int32 array of the n + 1 coefficients of det(x * I - A) mod p as balanced residues, low degree first.
-    A CSR (spasm_amd_charpoly) or a DeviceCSR (spasm_amd_dcsr_charpoly: on its device, no entry crosses the host)."""
+    A CSR (spasm_amd_charpoly) or a DeviceCSR (spasm_amd_dcsr_charpoly: on its device, no entry crosses the host).
+    split=True: A is split by the components of its index graph first and the blocks' polynomials are multiplied on the device
+    (spasm_amd_charpoly_split / _dcsr_charpoly_split): no limit on n, only on the rows of a block (1024)."""
     lib = _abi.lib()
+    if split:
+        if isinstance(A, CSR):
+            who, fn, arg, n = "spasm_amd_charpoly_split", lib.spasm_amd_charpoly_split, A.data, A.n
+        elif isinstance(A, DeviceCSR):
+            who, fn, arg, n = "spasm_amd_dcsr_charpoly_split", lib.spasm_amd_dcsr_charpoly_split, A._need(), A.shape[0]
+        else:
+            raise TypeError("a CSR or a DeviceCSR expected")
+        out = np.zeros(max(n, 0) + 1, dtype=np.int32)
+        with _quiet(True):
+            rc = fn(arg, out.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc != 0:
+            raise SpasmError(_abi.last_error() or f"{who} failed")
+        return out
     if isinstance(A, CSR):
         n = A.n
     elif isinstance(A, DeviceCSR):
@@ -1954,3 +1998,32 @@ def charpoly_stats():
 
 
 DeviceCSR.charpoly = charpoly
+
+
+# ---------------------------------------------------------------------------------------------
+# Characteristic polynomials by components  (spasm_amd_poly_product, _charpoly_split*; csrc/polyprod.hpp; engine extension)
+# ---------------------------------------------------------------------------------------------
+CHARPOLY_SPLIT_STATS = ("blocks", "lds_path", "global_path", "launches", "charpoly_device_us", "product_levels", "product_device_us", "spare")
+
+
+def poly_product(polys, prime):
+    """poly_product([f, ...], prime) -> numpy int32 array: the product of the polynomials mod prime as balanced residues, low
+    degree first (spasm_amd_poly_product: a product tree on the device).  Every f is a non-empty sequence of integers that fit
+    int32; [] gives [1]."""
+    polys = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for f in polys]
+    count = len(polys)
+    lens = (C.c_int32 * max(count, 1))(*[len(f) for f in polys])
+    ptrs = (C.POINTER(C.c_int32) * max(count, 1))(*[f.ctypes.data_as(C.POINTER(C.c_int32)) for f in polys])
+    out = np.zeros(max(sum(len(f) for f in polys) - count + 1, 1), dtype=np.int32)
+    with _quiet(True):
+        rc = _abi.lib().spasm_amd_poly_product(count, lens, ptrs, int(prime), out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_poly_product failed")
+    return out
+
+
+def charpoly_split_stats():
+    """Counters of the last split charpoly call of this thread (spasm_amd_charpoly_split_stats), keyed by CHARPOLY_SPLIT_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_charpoly_split_stats(out)
+    return {k: int(v) for k, v in zip(CHARPOLY_SPLIT_STATS, out)}

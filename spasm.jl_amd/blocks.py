@@ -17,7 +17,8 @@ from . import api
 class Block:
     """blocks[b] with the maps row2block / col2block = (block, position, 0-based) and their inverses (src/blocks.jl:1-7)."""
 
-    def __init__(self, blocks, row2block, col2block, block2row, block2col):
+    def __init__(self, blocks, row2block, col2block, block2row, block2col, index=False):
+        self.index = index  # True: split by index (row i and column i are one vertex), see from_csr
         self.blocks = blocks
         self.row2block = row2block
         self.col2block = col2block
@@ -32,23 +33,52 @@ class Block:
         return (len(self.row2block), len(self.col2block))
 
     @classmethod
-    def from_csr(cls, A, device=False):
+    def from_csr(cls, A, device=False, index=False):
         """Block(A::CSR): union-find over rows and columns joined by the non-zeros (src/blocks.jl:35-105).
         Blocks are numbered by their smallest member in (rows, then columns) order.  device=True: the same Block, found and
-        split on the device (api.DeviceBlocks)."""
-        if device:
-            with api.DeviceBlocks(A) as D:
-                B = D.to_block()
-            return cls(B.blocks, B.row2block, B.col2block, B.block2row, B.block2col)
+        split on the device (api.DeviceBlocks).
+        index=True (a square A): row i and column i are one vertex, i.e. the graph gets the edge row i - column i for every i.  The
+        blocks are then A[S, S] for the components S of the index graph, A is block diagonal up to a SIMULTANEOUS permutation of rows
+        and columns, and charpoly(block) is the product of the blocks' characteristic polynomials.  On the host this is a plain
+        union-find in Python (the larger root goes under the smaller), independent of the device code."""
         n, m = A.shape
+        if index and n != m:
+            raise ValueError(f"not square ({n} x {m})")
+        if device:
+            with api.DeviceBlocks(A, index=index) as D:
+                B = D.to_block()
+            return cls(B.blocks, B.row2block, B.col2block, B.block2row, B.block2col, index=index)
         nz = api.nnz(A)
         p, j, x = A.p, A.j[:nz], A.x[:nz]
-        import scipy.sparse as sp
-        from scipy.sparse.csgraph import connected_components
+        if index:
+            parent = list(range(n + m))
 
-        rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(p))
-        G = sp.coo_matrix((np.ones(nz, dtype=np.int8), (rows, j.astype(np.int64) + n)), shape=(n + m, n + m))
-        ncomp, lab = connected_components(G, directed=False)
+            def find(v):
+                while parent[v] != v:
+                    parent[v] = parent[parent[v]]
+                    v = parent[v]
+                return v
+
+            def unite(a, b):
+                a, b = find(a), find(b)
+                if a != b:
+                    parent[max(a, b)] = min(a, b)
+
+            pl, jl = [int(v) for v in p[: n + 1]], j.tolist()
+            for i in range(n):
+                for k in range(pl[i], pl[i + 1]):
+                    unite(i, n + jl[k])  # every stored entry, whatever its value
+                unite(i, n + i)  # the tie
+            roots = [find(v) for v in range(n + m)]
+            number = {r: b for b, r in enumerate(sorted(set(roots)))}
+            ncomp, lab = len(number), np.array([number[r] for r in roots], dtype=np.int64)
+        else:
+            import scipy.sparse as sp
+            from scipy.sparse.csgraph import connected_components
+
+            rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(p))
+            G = sp.coo_matrix((np.ones(nz, dtype=np.int8), (rows, j.astype(np.int64) + n)), shape=(n + m, n + m))
+            ncomp, lab = connected_components(G, directed=False)
         first = np.full(ncomp, n + m, dtype=np.int64)
         np.minimum.at(first, lab, np.arange(n + m))
         renum = np.empty(ncomp, dtype=np.int64)
@@ -73,7 +103,7 @@ class Block:
             sp_ = np.concatenate([[0], np.cumsum(lens)]) if rws else np.zeros(1, dtype=np.int64)
             idx = np.concatenate([np.arange(p[i], p[i + 1]) for i in rws]) if rws and sp_[-1] else np.zeros(0, dtype=np.int64)
             blocks.append(api.CSR.from_arrays(len(rws), len(block2col[b]), sp_, colpos[j[idx]] if len(idx) else [], x[idx] if len(idx) else [], prime=A.prime))
-        return cls(blocks, row2block, col2block, block2row, block2col)
+        return cls(blocks, row2block, col2block, block2row, block2col, index=index)
 
     def to_csr(self):
         """CSR(block::Block{CSR}) (src/blocks.jl:142-170)."""
@@ -244,3 +274,20 @@ def det(block):
         if (n - cycles) % 2:
             value = -value % p
     return int(api.balanced(value, p))
+
+
+def charpoly(block):
+    """The n + 1 coefficients of det(x * I - A) mod p of the matrix the block was split from.  Only an INDEX split keeps the
+    spectrum: a DeviceBlocks made with index=True goes to the device entry (api.DeviceBlocks.charpoly); a host Block made with
+    Block.from_csr(A, index=True) takes ONE api.charpoly_batch call for its blocks and api.poly_product for their product.  A Block
+    without index is refused."""
+    if isinstance(block, api.DeviceBlocks):
+        return block.charpoly()
+    if not getattr(block, "index", False):
+        raise ValueError("the Block is not an index split (Block.from_csr(A, index=True)): its blocks do not carry the spectrum")
+    for X in block.blocks:
+        if not isinstance(X, api.CSR):
+            raise TypeError("a Block of CSR expected")
+    if not block.blocks:
+        return np.ones(1, dtype=np.int32)
+    return api.poly_product(api.charpoly_batch(block.blocks), block.blocks[0].prime)

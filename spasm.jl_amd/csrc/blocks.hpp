@@ -11,6 +11,8 @@
 //                                vertices are touched (the parent of a row is a row), the column words are read-only here.
 //   (c) k_blk_flatten            parent[v] = find(v), and root[v] = (find(v) == v)
 //   (d) an exclusive scan of root[] numbers the roots; k_blk_label gives every vertex the number of its root.
+// The index split (n == m, below) runs one more phase between (b) and (c), in a launch of its own:
+//   (t) k_blk_tie                unite(i, parent[n+i]) for every i: row i and column i end in one tree.
 //
 // The one hooking rule: unite(a, b) finds the two roots and hangs the LARGER root under the SMALLER one with
 // atomicCAS(&parent[hi], hi, lo); when the CAS fails (hi is no longer a root) it starts again from what the CAS returned.  find()
@@ -34,6 +36,29 @@
 // of unite (atomic at the L2, expected value = the vertex itself) fails and returns the newer parent: nothing is lost, the retry
 // goes on below.  An edge is never dropped: unite returns only when both ends had the same root or its own CAS succeeded.  What
 // one PHASE wrote is visible to the next because a kernel boundary lies between them; no fence is needed inside a kernel.
+//
+// Index split.  For a square matrix the graph gets the edge (i, n+i) for every i on top of the entries' edges: row i and column i
+// count as ONE vertex, the index i.  The components are then sets S_b of indices, A is diag(A[S_0,S_0], A[S_1,S_1], ..) up to a
+// SIMULTANEOUS permutation of rows and columns, and a similarity keeps the spectrum: chi_A = prod chi_{A[S_b,S_b]}.  (The free
+// split pairs rows with columns as it likes: rank and determinant up to sign survive, the characteristic polynomial does not --
+// the 3-cycle permutation matrix is three 1 x 1 blocks there and one 3 x 3 block here.)
+//   Why (t) is a launch of its own.  (b) rests on "the column words are read-only here".  The tie WRITES column words: a column
+//     without entries is its own root after (a), and unite(i, n+i) hooks it under the root of row i (n+i is the larger id).  After
+//     the kernel boundary behind (b) every column word is either a row that holds the column (hence, by (b), a vertex of the tree
+//     of every row that holds it) or the column itself.  In (t) the word parent[n+i] is read by thread i alone (no row ever gets a
+//     column as parent: a hook puts the larger id under the smaller, and every column id is above every row id) and written by
+//     thread i alone (the CAS of its own unite, from n+i to a row).  All other traffic of (t) is unite on row words, as in (b).
+//   The three properties.  Every write of (t) is still an atomic min of find or a CAS from v to something smaller, so the chain
+//     argument of Termination holds word for word (a failed CAS leaves both ends below hi).  The root is the minimum: the induction
+//     is over hooks, and (t) adds hooks of the same kind only.  After (t) both ends of every edge of the extended graph lie in one
+//     tree: an entry edge (i, n+j) because parent[n+j] is a row that (b) united with i (or became one of its tree in (t): trees
+//     only merge), a tie edge because unite(i, parent[n+i]) returned.  So the trees are the components of the extended graph and
+//     (c) leaves parent[v] = min of v's component: a function of the graph, not of the races of (a), (b), (t).  Stale reads: as
+//     below, nothing in the argument looks at which kernel wrote a value.
+//   Consequences.  Every component holds i together with n+i, so its smallest vertex is a row and row_block[i] == col_block[i].
+//     The two stable sorts then see the same keys in the same order: block_rows == block_cols block for block, every block is
+//     square, row_pos[i] == col_pos[i], and the blocks ascend by their smallest index.  There is no 1 x 0 or 0 x 1 block: an index
+//     with neither row nor column entries is a 1 x 1 zero block.  Two handles of one matrix are byte-identical, as before.
 //
 // Numbering (the contract of Block.from_csr).  Blocks in ascending order of their smallest vertex = ascending root id, rows before
 // columns; inside a block the rows and the columns keep their order in A.  A stable radix sort of (block number, index) for the rows
@@ -149,6 +174,14 @@ __global__ void k_blk_init(int nv, int *__restrict__ parent)
 {
     const i64d v = (i64d)blockIdx.x * blockDim.x + threadIdx.x;
     if (v < nv) parent[v] = (int)v;
+}
+
+// (t): the tie of the index split, row i with column i (n == m); the only phase that writes a column word after (a)
+__global__ void k_blk_tie(int n, int *parent)
+{
+    const i64d i = (i64d)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    blk_unite(parent, (int)i, blk_ld(parent + n + i));
 }
 
 // (c): every vertex straight under its root; root[v] = 1 for the roots (no hook happens here, so a root stays one)

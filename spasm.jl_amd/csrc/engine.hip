@@ -7284,6 +7284,7 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
 struct spasm_amd_blocks {
     int dev = 0;
     int n = 0, m = 0, nb = 0;
+    int index = 0;                                                                 // 1: the index split (row i tied to column i)
     i64 nnz = 0;
     i64 prime = 0;
     DevBuf<int> row_block, row_pos, col_block, col_pos, block_rows, block_cols;   // n, n, m, m, n, m
@@ -7323,12 +7324,15 @@ void blk_sort(DevBuf<unsigned char> &tmp, const int *key, int *key_out, const in
     HIPCHK(rocprim::radix_sort_pairs(tmp.p, bytes, key, key_out, val, val_out, (size_t)cnt, 0, bits, s));
 }
 
-// components, numbering and split of the n x m matrix (dP, dJ, dX) that lies on the current device
-spasm_amd_blocks *blocks_build(int n, int m, i64 nnz, i64 prime, const i64d *dP, const int *dJ, const int *dX)
+// components, numbering and split of the n x m matrix (dP, dJ, dX) that lies on the current device; index: the index split
+// (n == m, row i and column i are one vertex: the tie phase of blocks.hpp)
+spasm_amd_blocks *blocks_build(int n, int m, i64 nnz, i64 prime, const i64d *dP, const int *dJ, const int *dX, bool index)
 {
     hipStream_t s = nullptr;
     std::unique_ptr<spasm_amd_blocks> B(new spasm_amd_blocks());
     HIPCHK(hipGetDevice(&B->dev));
+    if (index && n != m) throw EngineError("internal error: an index split of a matrix that is not square");
+    B->index = index ? 1 : 0;
     B->n = n;
     B->m = m;
     B->nnz = nnz;
@@ -7372,6 +7376,7 @@ spasm_amd_blocks *blocks_build(int n, int m, i64 nnz, i64 prime, const i64d *dP,
         hipLaunchKernelGGL(k_blk_init, dim3(cdiv(nv, 256)), dim3(256), 0, s, nv, parent.p);
         blk_launch_rows<BLK_MINCOL>(a, nnz, s);
         blk_launch_rows<BLK_UNITE>(a, nnz, s);
+        if (index) hipLaunchKernelGGL(k_blk_tie, dim3(cdiv(n, 256)), dim3(256), 0, s, n, parent.p);
         hipLaunchKernelGGL(k_blk_flatten, dim3(cdiv(nv, 256)), dim3(256), 0, s, nv, parent.p, root.p);
         HIPCHK(hipGetLastError());
     }
@@ -7450,6 +7455,7 @@ spasm_amd_blocks *blocks_build(int n, int m, i64 nnz, i64 prime, const i64d *dP,
         if (b == 0 || z > B->big[2]) { B->big[0] = r; B->big[1] = c; B->big[2] = z; }
     }
     if (B->h_ent0[(size_t)nb] != nnz) throw EngineError("internal error: the blocks do not hold the entries of the matrix");
+    if (index && B->h_row_start != B->h_col_start) throw EngineError("internal error: a block of an index split is not square");
     return B.release();
 }
 
@@ -7467,9 +7473,18 @@ void blocks_check_host(const struct spasm_csr *A)
     if (A->p[A->n] > 0 && !A->j) throw EngineError("malformed matrix");
 }
 
-spasm_amd_blocks *blocks_create(const struct spasm_csr *A)
+void blocks_check_square(int n, int m)
+{
+    if (n == m) return;
+    char msg[96];
+    snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
+    throw EngineError(msg);
+}
+
+spasm_amd_blocks *blocks_create(const struct spasm_csr *A, bool index = false)
 {
     blocks_check_host(A);
+    if (index) blocks_check_square(A->n, A->m);
     require_device();
     hipStream_t s = nullptr;
     const int n = A->n, m = A->m;
@@ -7493,14 +7508,15 @@ spasm_amd_blocks *blocks_create(const struct spasm_csr *A)
         HIPCHK(hipStreamSynchronize(s));
         if (hbad) throw EngineError("a column index lies outside the matrix");
     }
-    return blocks_build(n, m, nnz, A->field->p, dp.p, dj.p, dx.p);
+    return blocks_build(n, m, nnz, A->field->p, dp.p, dj.p, dx.p, index);
 }
 
-spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D)
+spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D, bool index = false)
 {
     if (!D) throw EngineError("NULL matrix");
     if (D->F.p <= 2 || D->F.p > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
     if ((i64)D->n + (i64)D->m >= ((i64)1 << 31)) throw EngineError("n + m must be below 2^31");
+    if (index) blocks_check_square(D->n, D->m);
     hipStream_t s = nullptr;
     DevBuf<int> dj, dx;
     dj.alloc((size_t)D->nnz);
@@ -7509,7 +7525,7 @@ spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D)
         hipLaunchKernelGGL(k_spg_unpack, dim3((int)std::min<i64>(cdiv(D->nnz, 256), 65536)), dim3(256), 0, s, (i64d)D->nnz, (const int2 *)D->ent.p, dj.p, dx.p);
         HIPCHK(hipGetLastError());
     }
-    return blocks_build(D->n, D->m, D->nnz, D->F.p, D->p.p, dj.p, dx.p);
+    return blocks_build(D->n, D->m, D->nnz, D->F.p, D->p.p, dj.p, dx.p, index);
 }
 
 void blocks_need(const spasm_amd_blocks *B)
@@ -9604,6 +9620,19 @@ SPASM_API spasm_amd_blocks *spasm_amd_blocks_create_dcsr(const spasm_amd_dcsr *D
     return abi_call<spasm_amd_blocks *>("spasm_amd_blocks_create_dcsr", nullptr, [&] { DeviceGuard g(D); return blocks_create_dcsr(D); });
 }
 
+// the index split: row i and column i are one vertex (n == m); an ordinary handle otherwise
+SPASM_API spasm_amd_blocks *spasm_amd_blocks_create_index(const struct spasm_csr *A)
+{
+    return abi_call<spasm_amd_blocks *>("spasm_amd_blocks_create_index", nullptr, [&] { DeviceGuard g; return blocks_create(A, true); });
+}
+
+SPASM_API spasm_amd_blocks *spasm_amd_blocks_create_index_dcsr(const spasm_amd_dcsr *D)
+{
+    return abi_call<spasm_amd_blocks *>("spasm_amd_blocks_create_index_dcsr", nullptr, [&] { DeviceGuard g(D); return blocks_create_dcsr(D, true); });
+}
+
+SPASM_API int spasm_amd_blocks_is_index(const spasm_amd_blocks *B) { return B ? B->index : -1; }
+
 SPASM_API void spasm_amd_blocks_info(const spasm_amd_blocks *B, i64 *out)
 {
     if (!B || !out) return;
@@ -10081,31 +10110,52 @@ void charpoly_check_size(int i, int n)
     throw EngineError(msg);
 }
 
+// What the launches of one call hold until the stream has passed them: descriptors, item lists, the images of the global path, the
+// events around the two paths.  order[q] = which item descriptor q describes (the LDS items first, then the global ones).
+struct CharpolyJob {
+    std::vector<int> order, items;
+    std::vector<BatchDesc> desc;
+    DevBuf<BatchDesc> d_desc;
+    DevBuf<int> d_items, d_img;
+    SpgEvents ev;
+    int nl = 0, ng = 0, launches = 0;
+    // after the stream was synchronized: st[0 .. 5] as spasm_amd_charpoly_stats documents them
+    void stats(i64 *st)
+    {
+        st[0] = nl + ng;
+        st[1] = nl;
+        st[2] = ng;
+        st[3] = launches;
+        if (nl > 0) st[4] = (i64)(ev.ms(0, 1) * 1000.0);
+        if (ng > 0) st[5] = (i64)(ev.ms(2, 3) * 1000.0);
+    }
+};
+
 // item[f] describes the f-th matrix (m = n) of a concatenated CSR on the device, its entries as columns dJ and values dX or packed
-// as dE; out[f] = its n + 1 coefficients.  The counters are set here.
-void charpoly_device(const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, const int2 *dE, std::vector<std::vector<int>> &out)
+// as dE.  Its n + 1 coefficients go to d_coef[rec[f] ..] (rec == NULL: back to back in the order of `order`; `words` = their sum).
+// Launches only: the caller synchronizes the stream.
+void charpoly_launch(CharpolyJob &job, const std::vector<BatchItem> &item, const i64 *rec, const i64d *dP, const int *dJ, const int *dX, const int2 *dE, int *d_coef,
+                     hipStream_t s)
 {
     const int nf = (int)item.size();
-    out.assign((size_t)nf, std::vector<int>());
-    i64 *st = g_charpoly_stats;
-    st[0] = nf;
-    if (nf == 0) return;
     for (int c = 0; c < BATCH_NCLASS; c++) {
         int bw, rmax;
         batch_layout(c, bw, rmax);
         if (rmax > 2 * bw) throw EngineError("internal error: the work words of a characteristic polynomial do not fit a class");
     }
-    hipStream_t s = nullptr;
-    // the LDS items first, then the global ones
-    std::vector<int> order;
+    std::vector<int> &order = job.order;
     for (int f = 0; f < nf; f++)
         if ((i64)item[(size_t)f].n * item[(size_t)f].n <= BATCH_LIMIT) order.push_back(f);
     const int nl = (int)order.size();
     for (int f = 0; f < nf; f++)
         if ((i64)item[(size_t)f].n * item[(size_t)f].n > BATCH_LIMIT) order.push_back(f);
-    std::vector<BatchDesc> desc((size_t)nf);
+    job.nl = nl;
+    job.ng = nf - nl;
+    std::vector<BatchDesc> &desc = job.desc;
+    desc.resize((size_t)nf);
     std::vector<unsigned char> cls((size_t)nf, 0);
-    std::vector<int> items((size_t)nf);
+    std::vector<int> &items = job.items;
+    items.resize((size_t)nf);
     i64 words = 0, image = 0;
     for (int q = 0; q < nf; q++) {
         const BatchItem *M = &item[(size_t)order[(size_t)q]];
@@ -10115,7 +10165,7 @@ void charpoly_device(const std::vector<BatchItem> &item, const i64d *dP, const i
         d.n = d.m = n;
         d.F = zp_field_make(M->prime);
         d.row0 = M->row0;
-        d.rec = words;
+        d.rec = rec ? rec[order[(size_t)q]] : words;
         words += (i64)n + 1;
         if (q < nl) {
             d.ld = (n % 2 == 0 && (i64)n * (n + 1) <= BATCH_PAD_CAP) ? n + 1 : n;
@@ -10130,48 +10180,57 @@ void charpoly_device(const std::vector<BatchItem> &item, const i64d *dP, const i
             items[(size_t)q] = q;
         }
     }
-    DevBuf<BatchDesc> d_desc;
-    DevBuf<int> d_items, d_coef, d_img;
-    d_desc.alloc((size_t)nf);
-    d_items.alloc((size_t)nf);
-    d_coef.alloc((size_t)words);
-    if (image > 0) d_img.alloc((size_t)image);
-    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+    job.d_desc.alloc((size_t)nf);
+    job.d_items.alloc((size_t)nf);
+    if (image > 0) job.d_img.alloc((size_t)image);
+    HIPCHK(hipMemcpyAsync(job.d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
     CharpolyArgs a;
     memset(&a, 0, sizeof a);
-    a.desc = d_desc.p;
+    a.desc = job.d_desc.p;
     a.P = dP;
     a.J = dJ;
     a.X = dX;
     a.E = dE;
-    a.coef = d_coef.p;
-    a.gimg = d_img.p;
-    SpgEvents ev;
-    int launches = 0;
+    a.coef = d_coef;
+    a.gimg = job.d_img.p;
+    SpgEvents &ev = job.ev;
     if (nl > 0) {
-        launches += batch_launch_jobs(kBatchCharpoly, cls, 0, nl, items, d_items.p, a, ev.e[0], s);
+        job.launches += batch_launch_jobs(kBatchCharpoly, cls, 0, nl, items, job.d_items.p, a, ev.e[0], s);
         HIPCHK(hipEventRecord(ev.e[1], s));
     }
     if (nf > nl) {
-        HIPCHK(hipMemcpyAsync(d_items.p + nl, items.data() + nl, (size_t)(nf - nl) * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(job.d_items.p + nl, items.data() + nl, (size_t)(nf - nl) * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipEventRecord(ev.e[2], s));
-        a.items = d_items.p + nl;
+        a.items = job.d_items.p + nl;
         hipLaunchKernelGGL(k_charpoly_global, dim3(nf - nl), dim3(512), 0, s, a);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev.e[3], s));
-        launches++;
+        job.launches++;
     }
+}
+
+// out[f] = the n + 1 coefficients of the f-th matrix of charpoly_launch.  The counters are set here.
+void charpoly_device(const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, const int2 *dE, std::vector<std::vector<int>> &out)
+{
+    const int nf = (int)item.size();
+    out.assign((size_t)nf, std::vector<int>());
+    i64 *st = g_charpoly_stats;
+    st[0] = nf;
+    if (nf == 0) return;
+    hipStream_t s = nullptr;
+    i64 words = 0;
+    for (const BatchItem &M : item) words += (i64)M.n + 1;
+    DevBuf<int> d_coef;
+    d_coef.alloc((size_t)words);
+    CharpolyJob job;
+    charpoly_launch(job, item, nullptr, dP, dJ, dX, dE, d_coef.p, s);
     std::vector<int> coef((size_t)words);
     HIPCHK(hipMemcpyAsync(coef.data(), d_coef.p, (size_t)words * sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    st[1] = nl;
-    st[2] = nf - nl;
-    st[3] = launches;
-    if (nl > 0) st[4] = (i64)(ev.ms(0, 1) * 1000.0);
-    if (nf > nl) st[5] = (i64)(ev.ms(2, 3) * 1000.0);
+    job.stats(st);
     for (int q = 0; q < nf; q++) {
-        const BatchDesc &d = desc[(size_t)q];
-        out[(size_t)order[(size_t)q]].assign(coef.begin() + d.rec, coef.begin() + d.rec + d.n + 1);
+        const BatchDesc &d = job.desc[(size_t)q];
+        out[(size_t)job.order[(size_t)q]].assign(coef.begin() + d.rec, coef.begin() + d.rec + d.n + 1);
     }
 }
 
@@ -10261,6 +10320,293 @@ SPASM_API int spasm_amd_dcsr_charpoly(const spasm_amd_dcsr *D, spasm_ZZp *coef)
 SPASM_API void spasm_amd_charpoly_stats(i64 *out)
 {
     if (out) memcpy(out, g_charpoly_stats, sizeof g_charpoly_stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Characteristic polynomials by components (blocks.hpp: the index split; polyprod.hpp: the product tree).  The blocks of an index
+// handle go to the kernels of charpoly.hpp straight from the handle's concatenated CSR; the kernels write the factors into one
+// concatenated array (the polynomial of block b at row_start[b] + b), which the product tree reduces on the device.
+// ------------------------------------------------------------------------------------------------
+#include "polyprod.hpp"
+
+namespace {
+
+// blocks, of them LDS path, of them global path, launches of the charpoly kernels, their device us, product levels, product device us, 0
+thread_local i64 g_charpoly_split_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+void charpoly_split_stats_reset() { memset(g_charpoly_split_stats, 0, sizeof g_charpoly_split_stats); }
+
+// The descriptors of all levels of a product tree, from the lengths alone, and its launches.
+struct PolyProduct {
+    struct Level { size_t pair0, t0, w0; int tcnt, wcnt, tb, wb; };
+    std::vector<Level> level;
+    std::vector<PpPair> pair;          // level after level
+    std::vector<int> tsum, tpair, wsum, wpair;
+    DevBuf<PpPair> d_pair;
+    DevBuf<int> d_tsum, d_tpair, d_wsum, d_wpair;
+    i64 total = 0, out_words = 0;
+
+    // len[k] >= 1 words at the exclusive scan of len; the sum is below 2^31 (the callers have checked both)
+    void plan(const std::vector<int> &len)
+    {
+        std::vector<int> off(len.size()), cur(len);
+        for (size_t k = 0; k < len.size(); k++) { off[k] = (int)total; total += len[k]; }
+        out_words = total - (i64)len.size() + 1;
+        while (cur.size() > 1) {
+            Level L;
+            L.pair0 = pair.size();
+            L.t0 = tsum.size();
+            L.w0 = wsum.size();
+            L.tcnt = L.wcnt = 0;
+            const size_t c = cur.size(), np = (c + 1) / 2;
+            std::vector<int> noff(np), nlen(np);
+            i64 tw = 0, ww = 0;
+            std::vector<int> ts, tp, ws, wp;
+            for (size_t k = 0; k < np; k++) {
+                const int a = cur[2 * k], b = 2 * k + 1 < c ? cur[2 * k + 1] : 0;
+                const int outlen = b ? a + b - 1 : a;
+                pair.push_back(PpPair{off[2 * k], a, b ? off[2 * k + 1] : 0, b});
+                if (b && std::min(a, b) >= PP_WAVE) { ws.push_back((int)ww); wp.push_back((int)k); ww += outlen; }
+                else { ts.push_back((int)tw); tp.push_back((int)k); tw += outlen; }
+                noff[k] = off[2 * k];
+                nlen[k] = outlen;
+            }
+            ts.push_back((int)tw);
+            ws.push_back((int)ww);
+            L.tcnt = (int)tp.size();
+            L.wcnt = (int)wp.size();
+            L.tb = cdiv(tw, 256);
+            L.wb = cdiv(ww, 4 * PP_WPW);
+            tsum.insert(tsum.end(), ts.begin(), ts.end());
+            wsum.insert(wsum.end(), ws.begin(), ws.end());
+            // the pair lists are padded to the length of the sums, so that one base serves both arrays of a shape
+            tp.push_back(0);
+            wp.push_back(0);
+            tpair.insert(tpair.end(), tp.begin(), tp.end());
+            wpair.insert(wpair.end(), wp.begin(), wp.end());
+            level.push_back(L);
+            off.swap(noff);
+            cur.swap(nlen);
+        }
+    }
+
+    void upload(hipStream_t s)
+    {
+        if (level.empty()) return;
+        d_pair.alloc(pair.size());
+        d_tsum.alloc(tsum.size());
+        d_tpair.alloc(tpair.size());
+        d_wsum.alloc(wsum.size());
+        d_wpair.alloc(wpair.size());
+        HIPCHK(hipMemcpyAsync(d_pair.p, pair.data(), pair.size() * sizeof(PpPair), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_tsum.p, tsum.data(), tsum.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_tpair.p, tpair.data(), tpair.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_wsum.p, wsum.data(), wsum.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(d_wpair.p, wpair.data(), wpair.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+
+    // x0 holds the factors (balanced residues), x1 is the other buffer of `total` words; returns the one that holds the product
+    int *run(const ZpField &F, int *x0, int *x1, hipStream_t s)
+    {
+        int *src = x0, *dst = x1;
+        for (const Level &L : level) {
+            PpArgs g;
+            memset(&g, 0, sizeof g);
+            g.F = F;
+            g.pair = d_pair.p + L.pair0;
+            g.tsum = d_tsum.p + L.t0;
+            g.tpair = d_tpair.p + L.t0;
+            g.wsum = d_wsum.p + L.w0;
+            g.wpair = d_wpair.p + L.w0;
+            g.tcnt = L.tcnt;
+            g.wcnt = L.wcnt;
+            g.tb = L.tb;
+            g.src = src;
+            g.dst = dst;
+            hipLaunchKernelGGL(k_pp_level, dim3(L.tb + L.wb), dim3(256), 0, s, g);
+            HIPCHK(hipGetLastError());
+            std::swap(src, dst);
+        }
+        return src;
+    }
+};
+
+// out[0 .. sum(len) - count] = the product of the count polynomials f[k] (len[k] words, any int32).  Nothing is written before all
+// is done.
+void poly_product(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out)
+{
+    if (count < 0) throw EngineError("count < 0");
+    if (!out) throw EngineError("NULL array");
+    if (count > 0 && (!len || !f)) throw EngineError("NULL array");
+    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    i64 total = 0;
+    for (int k = 0; k < count; k++) {
+        char msg[96];
+        if (len[k] < 1) {
+            snprintf(msg, sizeof msg, "polynomial %d: a length below 1 (%d)", k, len[k]);
+            throw EngineError(msg);
+        }
+        if (!f[k]) {
+            snprintf(msg, sizeof msg, "polynomial %d: NULL array", k);
+            throw EngineError(msg);
+        }
+        total += len[k];
+        if (total >= ((i64)1 << 31)) {
+            snprintf(msg, sizeof msg, "polynomial %d: the total length must be below 2^31", k);
+            throw EngineError(msg);
+        }
+    }
+    if (count == 0) { out[0] = 1; return; }
+    require_device();
+    hipStream_t s = nullptr;
+    const ZpField F = zp_field_make(prime);
+    PolyProduct pp;
+    pp.plan(std::vector<int>(len, len + count));
+    std::vector<int> host((size_t)total);
+    {
+        size_t at = 0;
+        for (int k = 0; k < count; k++) { memcpy(host.data() + at, f[k], (size_t)len[k] * sizeof(int)); at += (size_t)len[k]; }
+    }
+    DevBuf<int> x0, x1;
+    x0.alloc((size_t)total);
+    if (count > 1) x1.alloc((size_t)total);
+    HIPCHK(hipMemcpyAsync(x0.p, host.data(), (size_t)total * sizeof(int), hipMemcpyHostToDevice, s));
+    pp.upload(s);
+    hipLaunchKernelGGL(k_pp_reduce, dim3(cdiv(total, 256)), dim3(256), 0, s, F, (int)total, x0.p);
+    HIPCHK(hipGetLastError());
+    const int *res = pp.run(F, x0.p, x1.p, s);
+    std::vector<int> got((size_t)pp.out_words);
+    HIPCHK(hipMemcpyAsync(got.data(), res, (size_t)pp.out_words * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(out, got.data(), (size_t)pp.out_words * sizeof(int));
+}
+
+// The characteristic polynomial of the matrix behind an index handle: coef[0 .. n] = the product of the blocks' polynomials, or
+// (factors) coef[row_start[b] + b ..] = the polynomial of block b.  Both refusals come from the handle's metadata.
+void blocks_charpoly(spasm_amd_blocks *B, spasm_ZZp *coef, bool factors)
+{
+    charpoly_split_stats_reset();
+    blocks_need(B);
+    if (!coef) throw EngineError("NULL array");
+    if (!B->index) throw EngineError("the handle is not an index split (spasm_amd_blocks_create_index)");
+    const int nb = B->nb;
+    for (int b = 0; b < nb; b++) {
+        const i64 rn = B->h_row_start[(size_t)b + 1] - B->h_row_start[(size_t)b];
+        if (rn > CHARPOLY_NMAX) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "block %d: characteristic polynomial limited to n <= %d (n = %lld)", b, CHARPOLY_NMAX, (long long)rn);
+            throw EngineError(msg);
+        }
+    }
+    i64 *st = g_charpoly_split_stats;
+    st[0] = nb;
+    if (B->n == 0) {
+        if (!factors) coef[0] = 1;
+        return;
+    }
+    hipStream_t s = nullptr;
+    const i64 total = (i64)B->n + nb;   // below 2^31: n + m is
+    std::vector<BatchItem> item((size_t)nb);
+    std::vector<i64> rec((size_t)nb);
+    std::vector<int> len((size_t)nb);
+    for (int b = 0; b < nb; b++) {
+        const i64 r0 = B->h_row_start[(size_t)b], rn = B->h_row_start[(size_t)b + 1] - r0;
+        item[(size_t)b] = BatchItem{(int)rn, (int)rn, r0 + b, B->prime};
+        rec[(size_t)b] = r0 + b;
+        len[(size_t)b] = (int)rn + 1;
+    }
+    PolyProduct pp;
+    DevBuf<int> x0, x1;
+    x0.alloc((size_t)total);
+    if (!factors) {
+        pp.plan(len);
+        if (nb > 1) x1.alloc((size_t)total);
+        pp.upload(s);
+    }
+    CharpolyJob job;
+    charpoly_launch(job, item, rec.data(), B->P.p, B->J.p, B->X.p, nullptr, x0.p, s);
+    SpgEvents ev;
+    const int *res = x0.p;
+    if (!factors) {
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        res = pp.run(zp_field_make(B->prime), x0.p, x1.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+    }
+    const size_t words = factors ? (size_t)total : (size_t)B->n + 1;
+    std::vector<int> got(words);
+    HIPCHK(hipMemcpyAsync(got.data(), res, words * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 cs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    job.stats(cs);
+    st[1] = cs[1];
+    st[2] = cs[2];
+    st[3] = cs[3];
+    st[4] = cs[4] + cs[5];
+    if (!factors) {
+        st[5] = (i64)pp.level.size();
+        st[6] = (i64)(ev.ms(0, 1) * 1000.0);
+    }
+    memcpy(coef, got.data(), words * sizeof(int));
+}
+
+// index split, then blocks_charpoly on a handle that lives for the call
+template <class Make> void charpoly_split(Make &&make, spasm_ZZp *coef)
+{
+    std::unique_ptr<spasm_amd_blocks> B(make());
+    blocks_charpoly(B.get(), coef, false);
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- product of polynomials mod p (polyprod.hpp) and characteristic polynomials by components (engine extension) ----
+SPASM_API int spasm_amd_poly_product(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out)
+{
+    return abi_call("spasm_amd_poly_product", -1, [&] { DeviceGuard g; poly_product(count, len, f, prime, out); return 0; });
+}
+
+SPASM_API int spasm_amd_blocks_charpoly(spasm_amd_blocks *B, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_blocks_charpoly", -1, [&] { DeviceGuard g(B); blocks_charpoly(B, coef, false); return 0; });
+}
+
+SPASM_API int spasm_amd_blocks_charpoly_factors(spasm_amd_blocks *B, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_blocks_charpoly_factors", -1, [&] { DeviceGuard g(B); blocks_charpoly(B, coef, true); return 0; });
+}
+
+SPASM_API int spasm_amd_charpoly_split(const struct spasm_csr *A, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_charpoly_split", -1, [&] {
+        DeviceGuard g;
+        charpoly_split_stats_reset();
+        blocks_check_host(A);
+        if (!coef) throw EngineError("NULL array");
+        blocks_check_square(A->n, A->m);
+        charpoly_split([&] { return blocks_create(A, true); }, coef);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_charpoly_split(const spasm_amd_dcsr *D, spasm_ZZp *coef)
+{
+    return abi_call("spasm_amd_dcsr_charpoly_split", -1, [&] {
+        DeviceGuard g(D);
+        charpoly_split_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        if (!coef) throw EngineError("NULL array");
+        blocks_check_square(D->n, D->m);
+        charpoly_split([&] { return blocks_create_dcsr(D, true); }, coef);
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_charpoly_split_stats(i64 *out)
+{
+    if (out) memcpy(out, g_charpoly_split_stats, sizeof g_charpoly_split_stats);
 }
 
 } // extern "C"
