@@ -883,6 +883,68 @@ int spasm_amd_charpoly_split(const struct spasm_csr *A, spasm_ZZp *coef);
 int spasm_amd_dcsr_charpoly_split(const spasm_amd_dcsr *D, spasm_ZZp *coef);
 void spasm_amd_charpoly_split_stats(i64 *out);   /* of the last split charpoly call of this thread */
 
+/* ---- Engine extension: minimal polynomials mod p of sparse matrices by Wiedemann's method (csrc/krylov.hpp) ----
+ * The black-box route: no elimination and no fill-in, memory O(nnz + n * K), no limit on n below 2^24.  The Krylov sequence
+ * s_i = u^T A^i v of the resident exact product is projected on the device, its shortest linear recurrence is found by
+ * Berlekamp-Massey on the device, and the lcm over K projections is taken on the host.
+ *   krylov_sequence  op is a resident operator of a SQUARE n x n matrix ("not square (3 x 2)" otherwise), 1 <= K <= 64, U and V are
+ *                 row-major n x K with leading dimensions ldu, ldv >= K (the layout of spasm_amd_spmv_apply; any int32 is reduced
+ *                 where it is read), S is len x K, packed:  S[i * K + c] = sum_r U[r, c] * (A^i V)[r, c]  for 0 <= i < len, as
+ *                 balanced residues; trans = 1 uses A^T.  V and U are not modified.  len == 0 succeeds and writes nothing.  Per
+ *                 step one launch per non-empty row class of the operator (plus the combine when there are long rows): the step
+ *                 writes A X into one of two buffers of the operator and folds the projection into the same launch as an exact
+ *                 64-bit integer sum (|sum| < 2^62), so the result does not depend on scheduling and two runs give the same bytes.
+ *   krylov_sequence_dev  the same on device arrays, enqueued on the hipStream_t stream without any host synchronization (NULL:
+ *                 returns when S is written).  One sequence at a time per operator.
+ *   berlekamp_massey  `count` sequences of `len` terms in one launch, one workgroup each: sequence c is S[c], S[lds + c], ..
+ *                 (column c of a row-major len x lds HOST array, lds >= count; any int32 is reduced on load).  coef is count x ldc
+ *                 with ldc >= len + 1: row c receives the monic f(x) = x^L * C(1 / x) of the shortest recurrence
+ *                 sum_j C[j] * s[i - j] = 0 (C[0] = 1, L <= len), low degree first, deg[c] + 1 words with deg[c] = L, and the rest
+ *                 of the row is zeroed.  The zero sequence gives {1}; 1, 0, 0, 0 gives x.  where = 0 chooses the class by size:
+ *                 the two polynomials live in LDS while 2 * (len + 1) words fit 158 KiB (len <= 20223), else in device memory
+ *                 (exact, not fast); 1 forces the LDS class ("the LDS class does not fit (len = .., at most 20223)" when it does
+ *                 not); 2 forces the device-memory class.  Both classes give the same bytes.  Field operations only: every prime
+ *                 2 < p <= 0xFFFFFFFB works.  count == 0 succeeds and needs no device.
+ *   poly_lcm      the monic lcm of `count` polynomials mod prime (polynomial k is len[k] >= 1 words f[k][..], any int32, a zero
+ *                 leading word allowed, not the zero polynomial) by Euclid on the host in exact arithmetic: *outlen words are written
+ *                 to out (balanced residues, low degree first, the last one 1), which must hold sum(len) - count + 1 words.
+ *                 count == 0 gives {1}.  Needs no device.
+ *   minpoly_vectors  the vectors minpoly uses when U == V == NULL, as n x K packed arrays (either may be NULL): word (t, r, c), t = 0
+ *                 for U and 1 for V, is w mod p as a balanced residue, w the splitmix64 output of the state
+ *                 seed + 0x9E3779B97F4A7C15 * (2 * (r * K + c) + t + 1)  (z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27;
+ *                 z *= 0x94D049BB133111EB; z ^= z >> 31; all mod 2^64).  The same seed gives the same bytes.  Needs no device.
+ *   minpoly, spmv_minpoly, dcsr_minpoly
+ *                 A host matrix, a resident operator, a resident matrix (on its device; no entry crosses the host).  K == 0 means
+ *                 8, maxdeg <= 0 (or > n) means n.  U and V are packed n x K host arrays or both NULL (minpoly_vectors(seed)).
+ *                 coef must hold maxdeg + 1 words; *deg + 1 of them are written.  The sequence has 2 * maxdeg terms when
+ *                 maxdeg = n, and 2 * maxdeg + 2 when maxdeg < n: 2 * maxdeg terms fix a recurrence of degree <= maxdeg but
+ *                 cannot show that the bound was too small (Berlekamp-Massey returns L = maxdeg on them whatever the true degree);
+ *                 with two more terms a larger degree shows as L > maxdeg and the call fails with "degree bound too small".
+ *                 n == 0 gives {1} and needs no device.
+ *   CONTRACT      the result is monic and ALWAYS divides the minimal polynomial of A; it equals it with a probability that grows
+ *                 with p and K (a projection misses a factor with probability about deg / p; small primes want a larger K and
+ *                 still may miss).  If x divides the result (coef[0] == 0), A is singular: that is certain.  If *deg == n, the
+ *                 result is the characteristic polynomial of A.  A result of lower degree says nothing certain about rank.
+ *   stats         of the last of these calls of this thread: out[8] = n, K, steps (products with A), launches, Berlekamp-Massey
+ *                 class (1 LDS, 2 device memory), degree of the result, device microseconds of the sequence and of
+ *                 Berlekamp-Massey (HIP events; 0 for krylov_sequence_dev).  Every call clears what it does not fill.
+ *   deterministic two runs give the same bytes
+ *   errors        a NULL operator / matrix / array, a matrix that is not square, K outside 1 .. 64 (0 .. 64 for minpoly:
+ *                 "K out of range"), ldu or ldv < K, lds < count, "ldc < len + 1", only one of U and V given, a prime outside
+ *                 3 .. 0xFFFFFFFB, n >= 2^24, no device ("no HIP device"), out of memory: -1, NO output word is written,
+ *                 spasm_amd_last_error() names the cause.  All but the last two are found before a device is looked for (for a
+ *                 host matrix and for berlekamp_massey; an operator or a resident matrix has one already). */
+int spasm_amd_krylov_sequence(spasm_amd_spmv *op, int trans, int K, int len, const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S);
+int spasm_amd_krylov_sequence_dev(spasm_amd_spmv *op, int trans, int K, int len, const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv,
+                                  spasm_ZZp *S, void *stream);
+int spasm_amd_berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime, int where, spasm_ZZp *coef, i64 ldc, int *deg);
+int spasm_amd_poly_lcm(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out, int *outlen);
+int spasm_amd_minpoly_vectors(int n, int K, uint64_t seed, i64 prime, spasm_ZZp *U, spasm_ZZp *V);
+int spasm_amd_minpoly(const struct spasm_csr *A, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg);
+int spasm_amd_spmv_minpoly(spasm_amd_spmv *op, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg);
+int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg);
+void spasm_amd_minpoly_stats(i64 *out);   /* of the last Krylov / Berlekamp-Massey / minpoly call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -320,6 +320,15 @@ SIGNATURES = {
     "spasm_amd_charpoly_split": (C.c_int32, [_P(CsrStruct), _P(C.c_int32)]),
     "spasm_amd_dcsr_charpoly_split": (C.c_int32, [C.c_void_p, _P(C.c_int32)]),
     "spasm_amd_charpoly_split_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_krylov_sequence": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_krylov_sequence_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spasm_amd_berlekamp_massey": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_poly_lcm": (C.c_int32, [C.c_int32, _P(C.c_int32), _P(_P(C.c_int32)), C.c_int64, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_minpoly_vectors": (C.c_int32, [C.c_int32, C.c_int32, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spasm_amd_minpoly": (C.c_int32, [_P(CsrStruct), C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_spmv_minpoly": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_dcsr_minpoly": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_minpoly_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

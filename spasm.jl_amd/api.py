@@ -2027,3 +2027,164 @@ def charpoly_split_stats():
     out = (C.c_int64 * 8)()
     _abi.lib().spasm_amd_charpoly_split_stats(out)
     return {k: int(v) for k, v in zip(CHARPOLY_SPLIT_STATS, out)}
+
+
+# ---------------------------------------------------------------------------------------------
+# Minimal polynomials by Wiedemann's method  (spasm_amd_krylov_sequence, _berlekamp_massey, _poly_lcm, _minpoly*; csrc/krylov.hpp)
+# ---------------------------------------------------------------------------------------------
+MINPOLY_STATS = ("n", "K", "steps", "launches", "bm_class", "degree", "sequence_device_us", "bm_device_us")
+
+
+def krylov_sequence(op, U, V, length, trans=False):
+    """krylov_sequence(op, U, V, length, trans=False) -> S of shape (length, K): S[i, c] = sum_r U[r, c] * (A^i V)[r, c] mod p as
+    balanced residues, A the square matrix of the SpMV operator op (A^T with trans=True).  U and V are n x K (or n entries: K = 1),
+    1 <= K <= 64, int32 numpy arrays (spasm_amd_krylov_sequence) or int32 torch tensors on the current device (enqueued on the
+    current stream without a host synchronization; S is a tensor: spasm_amd_krylov_sequence_dev).  U and V are not modified."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n = op.shape[0]
+    length = int(length)
+    if length < 0:
+        raise ValueError("length must not be negative")
+    lib = _abi.lib()
+    if type(U).__module__.startswith("torch") or type(V).__module__.startswith("torch"):
+        import torch
+
+        for t, name in ((U, "U"), (V, "V")):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device.type != "cuda" or t.device.index != torch.cuda.current_device():
+                raise TypeError(f"{name} must be an int32 tensor on the current device")
+            if t.dim() not in (1, 2) or t.shape[0] != n or tuple(t.shape) != tuple(U.shape):
+                raise ValueError(f"U and V must both have shape ({n},) or ({n}, K), not {tuple(t.shape)}")
+        k = 1 if U.dim() == 1 else int(U.shape[1])
+        for t, name in ((U, "U"), (V, "V")):
+            if t.stride(-1) != 1 or (t.dim() == 2 and t.shape[0] > 1 and t.stride(0) < k):
+                raise ValueError(f"{name} must have unit stride along its rows")
+        ldu = k if U.dim() == 1 else max(U.stride(0), k)
+        ldv = k if V.dim() == 1 else max(V.stride(0), k)
+        S = torch.empty((length, k), dtype=torch.int32, device=U.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.spasm_amd_krylov_sequence_dev(op._op, int(bool(trans)), k, length, C.c_void_p(U.data_ptr()), ldu, C.c_void_p(V.data_ptr()), ldv,
+                                               C.c_void_p(S.data_ptr()), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return S
+    for a, name in ((U, "U"), (V, "V")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+            raise TypeError(f"{name} must be an int32 numpy array or torch tensor")
+        if a.ndim not in (1, 2) or a.shape[0] != n or a.shape != U.shape:
+            raise ValueError(f"U and V must both have shape ({n},) or ({n}, K), not {a.shape}")
+    k = 1 if U.ndim == 1 else U.shape[1]
+    Uc, Vc = _rows_view(U, "U"), _rows_view(V, "V")
+    ldu = k if U.ndim == 1 else max(Uc.strides[0] // 4, k)
+    ldv = k if V.ndim == 1 else max(Vc.strides[0] // 4, k)
+    S = np.zeros((length, k), dtype=np.int32)
+    rc = lib.spasm_amd_krylov_sequence(op._op, int(bool(trans)), int(k), length, Uc.ctypes.data, ldu, Vc.ctypes.data, ldv, S.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error())
+    return S
+
+
+def berlekamp_massey(S, prime, where=0):
+    """berlekamp_massey(S, prime, where=0) -> list of numpy int32 arrays, one per column of S (len x count; a 1-d S is one
+    sequence): the monic polynomial of the shortest linear recurrence of the column, low degree first, as balanced residues
+    (spasm_amd_berlekamp_massey: one workgroup per sequence; where = 1 forces the LDS class, 2 the device-memory class).  The
+    zero sequence gives [1]; 1, 0, 0, 0 gives x."""
+    S = np.asarray(S)
+    if S.dtype.kind not in "iu":
+        raise TypeError("integer entries expected")
+    one = S.ndim == 1
+    if one:
+        S = S[:, None]
+    if S.ndim != 2:
+        raise ValueError("a sequence or a len x count array expected")
+    S = np.ascontiguousarray(balanced(S, int(prime)))
+    length, count = S.shape
+    ldc = length + 1
+    coef = np.zeros((max(count, 1), ldc), dtype=np.int32)
+    deg = np.zeros(max(count, 1), dtype=np.int32)
+    rc = _abi.lib().spasm_amd_berlekamp_massey(count, length, S.ctypes.data, count, int(prime), int(where),
+                                               coef.ctypes.data, ldc, deg.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_berlekamp_massey failed")
+    out = [coef[c, : deg[c] + 1].copy() for c in range(count)]
+    return out[0] if one else out
+
+
+def poly_lcm(polys, prime):
+    """poly_lcm([f, ...], prime) -> numpy int32 array: the monic lcm of the polynomials mod prime as balanced residues, low degree
+    first (spasm_amd_poly_lcm: Euclid on the host, exact, no device).  Every f is a non-empty sequence of integers that fit int32
+    and is not the zero polynomial; [] gives [1]."""
+    polys = [np.ascontiguousarray(f, dtype=np.int32).reshape(-1) for f in polys]
+    count = len(polys)
+    lens = (C.c_int32 * max(count, 1))(*[len(f) for f in polys])
+    ptrs = (C.POINTER(C.c_int32) * max(count, 1))(*[f.ctypes.data_as(C.POINTER(C.c_int32)) for f in polys])
+    out = np.zeros(max(sum(len(f) for f in polys) - count + 1, 1), dtype=np.int32)
+    outlen = C.c_int32(0)
+    rc = _abi.lib().spasm_amd_poly_lcm(count, lens, ptrs, int(prime), out.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(outlen))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_poly_lcm failed")
+    return out[: outlen.value].copy()
+
+
+def minpoly_vectors(n, K, seed, prime):
+    """(U, V): the n x K int32 arrays minpoly uses for this seed when none are given (spasm_amd_minpoly_vectors)."""
+    U = np.zeros((n, K), dtype=np.int32)
+    V = np.zeros((n, K), dtype=np.int32)
+    rc = _abi.lib().spasm_amd_minpoly_vectors(int(n), int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(prime), U.ctypes.data, V.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_minpoly_vectors failed")
+    return U, V
+
+
+def minpoly(A, K=8, seed=0, maxdeg=None, U=None, V=None):
+    """minpoly(A, K=8, seed=0, maxdeg=None, U=None, V=None) -> numpy int32 array: the lcm of the minimal polynomials of K
+    projections u^T A^i v of the Krylov sequence of the square matrix A, monic, low degree first, balanced residues.  A is a CSR
+    (spasm_amd_minpoly), an SpMV operator (spasm_amd_spmv_minpoly) or a DeviceCSR (spasm_amd_dcsr_minpoly: on its device).  U and V
+    are n x K int32 arrays, or both None: minpoly_vectors(n, K, seed, prime).  maxdeg bounds the degree (None: n); a matrix whose
+    polynomial has a larger degree is refused ("degree bound too small").
+    The result always divides the minimal polynomial of A and equals it with a probability that grows with p and K.  If its
+    constant term is 0, A is singular (certain).  If its degree is n, it is the characteristic polynomial."""
+    lib = _abi.lib()
+    if isinstance(A, CSR):
+        who, fn, arg, n = "spasm_amd_minpoly", lib.spasm_amd_minpoly, A.data, A.n
+    elif isinstance(A, SpMV):
+        if not A._op:
+            raise SpasmError("the operator is closed")
+        who, fn, arg, n = "spasm_amd_spmv_minpoly", lib.spasm_amd_spmv_minpoly, A._op, A.shape[0]
+    elif isinstance(A, DeviceCSR):
+        who, fn, arg, n = "spasm_amd_dcsr_minpoly", lib.spasm_amd_dcsr_minpoly, A._need(), A.shape[0]
+    else:
+        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    K = int(K)
+    kk = 8 if K == 0 else K
+    ptrs = []
+    for a, name in ((U, "U"), (V, "V")):
+        if a is None:
+            ptrs.append(None)
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != (n, kk) or not a.flags["C_CONTIGUOUS"]:
+            raise TypeError(f"{name} must be a contiguous int32 numpy array of shape ({n}, {kk})")
+        ptrs.append(a.ctypes.data)
+    md = 0 if maxdeg is None else int(maxdeg)
+    out = np.zeros((md if 0 < md <= n else max(n, 0)) + 1, dtype=np.int32)
+    deg = C.c_int32(0)
+    with _quiet(True):
+        rc = fn(arg, K, int(seed) & 0xFFFFFFFFFFFFFFFF, md, ptrs[0], ptrs[1], out.ctypes.data, C.byref(deg))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return out[: deg.value + 1].copy()
+
+
+def minpoly_stats():
+    """Counters of the last Krylov / Berlekamp-Massey / minpoly call of this thread (spasm_amd_minpoly_stats), keyed by
+    MINPOLY_STATS."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_minpoly_stats(out)
+    return {k: int(v) for k, v in zip(MINPOLY_STATS, out)}
+
+
+SpMV.krylov_sequence = krylov_sequence
+SpMV.minpoly = minpoly
+DeviceCSR.minpoly = minpoly

@@ -5525,6 +5525,12 @@ void spmv_chunk(const SpmvView &V, const ZpField &F, int kw, int kc, const int *
     }
 }
 
+// the ping-pong buffers and the projection sums of one Krylov sequence (krylov.hpp; the section at the end of this file)
+struct KrylovWork {
+    DevBuf<int> w0, w1;
+    DevBuf<long long> acc;
+};
+
 } // namespace
 
 struct spasm_amd_spmv {
@@ -5535,6 +5541,7 @@ struct spasm_amd_spmv {
     bool have_t = false;
     SpmvView fwd, tr;
     DevBuf<int> hx, hy;   // staging of the host-array applies
+    KrylovWork kry;       // buffers of spasm_amd_krylov_sequence_dev (krylov.hpp)
 
     // the transposed view, built on the first x A: the device counting sort of the engine, then its rows binned
     void build_transpose()
@@ -10607,6 +10614,576 @@ SPASM_API int spasm_amd_dcsr_charpoly_split(const spasm_amd_dcsr *D, spasm_ZZp *
 SPASM_API void spasm_amd_charpoly_split_stats(i64 *out)
 {
     if (out) memcpy(out, g_charpoly_split_stats, sizeof g_charpoly_split_stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Minimal polynomials of sparse matrices by Wiedemann's method (krylov.hpp): the projected Krylov sequence of the resident exact
+// product, Berlekamp-Massey on the device, and the lcm over the K projections on the host.
+// ------------------------------------------------------------------------------------------------
+#include "krylov.hpp"
+
+namespace {
+
+// n, K, steps, launches, BM class (1 LDS, 2 device memory), degree, sequence device us, BM device us
+thread_local i64 g_minpoly_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+
+void minpoly_stats_reset() { memset(g_minpoly_stats, 0, sizeof g_minpoly_stats); }
+
+template <bool SMALL, int KW>
+int krylov_launch(const SpmvView &V, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
+                  hipStream_t s)
+{
+    constexpr int TS = spmv_short_team(KW);
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
+    auto grid = [&](i64 lanes) { return dim3((unsigned)std::max(1, std::min(cdiv(lanes, KRY_BS), cap))); };
+    int launches = 0;
+    HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
+    if (n > 0) {
+        hipLaunchKernelGGL((k_krylov_dot<KW>), grid((i64)n * KW), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+        launches++;
+    }
+    const int *X = X0;
+    i64d ldx = (i64d)ldx0;
+    int *Y = W.w0.p;
+    for (i64 i = 1; i < len && n > 0; i++) {
+        long long *ap = W.acc.p + i * KW;
+        if (V.nshort > 0) {
+            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, TS, false>), grid((i64)V.nshort * TS), dim3(KRY_BS), 0, s, V.nshort,
+                               V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, nullptr, U,
+                               (i64d)ldu, ap);
+            launches++;
+        }
+        if (V.nmid > 0) {
+            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, 64, false>), grid((i64)V.nmid * 64), dim3(KRY_BS), 0, s, V.nmid, V.mid_rows.p, nullptr, V.start,
+                               V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, nullptr, U, (i64d)ldu, ap);
+            launches++;
+        }
+        if (V.nlong > 0) {
+            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, 64, true>), grid((i64)V.nseg * 64), dim3(KRY_BS), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p, V.start,
+                               V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, V.part.p, U, (i64d)ldu, ap);
+            hipLaunchKernelGGL((k_krylov_combine<KW>), grid((i64)V.nlong * KW), dim3(KRY_BS), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p, kc, F,
+                               hp, mhp, Y, (i64d)KW, U, (i64d)ldu, ap);
+            launches += 2;
+        }
+        HIPCHK(hipGetLastError());
+        X = Y;
+        ldx = KW;
+        Y = Y == W.w0.p ? W.w1.p : W.w0.p;
+    }
+    const i64 total = len * kc;
+    hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, kc, KW, F, W.acc.p, S);
+    HIPCHK(hipGetLastError());
+    return launches + 1;
+}
+
+template <bool SMALL>
+int krylov_chunk(int kw, const SpmvView &V, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
+                 hipStream_t s)
+{
+    switch (kw) {
+    case 1: return krylov_launch<SMALL, 1>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    case 2: return krylov_launch<SMALL, 2>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    case 4: return krylov_launch<SMALL, 4>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    case 8: return krylov_launch<SMALL, 8>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    case 16: return krylov_launch<SMALL, 16>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    case 32: return krylov_launch<SMALL, 32>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    default: return krylov_launch<SMALL, 64>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
+    }
+}
+
+// S[i * K + c] = sum_r U[r, c] * (A^i V)[r, c], 0 <= i < len, on device arrays, enqueued on s; no host synchronization.  V is the
+// view of a square matrix; 1 <= K <= 64, len >= 1.  Returns the launches.
+int krylov_run(const SpmvView &V, const ZpField &F, int K, i64 len, const int *U, i64 ldu, const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
+{
+    int kw = 1;
+    while (kw < K) kw <<= 1;
+    int dev = 0, cu = 256;
+    HIPCHK(hipGetDevice(&dev));
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    const size_t words = (size_t)V.rows * kw;
+    if (len > 1) {
+        W.w0.ensure(words);
+        if (len > 2) W.w1.ensure(words);
+    }
+    W.acc.ensure((size_t)len * kw);
+    const int cap = cu * KRY_WG_PER_CU;
+    return F.small ? krylov_chunk<true>(kw, V, F, K, len, U, ldu, X, ldx, W, S, cap, s) : krylov_chunk<false>(kw, V, F, K, len, U, ldu, X, ldx, W, S, cap, s);
+}
+
+void krylov_check(const spasm_amd_spmv *op, int trans, int K, i64 len, const void *U, i64 ldu, const void *V, i64 ldv, const void *S)
+{
+    if (!op) throw EngineError("NULL operator");
+    if (op->A.n != op->A.m) {
+        char msg[96];
+        snprintf(msg, sizeof msg, "not square (%d x %d)", op->A.n, op->A.m);
+        throw EngineError(msg);
+    }
+    if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
+    if (len < 0 || len * 64 >= ((i64)1 << 31) || ldu < K || ldv < K || (trans != 0 && trans != 1))
+        throw EngineError("bad arguments (trans 0/1, 0 <= len < 2^25, ldu >= K, ldv >= K)");
+    if (len > 0 && (!S || (op->A.n > 0 && (!U || !V)))) throw EngineError("NULL array");
+}
+
+// the class of a Berlekamp-Massey launch: 1 LDS, 2 device memory
+int bm_class(int len, int where)
+{
+    if (where < 0 || where > 2) throw EngineError("where must be 0 (by size), 1 (LDS) or 2 (device memory)");
+    const bool fits = 2 * ((i64)len + 1) <= BM_LDS_WORDS;
+    if (where == 1 && !fits) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "the LDS class does not fit (len = %d, at most %d)", len, BM_LDS_WORDS / 2 - 1);
+        throw EngineError(msg);
+    }
+    return where == 2 || !fits ? 2 : 1;
+}
+
+void bm_check_len(const ZpField &F, i64 len)
+{
+    if (len < 0 || len >= ((i64)1 << 30)) throw EngineError("len out of range (0 <= len < 2^30)");
+    if (len > (i64)zp_lazy_terms(F) * BM_BS) throw EngineError("len beyond the lazy accumulator of the discrepancy for this prime");
+}
+
+// count sequences on the device (sequence c is column c of S, leading dimension lds) -> d_coef (count x ldc), d_deg; enqueued on s
+void bm_device(const ZpField &F, int count, int len, const int *dS, i64 lds, int cls, int *d_coef, i64 ldc, int *d_deg, DevBuf<int> &gwork, hipStream_t s)
+{
+    BmArgs a;
+    a.F = F;
+    a.len = len;
+    a.S = dS;
+    a.lds = (i64d)lds;
+    a.coef = d_coef;
+    a.ldc = (i64d)ldc;
+    a.deg = d_deg;
+    a.gwork = nullptr;
+    if (cls == 1) {
+        static bool attr_done[kMaxDev] = {false};
+        bool &done = attr_done[current_device()];
+        if (!done) {
+            HIPCHK(hipFuncSetAttribute((const void *)k_berlekamp_massey<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BM_LDS_WORDS * 4));
+            HIPCHK(hipFuncSetAttribute((const void *)k_berlekamp_massey<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, BM_LDS_WORDS * 4));
+            done = true;
+        }
+        const size_t lds_bytes = 2 * ((size_t)len + 1) * sizeof(int);
+        if (F.small) hipLaunchKernelGGL((k_berlekamp_massey<true, true>), dim3(count), dim3(BM_BS), lds_bytes, s, a);
+        else hipLaunchKernelGGL((k_berlekamp_massey<false, true>), dim3(count), dim3(BM_BS), lds_bytes, s, a);
+    } else {
+        gwork.ensure((size_t)count * 2 * ((size_t)len + 1));
+        a.gwork = gwork.p;
+        if (F.small) hipLaunchKernelGGL((k_berlekamp_massey<true, false>), dim3(count), dim3(BM_BS), 0, s, a);
+        else hipLaunchKernelGGL((k_berlekamp_massey<false, false>), dim3(count), dim3(BM_BS), 0, s, a);
+    }
+    HIPCHK(hipGetLastError());
+}
+
+void berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime, int where, spasm_ZZp *coef, i64 ldc, int *deg)
+{
+    minpoly_stats_reset();
+    if (count < 0) throw EngineError("count < 0");
+    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    const ZpField F = zp_field_make(prime);
+    bm_check_len(F, len);
+    if (lds < count) throw EngineError("lds < count");
+    if (ldc < (i64)len + 1) throw EngineError("ldc < len + 1");
+    if ((i64)count * ldc >= ((i64)1 << 40)) throw EngineError("count * ldc too large");
+    const int cls = bm_class(len, where);
+    if (count == 0) return;
+    if (!coef || !deg || (len > 0 && !S)) throw EngineError("NULL array");
+    require_device();
+    hipStream_t s = nullptr;
+    DevBuf<int> dS, d_coef, d_deg, gwork;
+    dS.alloc((size_t)len * (size_t)count);
+    d_coef.alloc((size_t)count * (size_t)ldc);
+    d_deg.alloc((size_t)count);
+    if (len > 0)
+        HIPCHK(hipMemcpy2DAsync(dS.p, (size_t)count * sizeof(int), S, (size_t)lds * sizeof(int), (size_t)count * sizeof(int), (size_t)len, hipMemcpyHostToDevice, s));
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    bm_device(F, count, len, dS.p, count, cls, d_coef.p, ldc, d_deg.p, gwork, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> hc((size_t)count * (size_t)ldc), hd((size_t)count);
+    HIPCHK(hipMemcpyAsync(hc.data(), d_coef.p, hc.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hd.data(), d_deg.p, hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = g_minpoly_stats;
+    st[1] = count;
+    st[3] = 1;
+    st[4] = cls;
+    st[7] = (i64)(ev.ms(0, 1) * 1000.0);
+    memcpy(coef, hc.data(), hc.size() * sizeof(int));
+    memcpy(deg, hd.data(), hd.size() * sizeof(int));
+}
+
+// ---- polynomials over GF(p) on the host, as residues in [0, p), low degree first, no zero leading word (the zero polynomial is empty)
+typedef std::vector<uint64_t> HPoly;
+
+HPoly hpoly_load(const int *f, int len, uint64_t p)
+{
+    HPoly a((size_t)len);
+    for (int k = 0; k < len; k++) {
+        int64_t r = (int64_t)f[k] % (int64_t)p;
+        a[(size_t)k] = (uint64_t)(r < 0 ? r + (int64_t)p : r);
+    }
+    while (!a.empty() && a.back() == 0) a.pop_back();
+    return a;
+}
+
+uint64_t hinv(uint64_t a, uint64_t p)
+{
+    int64_t r0 = (int64_t)a, r1 = (int64_t)p, s0 = 1, s1 = 0;
+    while (r1 != 0) {
+        const int64_t q = r0 / r1;
+        int64_t t = r0 - q * r1; r0 = r1; r1 = t;
+        t = s0 - q * s1; s0 = s1; s1 = t;
+    }
+    int64_t r = s0 % (int64_t)p;
+    return (uint64_t)(r < 0 ? r + (int64_t)p : r);
+}
+
+// a <- a mod b (b not zero); quo (may be NULL) <- the quotient.  Products of two residues fit a u64 (p < 2^32).
+void hpoly_divrem(HPoly &a, const HPoly &b, uint64_t p, HPoly *quo)
+{
+    const size_t db = b.size() - 1;
+    if (quo) quo->assign(a.size() > db ? a.size() - db : 0, 0);
+    const uint64_t ib = hinv(b.back(), p);
+    while (a.size() > db) {
+        const size_t sh = a.size() - 1 - db;
+        const uint64_t q = a.back() * ib % p;
+        if (quo) (*quo)[sh] = q;
+        const uint64_t nq = p - q; // q != 0: a has no zero leading word
+        for (size_t k = 0; k <= db; k++) a[sh + k] = (a[sh + k] + nq * b[k]) % p;
+        while (!a.empty() && a.back() == 0) a.pop_back();
+    }
+}
+
+void hpoly_monic(HPoly &a, uint64_t p)
+{
+    if (a.empty() || a.back() == 1) return;
+    const uint64_t i = hinv(a.back(), p);
+    for (uint64_t &w : a) w = w * i % p;
+}
+
+// the monic lcm of two non-zero polynomials: a * (b / gcd(a, b))
+HPoly hpoly_lcm(HPoly a, HPoly b, uint64_t p)
+{
+    hpoly_monic(a, p);
+    hpoly_monic(b, p);
+    if (a == b) return a;
+    HPoly g = a, h = b;
+    while (!h.empty()) {
+        hpoly_divrem(g, h, p, nullptr);
+        g.swap(h);
+    }
+    HPoly q, r = b;
+    hpoly_divrem(r, g, p, &q);
+    HPoly out(a.size() + q.size() - 1, 0);
+    for (size_t i = 0; i < a.size(); i++) {
+        if (a[i] == 0) continue;
+        for (size_t j = 0; j < q.size(); j++) out[i + j] = (out[i + j] + a[i] * q[j]) % p;
+    }
+    hpoly_monic(out, p);
+    return out;
+}
+
+void hpoly_store(const HPoly &a, uint64_t p, int *out)
+{
+    for (size_t k = 0; k < a.size(); k++) out[k] = (int)(a[k] > p / 2 ? (int64_t)a[k] - (int64_t)p : (int64_t)a[k]);
+}
+
+void poly_lcm(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out, int *outlen)
+{
+    if (count < 0) throw EngineError("count < 0");
+    if (!out || !outlen) throw EngineError("NULL array");
+    if (count > 0 && (!len || !f)) throw EngineError("NULL array");
+    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    const uint64_t p = (uint64_t)prime;
+    std::vector<HPoly> poly;
+    i64 total = 0;
+    for (int k = 0; k < count; k++) {
+        char msg[96];
+        if (len[k] < 1) {
+            snprintf(msg, sizeof msg, "polynomial %d: a length below 1 (%d)", k, len[k]);
+            throw EngineError(msg);
+        }
+        if (!f[k]) {
+            snprintf(msg, sizeof msg, "polynomial %d: NULL array", k);
+            throw EngineError(msg);
+        }
+        total += len[k];
+        if (total >= ((i64)1 << 31)) {
+            snprintf(msg, sizeof msg, "polynomial %d: the total length must be below 2^31", k);
+            throw EngineError(msg);
+        }
+        poly.push_back(hpoly_load(f[k], len[k], p));
+        if (poly.back().empty()) {
+            snprintf(msg, sizeof msg, "polynomial %d: the zero polynomial has no lcm", k);
+            throw EngineError(msg);
+        }
+    }
+    HPoly r(1, 1);
+    for (const HPoly &g : poly) r = hpoly_lcm(r, g, p);
+    hpoly_store(r, p, out);
+    *outlen = (int)r.size();
+}
+
+// The vectors of spasm_amd_minpoly when the caller gives none: word (t, r, c) -- t = 0 for U, 1 for V -- is the splitmix64 output
+// of the state seed + 0x9E3779B97F4A7C15 * (2 * (r * K + c) + t + 1), reduced mod p to the balanced residue.
+uint64_t minpoly_mix(uint64_t z)
+{
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    return z ^ (z >> 31);
+}
+
+void minpoly_vectors(int n, int K, uint64_t seed, i64 prime, int *U, int *V)
+{
+    const uint64_t p = (uint64_t)prime;
+    for (int t = 0; t < 2; t++) {
+        int *dst = t ? V : U;
+        if (!dst) continue;
+        for (i64 e = 0; e < (i64)n * K; e++) {
+            const uint64_t w = minpoly_mix(seed + 0x9E3779B97F4A7C15ULL * (2 * (uint64_t)e + (uint64_t)t + 1)) % p;
+            dst[e] = (int)(w > p / 2 ? (int64_t)w - (int64_t)p : (int64_t)w);
+        }
+    }
+}
+
+int minpoly_K(int K)
+{
+    if (K < 0 || K > 64) throw EngineError("K out of range (0 <= K <= 64, 0 means 8)");
+    return K == 0 ? 8 : K;
+}
+
+// The lcm of the minimal polynomials of the K projected sequences of the square matrix behind view V.
+void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *X, spasm_ZZp *coef, int *deg)
+{
+    const int n = V.rows;
+    const int md = (maxdeg <= 0 || maxdeg > n) ? n : maxdeg;
+    if (n >= (1 << 24)) throw EngineError("minimal polynomial limited to n < 2^24");
+    // 2 * md terms determine a recurrence of degree <= md; two more terms show a degree above md as L > md (see the header)
+    const int len = md < n ? 2 * md + 2 : 2 * n;
+    bm_check_len(F, len);
+    hipStream_t s = nullptr;
+    std::vector<int> hu, hv;
+    if (!U) {
+        hu.resize((size_t)n * K);
+        hv.resize((size_t)n * K);
+        minpoly_vectors(n, K, seed, F.p, hu.data(), hv.data());
+        U = hu.data();
+        X = hv.data();
+    }
+    DevBuf<int> dU, dV, dS, d_coef, d_deg, gwork;
+    KrylovWork W;
+    const size_t nk = (size_t)n * K;
+    dU.alloc(nk);
+    dV.alloc(nk);
+    dS.alloc((size_t)len * K);
+    const i64 ldc = (i64)len + 1;
+    d_coef.alloc((size_t)K * (size_t)ldc);
+    d_deg.alloc((size_t)K);
+    HIPCHK(hipMemcpyAsync(dU.p, U, nk * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(dV.p, X, nk * sizeof(int), hipMemcpyHostToDevice, s));
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    const int launches = krylov_run(V, F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    const int cls = bm_class(len, 0);
+    bm_device(F, K, len, dS.p, K, cls, d_coef.p, ldc, d_deg.p, gwork, s);
+    HIPCHK(hipEventRecord(ev.e[2], s));
+    std::vector<int> hd((size_t)K);
+    HIPCHK(hipMemcpyAsync(hd.data(), d_deg.p, hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = g_minpoly_stats;
+    st[0] = n;
+    st[1] = K;
+    st[2] = len - 1;
+    st[3] = launches + 1;
+    st[4] = cls;
+    st[6] = (i64)(ev.ms(0, 1) * 1000.0);
+    st[7] = (i64)(ev.ms(1, 2) * 1000.0);
+    for (int c = 0; c < K; c++)
+        if (hd[(size_t)c] > md) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d, maxdeg %d)", c, hd[(size_t)c], md);
+            throw EngineError(msg);
+        }
+    HPoly r(1, 1);
+    std::vector<int> hc((size_t)md + 1);
+    for (int c = 0; c < K; c++) {
+        const int d = hd[(size_t)c];
+        HIPCHK(hipMemcpy(hc.data(), d_coef.p + (size_t)c * (size_t)ldc, ((size_t)d + 1) * sizeof(int), hipMemcpyDeviceToHost));
+        r = hpoly_lcm(r, hpoly_load(hc.data(), d + 1, (uint64_t)F.p), (uint64_t)F.p);
+        if ((i64)r.size() - 1 > md) throw EngineError("degree bound too small (the lcm of the projections exceeds maxdeg)");
+    }
+    st[5] = (i64)r.size() - 1;
+    hpoly_store(r, (uint64_t)F.p, coef);
+    *deg = (int)r.size() - 1;
+}
+
+void minpoly_check_out(const spasm_ZZp *U, const spasm_ZZp *X, const spasm_ZZp *coef, const int *deg)
+{
+    if (!coef || !deg) throw EngineError("NULL array");
+    if ((U == nullptr) != (X == nullptr)) throw EngineError("U and V must both be given or both be NULL");
+}
+
+void minpoly_square(int n, int m)
+{
+    if (n == m) return;
+    char msg[96];
+    snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
+    throw EngineError(msg);
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- Krylov sequences, Berlekamp-Massey and minimal polynomials (krylov.hpp; engine extension) ----
+SPASM_API int spasm_amd_krylov_sequence(spasm_amd_spmv *op, int trans, int K, int len, const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    return abi_call("spasm_amd_krylov_sequence", -1, [&] {
+        minpoly_stats_reset();
+        krylov_check(op, trans, K, len, U, ldu, V, ldv, S);
+        if (len == 0) return 0;
+        DeviceGuard g(op);
+        if (trans) op->build_transpose();
+        const SpmvView &view = trans ? op->tr : op->fwd;
+        const size_t n = (size_t)op->A.n, kk = (size_t)K;
+        hipStream_t s = nullptr;
+        DevBuf<int> dU, dV, dS;
+        KrylovWork W;
+        dU.alloc(n * kk);
+        dV.alloc(n * kk);
+        dS.alloc((size_t)len * kk);
+        if (n > 0) {
+            HIPCHK(hipMemcpy2DAsync(dU.p, kk * sizeof(int), U, (size_t)ldu * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpy2DAsync(dV.p, kk * sizeof(int), V, (size_t)ldv * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+        }
+        SpgEvents ev;
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        const int launches = krylov_run(view, op->F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        std::vector<int> out((size_t)len * kk);
+        HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        i64 *st = g_minpoly_stats;
+        st[0] = (i64)n;
+        st[1] = K;
+        st[2] = len - 1;
+        st[3] = launches;
+        st[6] = (i64)(ev.ms(0, 1) * 1000.0);
+        memcpy(S, out.data(), out.size() * sizeof(int));
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_krylov_sequence_dev(spasm_amd_spmv *op, int trans, int K, int len, const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv,
+                                            spasm_ZZp *S, void *stream)
+{
+    return abi_call("spasm_amd_krylov_sequence_dev", -1, [&] {
+        minpoly_stats_reset();
+        krylov_check(op, trans, K, len, U, ldu, V, ldv, S);
+        if (len == 0) return 0;
+        DeviceGuard g(op);
+        if (trans) op->build_transpose();
+        hipStream_t s = (hipStream_t)stream;
+        const int launches = krylov_run(trans ? op->tr : op->fwd, op->F, K, len, U, ldu, V, ldv, op->kry, S, s);
+        if (!stream) HIPCHK(hipStreamSynchronize(s));
+        i64 *st = g_minpoly_stats;
+        st[0] = op->A.n;
+        st[1] = K;
+        st[2] = len - 1;
+        st[3] = launches;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime, int where, spasm_ZZp *coef, i64 ldc, int *deg)
+{
+    return abi_call("spasm_amd_berlekamp_massey", -1, [&] { DeviceGuard g; berlekamp_massey(count, len, S, lds, prime, where, coef, ldc, deg); return 0; });
+}
+
+SPASM_API int spasm_amd_poly_lcm(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out, int *outlen)
+{
+    return abi_call("spasm_amd_poly_lcm", -1, [&] { poly_lcm(count, len, f, prime, out, outlen); return 0; });
+}
+
+SPASM_API int spasm_amd_minpoly_vectors(int n, int K, uint64_t seed, i64 prime, spasm_ZZp *U, spasm_ZZp *V)
+{
+    return abi_call("spasm_amd_minpoly_vectors", -1, [&] {
+        if (n < 0 || K < 1 || K > 64) throw EngineError("bad arguments (n >= 0, 1 <= K <= 64)");
+        if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+        minpoly_vectors(n, K, seed, prime, U, V);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_minpoly(const struct spasm_csr *A, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
+{
+    return abi_call("spasm_amd_minpoly", -1, [&] {
+        DeviceGuard g;
+        minpoly_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        minpoly_square(A->n, A->m);
+        K = minpoly_K(K);
+        minpoly_check_out(U, V, coef, deg);
+        if (A->n == 0) { coef[0] = 1; *deg = 0; return 0; }
+        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_minpoly"));
+        minpoly_run(op->fwd, op->F, K, seed, maxdeg, U, V, coef, deg);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_spmv_minpoly(spasm_amd_spmv *op, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
+{
+    return abi_call("spasm_amd_spmv_minpoly", -1, [&] {
+        minpoly_stats_reset();
+        if (!op) throw EngineError("NULL operator");
+        DeviceGuard g(op);
+        minpoly_square(op->A.n, op->A.m);
+        K = minpoly_K(K);
+        minpoly_check_out(U, V, coef, deg);
+        if (op->A.n == 0) { coef[0] = 1; *deg = 0; return 0; }
+        minpoly_run(op->fwd, op->F, K, seed, maxdeg, U, V, coef, deg);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
+{
+    return abi_call("spasm_amd_dcsr_minpoly", -1, [&] {
+        minpoly_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        DeviceGuard g(D);
+        minpoly_square(D->n, D->m);
+        K = minpoly_K(K);
+        minpoly_check_out(U, V, coef, deg);
+        if (D->n == 0) { coef[0] = 1; *deg = 0; return 0; }
+        // a view of the resident entries: the row pointers serve as starts, the lengths are their differences
+        hipStream_t s = nullptr;
+        SpmvView view;
+        view.rows = view.cols = D->n;
+        view.start = D->p.p;
+        view.ent = D->ent.p;
+        view.tlen.alloc((size_t)D->n + 1);
+        hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(D->n, 256)), dim3(256), 0, s, D->n, D->p.p, view.tlen.p);
+        HIPCHK(hipGetLastError());
+        view.len = view.tlen.p;
+        std::vector<i64d> hp((size_t)D->n + 1);
+        HIPCHK(hipMemcpyAsync(hp.data(), D->p.p, hp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        std::vector<i64> hl((size_t)D->n);
+        for (int i = 0; i < D->n; i++) hl[(size_t)i] = hp[(size_t)i + 1] - hp[(size_t)i];
+        view.bin(hl, s);
+        minpoly_run(view, D->F, K, seed, maxdeg, U, V, coef, deg);
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_minpoly_stats(i64 *out)
+{
+    if (out) memcpy(out, g_minpoly_stats, sizeof g_minpoly_stats);
 }
 
 } // extern "C"
