@@ -771,6 +771,27 @@ int spasm_amd_zp_probe(i64 prime, int n, const int *a, const int *b, const int *
  * ("no HIP device") or with bad arguments 1, and out is not written. */
 int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *b, const int *count, int *out);
 
+/* The primitives of csrc/zp.hpp one at a time, on chosen arguments (tests/test_gpu_zp.py, tests/test_zp_host.py).  All return 0 on
+ * success and 1 on an error; the entries that run on the device fail without one ("no HIP device") and write nothing then.
+ *   zp_reduce_probe        out[i] = zp_reduce(x[i]), the balanced residue of an i64 with |x| <= min(3 * 2^51 * p, 2^62) (the domain the
+ *                          header of zp.hpp derives).  where = 0: the host compilation of the function in a plain loop, no device
+ *                          needed; where = 1: one lane per value on the device.
+ *   zp_field_probe_host    the first six results of spasm_amd_zp_probe (a*b, a*b+c, a+b, a-b, -a, a^-1 with 0 for a = 0), 6 ints per
+ *                          vector, from the host compilation: no device needed; the device's six must be the same bits.
+ *   zp_lazy_probe          out[i] = the raw, unreduced lazy product of a[i] and b[i] as the accumulators take it (i32 for p < 2^16,
+ *                          widened; i64 above): congruent to a*b, |out| <= p/2 + 256 for p < 2^16 and <= 0.51 p above.
+ *   zp_small_lazy_probe    p < 2^16 only: out[i] = the raw one-step reduction zp_small_lazy(x[i]) of an i32 with |x| <= 2^30 and
+ *                          |x / p| < 2^22, which the lazy product applies to x = a * b.
+ *   zp_small_lazy_scan     p < 2^16 only: the same function at EVERY x of [x_lo, x_hi] (same domain), in chunks of `chunk`
+ *                          consecutive values, chunk k starting at x_lo + k * chunk and the last one cut at x_hi: tmax[k] and tmin[k]
+ *                          receive the chunk's largest and smallest result, bad[k] its number of results not congruent to x mod p (by
+ *                          integer remainder).  The three arrays have (x_hi - x_lo) / chunk + 1 entries, at most 2^24. */
+int spasm_amd_zp_reduce_probe(i64 prime, int where, int n, const i64 *x, int *out);
+int spasm_amd_zp_field_probe_host(i64 prime, int n, const int *a, const int *b, const int *c, int *out);
+int spasm_amd_zp_lazy_probe(i64 prime, int n, const int *a, const int *b, i64 *out);
+int spasm_amd_zp_small_lazy_probe(i64 prime, int n, const int *x, int *out);
+int spasm_amd_zp_small_lazy_scan(i64 prime, i64 x_lo, i64 x_hi, int chunk, int *tmax, int *tmin, int *bad);
+
 /* ---- Engine extension: determinants mod p (csrc/det.hpp) ----
  * The elimination computes every pivot and then keeps only their number; these entries return the determinant of a square matrix
  * as a balanced residue, at the three scales of the engine: many small matrices in one call, a split matrix block by block, a

@@ -202,6 +202,11 @@ SIGNATURES = {
     "spasm_amd_rank": (C.c_int64, [_P(CsrStruct), _P(EchelonizeOptsStruct)]),
     "spasm_amd_zp_probe": (C.c_int32, [C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     "spasm_amd_zp_sum_probe": (C.c_int32, [C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_zp_reduce_probe": (C.c_int32, [C.c_int64, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int32)]),
+    "spasm_amd_zp_field_probe_host": (C.c_int32, [C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_zp_lazy_probe": (C.c_int32, [C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int64)]),
+    "spasm_amd_zp_small_lazy_probe": (C.c_int32, [C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_zp_small_lazy_scan": (C.c_int32, [C.c_int64, C.c_int64, C.c_int64, C.c_int32, _P(C.c_int32), _P(C.c_int32), _P(C.c_int32)]),
     "spasm_amd_shard_create": (C.c_void_p, [_P(CsrStruct), C.c_int32, C.c_int32]),
     "spasm_amd_shard_create_strided": (C.c_void_p, [_P(CsrStruct), C.c_int32, C.c_int32, C.c_int32]),
     "spasm_amd_shard_elect": (C.c_int32, [C.c_void_p, C.c_void_p]),

@@ -6567,7 +6567,9 @@ spasm_amd_trsolve *trsolve_create(const struct spasm_csr *T, const int *piv, int
                 continue;
             }
             const int k = colrow[(size_t)j];
-            if (k == i) d += Tx[e];
+            // reduced entry by entry: T is the caller's (raw ints, repeated entries are summed), and a sum of raw values can leave
+            // the domain of zp_reduce (a row of p = 3 that repeats its diagonal 3 * 2^20 * p times); this one stays below 2^30 p
+            if (k == i) d += zp_reduce(F, (int64_t)Tx[e]);
             else if (k >= 0) {
 #pragma omp atomic
                 indeg[(size_t)k]++;
@@ -9320,6 +9322,132 @@ SPASM_API int spasm_amd_zp_sum_probe(i64 prime, int n, const int *a, const int *
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
         }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// zp_reduce on chosen i64 values: where = 0 the host compilation of zp.hpp in a plain loop (no device needed), where = 1 k_zp_reduce_probe
+SPASM_API int spasm_amd_zp_reduce_probe(i64 prime, int where, int n, const i64 *x, int *out)
+{
+    return abi_call("spasm_amd_zp_reduce_probe", 1, [&] {
+        if (prime <= 2 || prime > 0xfffffffbLL || n < 0 || (where != 0 && where != 1)) throw EngineError("bad arguments");
+        const ZpField F = zp_field_make(prime);
+        if (where == 0) {
+            for (int i = 0; i < n; i++) out[i] = zp_reduce(F, x[i]);
+            return 0;
+        }
+        require_device();
+        DevBuf<long long> dx;
+        DevBuf<int> dout;
+        dx.alloc((size_t)n + 1); dout.alloc((size_t)n + 1);
+        hipStream_t s = nullptr;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)n * sizeof(long long), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_zp_reduce_probe, dim3(cdiv(n, 256)), dim3(256), 0, s, F, n, dx.p, dout.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// the first six columns of spasm_amd_zp_probe (mul, axpy, add, sub, neg, inverse) from the host compilation of zp.hpp: no device needed
+SPASM_API int spasm_amd_zp_field_probe_host(i64 prime, int n, const int *a, const int *b, const int *c, int *out)
+{
+    return abi_call("spasm_amd_zp_field_probe_host", 1, [&] {
+        if (prime <= 2 || prime > 0xfffffffbLL || n < 0) throw EngineError("bad arguments");
+        const ZpField F = zp_field_make(prime);
+        for (int i = 0; i < n; i++) {
+            const int x = a[i], y = b[i], z = c[i];
+            int *o = out + (size_t)6 * i;
+            o[0] = zp_mul(F, x, y);
+            o[1] = zp_axpy(F, x, y, z);
+            o[2] = zp_add(F, x, y);
+            o[3] = zp_sub(F, x, y);
+            o[4] = zp_neg(F, x);
+            o[5] = x != 0 ? zp_inverse(F, x) : 0;
+        }
+        return 0;
+    });
+}
+
+// the raw lazy products of n pairs, unreduced: see k_zp_lazy_probe
+SPASM_API int spasm_amd_zp_lazy_probe(i64 prime, int n, const int *a, const int *b, i64 *out)
+{
+    return abi_call("spasm_amd_zp_lazy_probe", 1, [&] {
+        require_device();
+        if (prime <= 2 || prime > 0xfffffffbLL || n < 0) throw EngineError("bad arguments");
+        const ZpField F = zp_field_make(prime);
+        DevBuf<int> da, db;
+        DevBuf<long long> dout;
+        da.alloc((size_t)n + 1); db.alloc((size_t)n + 1); dout.alloc((size_t)n + 1);
+        hipStream_t s = nullptr;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(da.p, a, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(db.p, b, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            if (F.small) hipLaunchKernelGGL(k_zp_lazy_probe<true>, dim3(cdiv(n, 256)), dim3(256), 0, s, F, n, da.p, db.p, dout.p);
+            else hipLaunchKernelGGL(k_zp_lazy_probe<false>, dim3(cdiv(n, 256)), dim3(256), 0, s, F, n, da.p, db.p, dout.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// the domain of zp_small_lazy as the kernels call it: p < 2^16, |x| <= 2^30 (a product of two 24-bit operands of ZpAcc<true>) and |x / p| < 2^22
+static void zp_small_lazy_domain(i64 prime, i64 x_lo, i64 x_hi)
+{
+    if (prime <= 2 || prime >= 65536) throw EngineError("bad arguments (2 < p < 2^16 needed)");
+    const i64 top = std::min<i64>((i64)1 << 30, (prime << 22) - 1);
+    if (x_lo < -top || x_hi > top) throw EngineError("bad arguments (x outside the domain of zp_small_lazy)");
+}
+
+// the raw zp_small_lazy(x[i]) for p < 2^16: see k_zp_small_lazy_probe
+SPASM_API int spasm_amd_zp_small_lazy_probe(i64 prime, int n, const int *x, int *out)
+{
+    return abi_call("spasm_amd_zp_small_lazy_probe", 1, [&] {
+        require_device();
+        if (n < 0) throw EngineError("bad arguments");
+        i64 lo = 0, hi = 0;
+        for (int i = 0; i < n; i++) { lo = std::min<i64>(lo, x[i]); hi = std::max<i64>(hi, x[i]); }
+        zp_small_lazy_domain(prime, lo, hi);
+        const ZpField F = zp_field_make(prime);
+        DevBuf<int> dx, dout;
+        dx.alloc((size_t)n + 1); dout.alloc((size_t)n + 1);
+        hipStream_t s = nullptr;
+        if (n > 0) {
+            HIPCHK(hipMemcpyAsync(dx.p, x, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+            hipLaunchKernelGGL(k_zp_small_lazy_probe, dim3(cdiv(n, 256)), dim3(256), 0, s, F, n, dx.p, dout.p);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        }
+        HIPCHK(hipStreamSynchronize(s));
+        return 0;
+    });
+}
+
+// zp_small_lazy over every x of [x_lo, x_hi], one record per chunk of consecutive values: see k_zp_small_lazy_scan
+SPASM_API int spasm_amd_zp_small_lazy_scan(i64 prime, i64 x_lo, i64 x_hi, int chunk, int *tmax, int *tmin, int *bad)
+{
+    return abi_call("spasm_amd_zp_small_lazy_scan", 1, [&] {
+        require_device();
+        if (chunk <= 0 || x_hi < x_lo) throw EngineError("bad arguments");
+        zp_small_lazy_domain(prime, x_lo, x_hi);
+        const ZpField F = zp_field_make(prime);
+        const i64 nchunks = (x_hi - x_lo) / chunk + 1;
+        if (nchunks > ((i64)1 << 24)) throw EngineError("bad arguments (more than 2^24 chunks)");
+        DevBuf<int> dmax, dmin, dbad;
+        dmax.alloc((size_t)nchunks); dmin.alloc((size_t)nchunks); dbad.alloc((size_t)nchunks);
+        hipStream_t s = nullptr;
+        const int grid = (int)std::min<i64>(nchunks, 16384);
+        hipLaunchKernelGGL(k_zp_small_lazy_scan, dim3(grid), dim3(64), 0, s, F, (long long)x_lo, (long long)x_hi, chunk, (int)nchunks, dmax.p, dmin.p, dbad.p);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(tmax, dmax.p, (size_t)nchunks * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(tmin, dmin.p, (size_t)nchunks * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(bad, dbad.p, (size_t)nchunks * sizeof(int), hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         return 0;
     });

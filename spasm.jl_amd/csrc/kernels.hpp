@@ -3015,3 +3015,57 @@ __global__ void k_zp_sum_probe(ZpField F, int n, const int *__restrict__ a, cons
     out[i] = acc_reduce_short<SMALL>(F, acc);
 }
 
+// zp_reduce on chosen i64 arguments, one lane per value (tests/test_gpu_zp.py: the whole domain |x| <= min(3 * 2^51 * p, 2^62); the
+// host compilation of the same function runs the same values, spasm_amd_zp_reduce_probe with where = 0).
+__global__ void k_zp_reduce_probe(ZpField F, int n, const long long *__restrict__ x, int *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = zp_reduce(F, x[i]);
+}
+
+// the raw lazy product ZpAcc<SMALL>::mul_lazy(a, b), NOT reduced, widened to i64: congruence and magnitude are judged by the caller
+template <bool SMALL>
+__global__ void k_zp_lazy_probe(ZpField F, int n, const int *__restrict__ a, const int *__restrict__ b, long long *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = (long long)ZpAcc<SMALL>::mul_lazy(F, a[i], b[i]);
+}
+
+// the raw zp_small_lazy(x) of given x (p < 2^16), as ZpAcc<true>::mul_lazy calls it
+__global__ void k_zp_small_lazy_probe(ZpField F, int n, const int *__restrict__ x, int *__restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = zp_small_lazy(x[i], -F.finvp, (int)F.p);
+}
+
+// zp_small_lazy over EVERY x of [x_lo, x_hi] (p < 2^16, |x| <= 2^30): chunk c covers x_lo + c * chunk .. + chunk - 1 (cut at x_hi)
+// and is taken by one wave, lane l the values l, l + 64, ...; the wave's largest and smallest term and its number of terms that are
+// not congruent to x (plain i64 remainder of t - x, no float quotient) go out in one store each from lane 0.
+__global__ __launch_bounds__(64) void k_zp_small_lazy_scan(ZpField F, long long x_lo, long long x_hi, int chunk, int nchunks,
+                                                           int *__restrict__ tmax, int *__restrict__ tmin, int *__restrict__ bad)
+{
+    const int p = (int)F.p;
+    const float ninvp = -F.finvp;
+    for (int c = blockIdx.x; c < nchunks; c += gridDim.x) {
+        const long long lo = x_lo + (long long)c * chunk;
+        const long long rest = x_hi - lo + 1;
+        const int len = rest < (long long)chunk ? (int)rest : chunk;
+        int mx = INT_MIN, mn = INT_MAX, nb = 0;
+        for (int k = threadIdx.x; k < len; k += 64) {
+            const int x = (int)(lo + k);
+            const int t = zp_small_lazy(x, ninvp, p);
+            mx = t > mx ? t : mx;
+            mn = t < mn ? t : mn;
+            nb += ((long long)t - x) % p != 0;
+        }
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+            const int omx = __shfl_xor(mx, d), omn = __shfl_xor(mn, d);
+            mx = omx > mx ? omx : mx;
+            mn = omn < mn ? omn : mn;
+            nb += __shfl_xor(nb, d);
+        }
+        if (threadIdx.x == 0) { tmax[c] = mx; tmin[c] = mn; bad[c] = nb; }
+    }
+}
+

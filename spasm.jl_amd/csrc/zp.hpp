@@ -55,12 +55,24 @@ ZP_HD int zp_normalize(const ZpField &F, int64_t x)
     return (int)x;
 }
 
-// full reduction of an arbitrary i64 (|x| < 2^62) to the balanced residue
+// full reduction of an i64 to the balanced residue.  DOMAIN: |x| <= min(3 * 2^51 * p, 2^62) -- NOT every i64: below p = 683 the
+// quotient limit |x / p| <= 3 * 2^51 is the lower one (p = 3 stops at 9 * 2^51 < 2^54.2), from p = 683 upward it is 2^62.
+//   With u = 2^-53: (double)x = x (1 + e1), dinvp = (1 + e2) / p (one correctly rounded division of exact operands) and the
+//   product y rounds once more, |e_i| <= u: y = (x / p)(1 + e) with |e| <= (1 + u)^3 - 1 < 3.0000001 u.
+//     |y| <  2^52: rint adds at most 1/2 and |x / p| < 2^52 (1 + 4 u), so |q - x / p| < 1/2 + 1.5000002 < 2.01;
+//     |y| >= 2^52: y is an integer, q = y, and |q - x / p| <= 3 * 2^51 * 3.0000001 * 2^-53 < 2.26.
+//   So |r| = |x - q p| < 2.26 p, and the two corrections below bring every |r| < 2.5 p (an integer r <= halfp + 2 p, p odd)
+//   into [mhalfp, halfp].  Nothing wraps: |q p| <= |x| + 2.26 p < 2^63.  One correction is enough while |x / p| <= 2^51
+//   (|q - x / p| < 1.26, |r| < 1.5 p), which is all that the callers' sums reach; the second one carries the
+//   rest of the domain and is needed there (p = 479 and 503 from |x / p| ~ 2^52.3).  The limit is not far away: at
+//   |x / p| ~ 2^53.4 the quotient is 3 off and the result wrong (first at |x| ~ 2^55 for p = 3, 2^56 for p = 5 and 7, 2^61 for
+//   p = 127 and 251), so a caller that can exceed the domain reduces earlier or splits its sum.
+//   tests/test_zp_host.py (host compilation) and tests/test_gpu_zp.py (device) run the domain to its edge for 17 primes.
 ZP_HD int zp_reduce(const ZpField &F, int64_t x)
 {
     int64_t q = (int64_t)rint((double)x * F.dinvp);
     int64_t r = x - q * F.p;
-    // q is within 1 of the exact quotient, so one correction either way is enough
+    // q is within 2 of the exact quotient on the domain above: two corrections either way
     if (r < F.mhalfp) r += F.p;
     else if (r > F.halfp) r -= F.p;
     if (r < F.mhalfp) r += F.p;

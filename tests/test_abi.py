@@ -98,7 +98,10 @@ def test_hot_path_fails_loudly_without_gpu(S):
 
 def test_field_probes_fail_loudly_without_gpu(S):
     """spasm_amd_zp_probe / spasm_amd_zp_sum_probe run the field arithmetic ON the device: without one they return an error,
-    name the cause and leave the output alone (there is no host fall-back that could stand in for the kernels)."""
+    name the cause and leave the output alone (there is no host fall-back that could stand in for the kernels).  The probes of
+    the single primitives behave the same where they run a kernel, and their host entries run without a device
+    (check_primitive_probes below)."""
+    check_primitive_probes(S)
     lib = S._abi.lib()
     P = C.POINTER(C.c_int32)
     a = np.array([1, -1, 32760], dtype=np.int32)
@@ -119,6 +122,52 @@ def test_field_probes_fail_loudly_without_gpu(S):
     assert rc_sum != 0 and "spasm_amd_zp_sum_probe" in err_sum and "no HIP device" in err_sum, err_sum
     assert rc != 0 and "no HIP device" in err, err
     assert (out == 0x55555555).all() and (out8 == 0x55555555).all()
+
+
+def check_primitive_probes(S):
+    """The probes of the single primitives: the entries that run a kernel (zp_reduce_probe with where = 1, zp_lazy_probe,
+    zp_small_lazy_probe, zp_small_lazy_scan) return the same "no HIP device" error as the two above and write nothing; the host
+    entries (zp_reduce_probe with where = 0, zp_field_probe_host) succeed without a device."""
+    lib = S._abi.lib()
+    P = C.POINTER(C.c_int32)
+    P64 = C.POINTER(C.c_int64)
+    a = np.array([1, -1, 32760], dtype=np.int32)
+    b = np.array([32760, 32760, -32760], dtype=np.int32)
+    x64 = np.array([32760 * 32760, -(2**62), 2**62], dtype=np.int64)
+    bal = lambda v: (v + 32760) % 65521 - 32760  # noqa: E731
+    ptr = lambda v: v.ctypes.data_as(P)  # noqa: E731
+    # the host entries: with or without a device
+    out = np.full(3, 0x55555555, dtype=np.int32)
+    assert lib.spasm_amd_zp_reduce_probe(65521, 0, 3, x64.ctypes.data_as(P64), ptr(out)) == 0, S._abi.last_error()
+    assert out.tolist() == [bal(int(v)) for v in x64]
+    out6 = np.full(18, 0x55555555, dtype=np.int32)
+    assert lib.spasm_amd_zp_field_probe_host(65521, 3, ptr(a), ptr(b), ptr(a), ptr(out6)) == 0, S._abi.last_error()
+    assert out6.reshape(3, 6).tolist() == [[bal(x * y), bal(x * y + x), bal(x + y), bal(x - y), bal(-x), bal(pow(x, -1, 65521))]
+                                           for x, y in zip(a.tolist(), b.tolist())]
+    # the device entries
+    out = np.full(3, 0x55555555, dtype=np.int32)
+    out64 = np.full(3, 0x5555555555555555, dtype=np.int64)
+    tmax, tmin, bad = (np.full(1, 0x55555555, dtype=np.int32) for _ in range(3))
+    calls = [
+        ("spasm_amd_zp_reduce_probe", lambda: lib.spasm_amd_zp_reduce_probe(65521, 1, 3, x64.ctypes.data_as(P64), ptr(out))),
+        ("spasm_amd_zp_lazy_probe", lambda: lib.spasm_amd_zp_lazy_probe(65521, 3, ptr(a), ptr(b), out64.ctypes.data_as(P64))),
+        ("spasm_amd_zp_small_lazy_probe", lambda: lib.spasm_amd_zp_small_lazy_probe(65521, 3, ptr(a), ptr(out))),
+        ("spasm_amd_zp_small_lazy_scan", lambda: lib.spasm_amd_zp_small_lazy_scan(65521, -100, 100, 65536, ptr(tmax), ptr(tmin), ptr(bad))),
+    ]
+    have = lib.spasm_amd_device_count() > 0
+    for name, call in calls:
+        rc = call()
+        err = S._abi.last_error()
+        if have:
+            assert rc == 0, (name, err)
+        else:
+            assert rc != 0 and name in err and "no HIP device" in err, (name, err)
+    if have:
+        assert out.tolist() == [bal(int(v)) for v in a] and bad.tolist() == [0] and tmax[0] <= 32760 + 256 and tmin[0] >= -32760 - 256
+        assert all((int(t) - x * y) % 65521 == 0 for t, x, y in zip(out64, a.tolist(), b.tolist()))
+        return
+    assert (out == 0x55555555).all() and (out64 == 0x5555555555555555).all()
+    assert tmax[0] == tmin[0] == bad[0] == 0x55555555
 
 
 def test_dense_shard_steps_out_of_order_are_errors_not_crashes():

@@ -8,6 +8,8 @@ B. Layered matrices whose level widths sit on TRS_WIDE = 256, TRS_CHUNK = 64 and
    the plan reported by TriangularSolver.stats() is compared with a restatement of the packing rule.
 C. The constructions themselves, on the CPU: an independent Kahn pass finds the requested widths, and an entry-by-entry sparse
    product agrees with the right-hand sides that the GPU tests use.
+D. The diagonal of a row that repeats its pivot entry millions of times with unreduced values: the sum of the raw values leaves the
+   domain of zp_reduce, so trsolve_create reduces entry by entry.
 
 Every comparison is exact integer equality against Python ints or int64 numpy."""
 from types import SimpleNamespace
@@ -381,3 +383,41 @@ def test_layered_plan_and_solution(S, name, p, kind):
                 res = bal(c.R.astype(np.int64) - xT(X, c.D, p), p)
                 assert np.array_equal(B, res) and not B[c.pcol].any() and not X[idle].any()
             assert np.array_equal(X, X65[:, :k]) and np.array_equal(B, B65[:, :k]) and np.array_equal(ok, ~B65[:, :k].any(axis=0)), k
+
+
+# ---- D: the diagonal of a row that repeats its pivot entry with unreduced values ----------------------------------------------------
+
+# zp_reduce is exact for |x| <= min(3 * 2^51 * p, 2^62) (csrc/zp.hpp).  trsolve_create sums the entries of a row on its own pivot
+# column -- the caller's raw ints, repeated entries included -- so the sum of the raw values leaves that domain once one row of
+# p = 3 repeats a value near 2^31 more than 3 * 2^20 * p = 9 437 184 times; the entries are therefore reduced one by one.
+# 9 437 185 is the first length past the domain; 16 777 244 is the first one at which the quotient of the raw sum
+# N * (2^31 - 1) is 3 off, so that one reduction of it gives a wrong residue (found with the same double arithmetic on the CPU).
+DIAG_V = 2**31 - 1
+DIAG_LENGTHS = [3 * 2**20 * 3 + 1, 16777244]
+
+
+@gpu
+@pytest.mark.parametrize("N", DIAG_LENGTHS)
+def test_diagonal_of_repeated_unreduced_entries(S, N):
+    """One row, one column, p = 3: N entries 2^31 - 1 on the pivot column.  The diagonal is N * (2^31 - 1) mod 3 in Python integers
+    (1 for the first length, -1 for the second).  Back solve: x = b / d for b in {1, -1}; forward solve: accepted when d = 1, and
+    refused with the true value in the text otherwise."""
+    p = 3
+    assert N * DIAG_V > 3 * 2**51 * p >= (DIAG_LENGTHS[0] - 1) * DIAG_V
+    d = int(bal(np.asarray([N * DIAG_V % p]), p)[0])
+    assert d in (1, -1)
+    T = S.CSR.from_arrays(1, 1, np.array([0, N], dtype=np.int64), np.zeros(N, dtype=np.int32), np.full(N, DIAG_V, dtype=np.int32), prime=p)
+    piv = np.zeros(1, dtype=np.int32)
+    with S.TriangularSolver(T, piv, "back") as ts:
+        B = np.array([[1, -1]], dtype=np.int32)
+        X, ok = ts.solve(B)
+        assert ok.all() and not B.any()
+        assert X.tolist() == [[d, -d]]  # d is its own inverse
+    if d == 1:
+        with S.TriangularSolver(T, piv, "forward") as ts:
+            B = np.array([-1], dtype=np.int32)
+            X, ok = ts.solve(B)
+            assert ok and X.tolist() == [-1]
+    else:
+        with pytest.raises(S.SpasmError, match=r"the pivot of row 0 \(column 0\) is -1, not 1"):
+            S.TriangularSolver(T, piv, "forward")
