@@ -966,6 +966,62 @@ int spasm_amd_spmv_minpoly(spasm_amd_spmv *op, int K, uint64_t seed, int maxdeg,
 int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg);
 void spasm_amd_minpoly_stats(i64 *out);   /* of the last Krylov / Berlekamp-Massey / minpoly call of this thread */
 
+/* ---- Engine extension: polynomials of A applied to vectors, and sparse solves mod p without fill-in by Wiedemann's method
+ *      (csrc/horner.hpp) ----
+ * The solve that stays in O(nnz + n * K) memory: no elimination, no limit on n below 2^24.  One Horner step per product,
+ * Y <- op(A) X + c * B, on the row classes of the resident operator; the solve certifies every answer on the device.
+ *   poly_apply    op is a resident operator of a SQUARE n x n matrix ("not square (3 x 2)" otherwise), 1 <= K <= 64.
+ *                 X[:, c] <- f_c(op(A)) * V[:, c] with f_c = coef[c * ldc + 0 .. deg[c]], low degree first (any int32 is reduced on
+ *                 load; deg[c] = -1 is the zero polynomial; ldc >= max(deg) + 1); trans = 1 uses A^T.  deg and coef are HOST arrays.
+ *                 V and X are row-major n x K host arrays with leading dimensions ldv, ldx >= K (the layout of
+ *                 spasm_amd_krylov_sequence; any int32 in V is reduced where it is read); V must not overlap X and is not
+ *                 modified.  Columns of lower degree are zero-padded at the top of the schedule, so the call makes max(deg) products
+ *                 with A, each one launch per non-empty row class of the operator (plus the combine when there are long rows),
+ *                 after one elementwise launch for the leading coefficients.  The results are balanced residues.
+ *   poly_apply_dev  the same with V and X on the device, enqueued on the hipStream_t stream without any host synchronization
+ *                 (NULL: the default stream, and no synchronization either).  The coefficient table is uploaded once per call.
+ *                 One call at a time per operator: it uses the operator's two Krylov buffers.
+ *   wiedemann_solve, spmv_wiedemann_solve, dcsr_wiedemann_solve
+ *                 A host matrix, a resident operator, a resident matrix (on its device).  trans = 0 solves A x = b, trans = 1
+ *                 solves x A = b (the orientation of the library's gesv).  B and X are n x K row-major HOST arrays (ldb, ldx >= K),
+ *                 status has K words, 1 <= K <= 64.  Column c is independent of the others:
+ *                   1. the sequence s_i = u_c^T op(A)^i b_c is projected (2 * maxdeg terms when maxdeg = n, 2 * maxdeg + 2 when
+ *                      maxdeg < n; maxdeg <= 0 or > n means n; a degree above maxdeg is refused with "degree bound too small", as
+ *                      in minpoly).  u_c is column c of U (packed n x K) when U is given, else column c of the U of
+ *                      minpoly_vectors(n, K, seed + t) on try t: a column's result depends only on (A, b_c, u_c);
+ *                   2. Berlekamp-Massey gives its polynomial f_c;
+ *                   3. with q_c = (f_c - f_c(0)) / x, one Horner run gives x_c = -q_c(op(A)) b_c / f_c(0) when f_c(0) != 0, and
+ *                      z_c = q_c(op(A)) b_c when f_c(0) == 0;
+ *                   4. one more step R <- op(A) X + r B (r_c = -1 or 0) with the non-zero counts of R and X certifies the column.
+ *                 status[c] = 1  solved: f_c(0) != 0 and R_c == 0, so op(A) x_c = b_c holds (b_c = 0 gives x_c = 0);
+ *                 status[c] = 2  kernel vector: f_c(0) == 0, R_c == 0 and X_c != 0, so X_c is a non-zero vector with
+ *                                op(A) X_c = 0 and A is singular: that is certain; it says nothing about whether b_c is in the image;
+ *                 status[c] = 0  undecided after every try (the projection lost a factor each time): column c of X is zero.
+ *                 Undecided columns are packed into a narrower array and tried again with the next seed, `tries` tries in all
+ *                 (tries <= 0 means 3; one try only when U is given).  A status is never 1 or 2 without the device check having
+ *                 passed.  The return value is 0 when the call ran, whatever the statuses.  n == 0: every status is 1, no device.
+ *   stats         of the last of these calls of this thread: out[10] = n, K, tries used, products with A (sequences + Horner +
+ *                 checks), launches, largest degree of an f_c, columns solved, columns with a kernel vector, device microseconds
+ *                 of the sequences + Berlekamp-Massey and of Horner + checks (HIP events).  poly_apply fills n, K, products,
+ *                 launches.  Every call clears what it does not fill.
+ *   deterministic two runs give the same bytes (the counts are integer sums)
+ *   errors        a NULL operator / matrix / array, a matrix that is not square, K outside 1 .. 64 ("K out of range"), "ldb < K",
+ *                 "ldx < K", "ldv < K", "polynomial 2: ldc < deg + 1 ..", "polynomial 2: a degree below -1 (-2)", "V must not
+ *                 overlap X", a prime outside 3 .. 0xFFFFFFFB, n >= 2^24, "degree bound too small", no device ("no HIP device"),
+ *                 out of memory: -1, NO output word is written, spasm_amd_last_error() names the cause.  The argument errors are
+ *                 found before a device is looked for (for a host matrix; an operator or a resident matrix has one already). */
+int spasm_amd_poly_apply(spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const spasm_ZZp *V, i64 ldv,
+                         spasm_ZZp *X, i64 ldx);
+int spasm_amd_poly_apply_dev(spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const spasm_ZZp *V, i64 ldv,
+                             spasm_ZZp *X, i64 ldx, void *stream);
+int spasm_amd_wiedemann_solve(const struct spasm_csr *A, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                              const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status);
+int spasm_amd_spmv_wiedemann_solve(spasm_amd_spmv *op, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                                   const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status);
+int spasm_amd_dcsr_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                                   const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status);
+void spasm_amd_wiedemann_stats(i64 *out);   /* of the last poly_apply / Wiedemann solve call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

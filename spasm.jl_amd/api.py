@@ -2188,3 +2188,122 @@ def minpoly_stats():
 SpMV.krylov_sequence = krylov_sequence
 SpMV.minpoly = minpoly
 DeviceCSR.minpoly = minpoly
+
+
+# ---------------------------------------------------------------------------------------------
+# Polynomials of A applied to vectors, and Wiedemann's solve  (spasm_amd_poly_apply*, _wiedemann_solve*; csrc/horner.hpp)
+# ---------------------------------------------------------------------------------------------
+WIEDEMANN_STATS = ("n", "K", "tries", "products", "launches", "degree", "solved", "kernel_vectors", "sequence_device_us", "horner_device_us")
+
+
+def _poly_table(polys, k):
+    """(deg, coef, ldc) of k polynomials given low degree first; an empty one is the zero polynomial"""
+    polys = [np.asarray(f).reshape(-1) for f in polys]
+    if len(polys) != k:
+        raise ValueError(f"{k} polynomials expected, one per column, not {len(polys)}")
+    for f in polys:
+        if f.size and (f.dtype.kind not in "iu" or f.min() < -2**31 or f.max() > 2**31 - 1):
+            raise TypeError("the coefficients must be integers that fit int32")
+    ldc = max([f.size for f in polys] + [1])
+    coef = np.zeros((k, ldc), dtype=np.int32)
+    for c, f in enumerate(polys):
+        coef[c, : f.size] = f
+    deg = np.array([f.size - 1 for f in polys], dtype=np.int32)
+    return deg, coef, ldc
+
+
+def poly_apply(op, polys, V, trans=False):
+    """poly_apply(op, polys, V, trans=False) -> X with X[:, c] = f_c(A) V[:, c] mod p as balanced residues, A the square matrix of
+    the SpMV operator op (A^T with trans=True) and f_c = polys[c], low degree first (any int32; [] is the zero polynomial).  V is
+    n x K, 1 <= K <= 64, or n entries with polys one polynomial.  int32 numpy arrays (spasm_amd_poly_apply) or int32 torch tensors
+    on the current device (enqueued on the current stream without a host synchronization; X is a tensor:
+    spasm_amd_poly_apply_dev).  Horner's rule: max(deg) products with A.  V is not modified."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n = op.shape[0]
+    is_torch = type(V).__module__.startswith("torch")
+    ndim = V.dim() if is_torch else getattr(V, "ndim", 0)
+    if ndim not in (1, 2) or V.shape[0] != n:
+        raise ValueError(f"V must have shape ({n},) or ({n}, K)")
+    k = 1 if ndim == 1 else int(V.shape[1])
+    if ndim == 1 and (len(polys) == 0 or np.ndim(polys[0]) == 0):
+        polys = [polys]
+    deg, coef, ldc = _poly_table(polys, k)
+    lib = _abi.lib()
+    if is_torch:
+        import torch
+
+        if V.dtype != torch.int32 or V.device.type != "cuda" or V.device.index != torch.cuda.current_device():
+            raise TypeError("V must be an int32 tensor on the current device")
+        if V.stride(-1) != 1 or (ndim == 2 and V.shape[0] > 1 and V.stride(0) < k):
+            raise ValueError("V must have unit stride along its rows")
+        ldv = k if ndim == 1 else max(V.stride(0), k)
+        X = torch.empty(tuple(V.shape), dtype=torch.int32, device=V.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.spasm_amd_poly_apply_dev(op._op, int(bool(trans)), k, deg.ctypes.data, coef.ctypes.data, ldc, C.c_void_p(V.data_ptr()), ldv,
+                                          C.c_void_p(X.data_ptr()), k, C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return X
+    if not isinstance(V, np.ndarray) or V.dtype != np.int32:
+        raise TypeError("V must be an int32 numpy array or torch tensor")
+    Vc = _rows_view(V, "V")
+    ldv = k if ndim == 1 else max(Vc.strides[0] // 4, k)
+    X = np.zeros(V.shape, dtype=np.int32)
+    rc = lib.spasm_amd_poly_apply(op._op, int(bool(trans)), k, deg.ctypes.data, coef.ctypes.data, ldc, Vc.ctypes.data, ldv, X.ctypes.data, k)
+    if rc != 0:
+        raise SpasmError(_abi.last_error())
+    return X
+
+
+def wiedemann_solve(A, B, trans=False, seed=0, tries=3, maxdeg=None, U=None):
+    """wiedemann_solve(A, B, trans=False, seed=0, tries=3, maxdeg=None, U=None) -> (X, status): A x = b (x A = b with trans=True)
+    for every column b of B by Wiedemann's method, without elimination or fill-in.  A is a square CSR (spasm_amd_wiedemann_solve),
+    an SpMV operator (spasm_amd_spmv_wiedemann_solve) or a DeviceCSR (spasm_amd_dcsr_wiedemann_solve).  B is n x K, 1 <= K <= 64,
+    or n entries: one right-hand side (X then has n entries).  X is int32, balanced residues; status is an int32 array, one per
+    column:  1  solved, A x = b verified on the device;  2  the column of X is a non-zero vector of the kernel of A (A is singular:
+    certain; nothing is said about b);  0  undecided after `tries` tries with the seeds seed, seed + 1, .. (the column of X is
+    zero).  U (n x K) fixes the projection vectors and allows one try only.  maxdeg bounds the degree of the polynomials (None: n)."""
+    lib = _abi.lib()
+    if isinstance(A, CSR):
+        who, fn, arg, n = "spasm_amd_wiedemann_solve", lib.spasm_amd_wiedemann_solve, A.data, A.n
+    elif isinstance(A, SpMV):
+        if not A._op:
+            raise SpasmError("the operator is closed")
+        who, fn, arg, n = "spasm_amd_spmv_wiedemann_solve", lib.spasm_amd_spmv_wiedemann_solve, A._op, A.shape[0]
+    elif isinstance(A, DeviceCSR):
+        who, fn, arg, n = "spasm_amd_dcsr_wiedemann_solve", lib.spasm_amd_dcsr_wiedemann_solve, A._need(), A.shape[0]
+    else:
+        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    if not isinstance(B, np.ndarray) or B.dtype != np.int32 or B.ndim not in (1, 2) or B.shape[0] != n:
+        raise TypeError(f"B must be an int32 numpy array of shape ({n},) or ({n}, K)")
+    k = 1 if B.ndim == 1 else B.shape[1]
+    Bc = _rows_view(B, "B") if n > 0 else B   # (numpy gives an array without rows strides of its own)
+    ldb = k if B.ndim == 1 or n == 0 else max(Bc.strides[0] // 4, k)
+    uptr = None
+    if U is not None:
+        if not isinstance(U, np.ndarray) or U.dtype != np.int32 or U.size != n * k or U.shape[0] != n or not U.flags["C_CONTIGUOUS"]:
+            raise TypeError(f"U must be a contiguous int32 numpy array of shape ({n}, {k})")
+        uptr = U.ctypes.data
+    X = np.zeros(B.shape, dtype=np.int32)
+    status = np.zeros(max(k, 1), dtype=np.int32)
+    with _quiet(True):
+        rc = fn(arg, int(bool(trans)), int(k), Bc.ctypes.data, ldb, int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), 0 if maxdeg is None else int(maxdeg),
+                uptr, X.ctypes.data, max(k, 1), status.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return X, status[:k]
+
+
+def wiedemann_stats():
+    """Counters of the last poly_apply / wiedemann_solve call of this thread (spasm_amd_wiedemann_stats), keyed by WIEDEMANN_STATS."""
+    out = (C.c_int64 * 10)()
+    _abi.lib().spasm_amd_wiedemann_stats(out)
+    return {k: int(v) for k, v in zip(WIEDEMANN_STATS, out)}
+
+
+SpMV.poly_apply = poly_apply
+SpMV.wiedemann_solve = wiedemann_solve
+DeviceCSR.wiedemann_solve = wiedemann_solve

@@ -5529,6 +5529,14 @@ void spmv_chunk(const SpmvView &V, const ZpField &F, int kw, int kc, const int *
 struct KrylovWork {
     DevBuf<int> w0, w1;
     DevBuf<long long> acc;
+    // the coefficient table of a Horner run (horner.hpp): the host copy lives here until its upload has completed
+    DevBuf<int> tab;
+    std::vector<int> htab;
+    hipEvent_t tab_up = nullptr;
+    KrylovWork() {}
+    KrylovWork(const KrylovWork &) = delete;
+    KrylovWork &operator=(const KrylovWork &) = delete;
+    ~KrylovWork() { if (tab_up) (void)hipEventDestroy(tab_up); }
 };
 
 } // namespace
@@ -11149,6 +11157,24 @@ void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int 
     *deg = (int)r.size() - 1;
 }
 
+// a view of the resident entries of a square matrix (n > 0): the row pointers serve as starts, the lengths are their differences
+void dcsr_square_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s)
+{
+    view.rows = view.cols = D->n;
+    view.start = D->p.p;
+    view.ent = D->ent.p;
+    view.tlen.alloc((size_t)D->n + 1);
+    hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(D->n, 256)), dim3(256), 0, s, D->n, D->p.p, view.tlen.p);
+    HIPCHK(hipGetLastError());
+    view.len = view.tlen.p;
+    std::vector<i64d> hp((size_t)D->n + 1);
+    HIPCHK(hipMemcpyAsync(hp.data(), D->p.p, hp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<i64> hl((size_t)D->n);
+    for (int i = 0; i < D->n; i++) hl[(size_t)i] = hp[(size_t)i + 1] - hp[(size_t)i];
+    view.bin(hl, s);
+}
+
 void minpoly_check_out(const spasm_ZZp *U, const spasm_ZZp *X, const spasm_ZZp *coef, const int *deg)
 {
     if (!coef || !deg) throw EngineError("NULL array");
@@ -11288,22 +11314,8 @@ SPASM_API int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t se
         K = minpoly_K(K);
         minpoly_check_out(U, V, coef, deg);
         if (D->n == 0) { coef[0] = 1; *deg = 0; return 0; }
-        // a view of the resident entries: the row pointers serve as starts, the lengths are their differences
-        hipStream_t s = nullptr;
         SpmvView view;
-        view.rows = view.cols = D->n;
-        view.start = D->p.p;
-        view.ent = D->ent.p;
-        view.tlen.alloc((size_t)D->n + 1);
-        hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(D->n, 256)), dim3(256), 0, s, D->n, D->p.p, view.tlen.p);
-        HIPCHK(hipGetLastError());
-        view.len = view.tlen.p;
-        std::vector<i64d> hp((size_t)D->n + 1);
-        HIPCHK(hipMemcpyAsync(hp.data(), D->p.p, hp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        std::vector<i64> hl((size_t)D->n);
-        for (int i = 0; i < D->n; i++) hl[(size_t)i] = hp[(size_t)i + 1] - hp[(size_t)i];
-        view.bin(hl, s);
+        dcsr_square_view(D, view, nullptr);
         minpoly_run(view, D->F, K, seed, maxdeg, U, V, coef, deg);
         return 0;
     });
@@ -11312,6 +11324,449 @@ SPASM_API int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t se
 SPASM_API void spasm_amd_minpoly_stats(i64 *out)
 {
     if (out) memcpy(out, g_minpoly_stats, sizeof g_minpoly_stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Polynomials of the resident exact product applied to vectors (Horner's rule, horner.hpp), and on top of them sparse solves
+// without fill-in by Wiedemann's method that certify their own answers.
+// ------------------------------------------------------------------------------------------------
+#include "horner.hpp"
+
+namespace {
+
+// n, K, tries used, products with A, launches, largest degree, columns solved, columns with a kernel vector, device us of the
+// sequences + Berlekamp-Massey, device us of Horner + check
+thread_local i64 g_wied_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+void wied_stats_reset() { memset(g_wied_stats, 0, sizeof g_wied_stats); }
+
+// the steps of table rows T[0 .. rows) (KW words each).  X0 == NULL: the run starts from X = 0, so its first step is the plain
+// scale and rows - 1 products follow; else every row is a product and the first one reads X0.  The last step writes Yout (leading
+// dimension ldyo) and, when cnt is given, adds its non-zero counts to cnt[0 .. KW); the steps between ping-pong in W.
+template <bool SMALL, int KW>
+int horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout, i64 ldyo,
+                  KrylovWork &W, long long *cnt, int cap, hipStream_t s)
+{
+    constexpr int TS = spmv_short_team(KW);
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
+    auto grid = [&](i64 lanes) { return dim3((unsigned)std::max(1, std::min(cdiv(lanes, KRY_BS), cap))); };
+    int launches = 0;
+    const int *X = X0;
+    i64d ldx = (i64d)ldx0;
+    for (int i = 0; i < rows && n > 0; i++) {
+        const bool last = i == rows - 1;
+        int *Y = last ? Yout : (X == W.w0.p ? W.w1.p : W.w0.p);
+        const i64d ldy = last ? (i64d)ldyo : (i64d)KW;
+        long long *cp = last ? cnt : nullptr;
+        const int *Ti = T + (size_t)i * KW;
+        if (!X) {
+            hipLaunchKernelGGL((k_horner_scale<KW>), grid((i64)n * KW), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, Ti, B, (i64d)ldb, Y, ldy, cp);
+            launches++;
+        } else {
+            if (V.nshort > 0) {
+                hipLaunchKernelGGL((k_horner_step<SMALL, KW, TS, false>), grid((i64)V.nshort * TS), dim3(KRY_BS), 0, s, V.nshort,
+                                   V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, nullptr, Ti, B,
+                                   (i64d)ldb, cp);
+                launches++;
+            }
+            if (V.nmid > 0) {
+                hipLaunchKernelGGL((k_horner_step<SMALL, KW, 64, false>), grid((i64)V.nmid * 64), dim3(KRY_BS), 0, s, V.nmid, V.mid_rows.p, nullptr,
+                                   V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, nullptr, Ti, B, (i64d)ldb, cp);
+                launches++;
+            }
+            if (V.nlong > 0) {
+                hipLaunchKernelGGL((k_horner_step<SMALL, KW, 64, true>), grid((i64)V.nseg * 64), dim3(KRY_BS), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p,
+                                   V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, V.part.p, Ti, B, (i64d)ldb, nullptr);
+                hipLaunchKernelGGL((k_horner_combine<KW>), grid((i64)V.nlong * KW), dim3(KRY_BS), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p,
+                                   kc, F, hp, mhp, Y, ldy, Ti, B, (i64d)ldb, cp);
+                launches += 2;
+            }
+        }
+        HIPCHK(hipGetLastError());
+        X = Y;
+        ldx = ldy;
+    }
+    return launches;
+}
+
+template <bool SMALL>
+int horner_chunk(int kw, const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout,
+                 i64 ldyo, KrylovWork &W, long long *cnt, int cap, hipStream_t s)
+{
+    switch (kw) {
+    case 1: return horner_launch<SMALL, 1>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    case 2: return horner_launch<SMALL, 2>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    case 4: return horner_launch<SMALL, 4>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    case 8: return horner_launch<SMALL, 8>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    case 16: return horner_launch<SMALL, 16>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    case 32: return horner_launch<SMALL, 32>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    default: return horner_launch<SMALL, 64>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    }
+}
+
+int horner_kw(int K)
+{
+    int kw = 1;
+    while (kw < K) kw <<= 1;
+    return kw;
+}
+
+// rows >= 1 Horner steps on device arrays, enqueued on s; no host synchronization.  T is the device table, rows x horner_kw(K)
+// canonical residues.  Returns the launches.
+int horner_run(const SpmvView &V, const ZpField &F, int K, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout, i64 ldyo,
+               KrylovWork &W, long long *cnt, hipStream_t s)
+{
+    const int kw = horner_kw(K);
+    int dev = 0, cu = 256;
+    HIPCHK(hipGetDevice(&dev));
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    const size_t words = (size_t)V.rows * kw;
+    if (rows > 1) {
+        W.w0.ensure(words);
+        if (rows > 2) W.w1.ensure(words);
+    }
+    const int cap = cu * KRY_WG_PER_CU;
+    return F.small ? horner_chunk<true>(kw, V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s)
+                   : horner_chunk<false>(kw, V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+}
+
+inline uint64_t wied_residue(int x, uint64_t p)
+{
+    const int64_t r = (int64_t)x % (int64_t)p;
+    return (uint64_t)(r < 0 ? r + (int64_t)p : r);
+}
+
+inline int wied_balanced(uint64_t w, uint64_t p) { return (int)(w > p / 2 ? (int64_t)w - (int64_t)p : (int64_t)w); }
+
+// the table of spasm_amd_poly_apply in W.htab: row s holds the coefficients of degree D - s, D = max(deg); zeros above a
+// column's degree.  Returns D (-1: every polynomial is zero).
+int poly_table(const ZpField &F, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, std::vector<int> &tab)
+{
+    int D = -1;
+    for (int c = 0; c < K; c++) D = std::max(D, deg[c]);
+    const int kw = horner_kw(K);
+    tab.assign((size_t)(D + 1) * kw, 0);
+    const uint64_t p = (uint64_t)F.p;
+    for (int c = 0; c < K; c++)
+        for (int j = 0; j <= deg[c]; j++) tab[(size_t)(D - j) * kw + c] = wied_balanced(wied_residue(coef[(i64)c * ldc + j], p), p);
+    return D;
+}
+
+void poly_apply_check(const spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const spasm_ZZp *V, i64 ldv,
+                      const spasm_ZZp *X, i64 ldx)
+{
+    if (!op) throw EngineError("NULL operator");
+    minpoly_square(op->A.n, op->A.m);
+    if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
+    if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
+    if (ldv < K) throw EngineError("ldv < K");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (!deg || !coef) throw EngineError("NULL array");
+    for (int c = 0; c < K; c++) {
+        char msg[112];
+        if (deg[c] < -1) {
+            snprintf(msg, sizeof msg, "polynomial %d: a degree below -1 (%d)", c, deg[c]);
+            throw EngineError(msg);
+        }
+        if (deg[c] >= (1 << 24)) {
+            snprintf(msg, sizeof msg, "polynomial %d: degree limited to < 2^24 (%d)", c, deg[c]);
+            throw EngineError(msg);
+        }
+        if (ldc < (i64)deg[c] + 1) {
+            snprintf(msg, sizeof msg, "polynomial %d: ldc < deg + 1 (ldc = %lld, deg = %d)", c, (long long)ldc, deg[c]);
+            throw EngineError(msg);
+        }
+    }
+    const i64 n = op->A.n;
+    if (n > 0) {
+        if (!V || !X) throw EngineError("NULL array");
+        const uintptr_t v0 = (uintptr_t)V, v1 = v0 + (size_t)((n - 1) * ldv + K) * sizeof(int);
+        const uintptr_t x0 = (uintptr_t)X, x1 = x0 + (size_t)((n - 1) * ldx + K) * sizeof(int);
+        if (v0 < x1 && x0 < v1) throw EngineError("V must not overlap X");
+    }
+}
+
+// X <- f_c(op(A)) V on device arrays, enqueued on s: the table goes up once, then max(deg) products.  Returns the launches.
+int poly_apply_dev(spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const int *dV, i64 ldv, int *dX, i64 ldx,
+                   hipStream_t s, int *products)
+{
+    if (trans) op->build_transpose();
+    const SpmvView &view = trans ? op->tr : op->fwd;
+    KrylovWork &W = op->kry;
+    const size_t n = (size_t)op->A.n;
+    // the host copy of the previous call's table may still be on its way up
+    if (W.tab_up) HIPCHK(hipEventSynchronize(W.tab_up));
+    else HIPCHK(hipEventCreateWithFlags(&W.tab_up, hipEventDisableTiming));
+    const int D = poly_table(op->F, K, deg, coef, ldc, W.htab);
+    *products = std::max(D, 0);
+    if (D < 0) {
+        HIPCHK(hipMemset2DAsync(dX, (size_t)ldx * sizeof(int), 0, (size_t)K * sizeof(int), n, s));
+        return 0;
+    }
+    W.tab.ensure(W.htab.size());
+    HIPCHK(hipMemcpyAsync(W.tab.p, W.htab.data(), W.htab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(W.tab_up, s));
+    return horner_run(view, op->F, K, D + 1, W.tab.p, dV, ldv, nullptr, 0, dX, ldx, W, nullptr, s);
+}
+
+void wied_check(int n, int m, int trans, int K, const void *B, i64 ldb, const void *X, i64 ldx, const int *status)
+{
+    minpoly_square(n, m);
+    if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
+    if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
+    if (ldb < K) throw EngineError("ldb < K");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (!status || (n > 0 && (!B || !X))) throw EngineError("NULL array");
+    if (n >= (1 << 24)) throw EngineError("Wiedemann solve limited to n < 2^24");
+}
+
+// the system with no unknown: the empty x solves it
+void wied_empty(int K, int *status)
+{
+    for (int c = 0; c < K; c++) status[c] = 1;
+    g_wied_stats[1] = K;
+    g_wied_stats[6] = K;
+}
+
+// The solve behind the three entries: V is the view of op(A), square, n > 0; the arguments have been checked.  Nothing is written
+// to X or status before every try has run.
+void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg, const spasm_ZZp *U,
+              spasm_ZZp *X, i64 ldx, int *status)
+{
+    const int n = V.rows;
+    const uint64_t p = (uint64_t)F.p;
+    const int md = (maxdeg <= 0 || maxdeg > n) ? n : maxdeg;
+    // 2 * md terms determine a recurrence of degree <= md; two more terms show a degree above md as L > md (see the header)
+    const int len = md < n ? 2 * md + 2 : 2 * n;
+    bm_check_len(F, len);
+    const int ntries = U ? 1 : (tries <= 0 ? 3 : tries);
+    const i64 ldc = (i64)len + 1;
+    const int cls = bm_class(len, 0);
+    hipStream_t s = nullptr;
+    std::vector<int> outX((size_t)n * K, 0), outS((size_t)K, 0), act((size_t)K);
+    for (int c = 0; c < K; c++) act[(size_t)c] = c;
+    std::vector<int> hu, pu, pb, hx, hc((size_t)md + 1), hd, tab;
+    std::vector<long long> hcnt;
+    std::vector<char> regular;
+    DevBuf<int> dU, dB, dS, d_coef, d_deg, gwork, dX, dR, dT;
+    DevBuf<long long> dcnt;
+    KrylovWork W;
+    SpgEvents ev;
+    i64 *st = g_wied_stats;
+    st[0] = n;
+    st[1] = K;
+    for (int t = 0; t < ntries && !act.empty(); t++) {
+        const int ka = (int)act.size(), kw = horner_kw(ka);
+        const size_t nk = (size_t)n * ka;
+        // the undecided columns, packed; a column keeps the u of its original index
+        const int *Us = U;
+        if (!U) {
+            hu.resize((size_t)n * K);
+            minpoly_vectors(n, K, seed + (uint64_t)t, F.p, hu.data(), nullptr);
+            Us = hu.data();
+        }
+        pu.resize(nk);
+        pb.resize(nk);
+        for (int r = 0; r < n; r++)
+            for (int a = 0; a < ka; a++) {
+                pu[(size_t)r * ka + a] = Us[(size_t)r * K + act[(size_t)a]];
+                pb[(size_t)r * ka + a] = B[(i64)r * ldb + act[(size_t)a]];
+            }
+        dU.ensure(nk);
+        dB.ensure(nk);
+        dX.ensure(nk);
+        dR.ensure((size_t)n * kw);
+        dS.ensure((size_t)len * ka);
+        d_coef.ensure((size_t)ka * (size_t)ldc);
+        d_deg.ensure((size_t)ka);
+        dcnt.ensure((size_t)2 * kw);
+        HIPCHK(hipMemcpyAsync(dU.p, pu.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dB.p, pb.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        int launches = krylov_run(V, F, ka, len, dU.p, ka, dB.p, ka, W, dS.p, s);
+        bm_device(F, ka, len, dS.p, ka, cls, d_coef.p, ldc, d_deg.p, gwork, s);
+        launches++;
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        hd.resize((size_t)ka);
+        HIPCHK(hipMemcpyAsync(hd.data(), d_deg.p, hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        st[2] = t + 1;
+        st[3] += len - 1;
+        st[4] += launches;
+        st[8] += (i64)(ev.ms(0, 1) * 1000.0);
+        int Lmax = 0;
+        for (int a = 0; a < ka; a++) {
+            const int L = hd[(size_t)a];
+            if (L > md) {
+                char msg[128];
+                snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d, maxdeg %d)", act[(size_t)a], L, md);
+                throw EngineError(msg);
+            }
+            Lmax = std::max(Lmax, L);
+        }
+        st[5] = std::max(st[5], (i64)Lmax);
+        // the table: column a carries q = (f - f(0)) / x, scaled by -1 / f(0) when f(0) != 0, zero-padded at the top; one more row
+        // for the check: -1 where x is expected to solve the system, 0 where it is expected to lie in the kernel
+        const int rows = Lmax; // max deg q + 1
+        tab.assign((size_t)(rows + 1) * kw, 0);
+        regular.assign((size_t)ka, 0);
+        for (int a = 0; a < ka; a++) {
+            const int L = hd[(size_t)a];
+            HIPCHK(hipMemcpy(hc.data(), d_coef.p + (size_t)a * (size_t)ldc, ((size_t)L + 1) * sizeof(int), hipMemcpyDeviceToHost));
+            const uint64_t f0 = wied_residue(hc[0], p);
+            const uint64_t scale = f0 ? (p - hinv(f0, p)) % p : 1;
+            regular[(size_t)a] = f0 != 0;
+            for (int j = 0; j < L; j++)
+                tab[(size_t)(rows - 1 - j) * kw + a] = wied_balanced(wied_residue(hc[(size_t)j + 1], p) * scale % p, p);
+            tab[(size_t)rows * kw + a] = f0 ? -1 : 0;
+        }
+        dT.ensure(tab.size());
+        HIPCHK(hipMemcpyAsync(dT.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)2 * kw * sizeof(long long), s));
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        launches = 0;
+        if (rows == 0) HIPCHK(hipMemsetAsync(dX.p, 0, nk * sizeof(int), s));
+        else launches += horner_run(V, F, ka, rows, dT.p, dB.p, ka, nullptr, 0, dX.p, ka, W, dcnt.p, s);
+        // the certificate: R <- op(A) X + r B, with the non-zero counts of X (above) and of R
+        launches += horner_run(V, F, ka, 1, dT.p + (size_t)rows * kw, dB.p, ka, dX.p, ka, dR.p, kw, W, dcnt.p + kw, s);
+        HIPCHK(hipEventRecord(ev.e[3], s));
+        hcnt.resize((size_t)2 * kw);
+        hx.resize(nk);
+        HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt.p, hcnt.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hx.data(), dX.p, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        st[3] += std::max(rows - 1, 0) + 1;
+        st[4] += launches;
+        st[9] += (i64)(ev.ms(2, 3) * 1000.0);
+        std::vector<int> left;
+        for (int a = 0; a < ka; a++) {
+            const int c = act[(size_t)a];
+            const bool rzero = hcnt[(size_t)kw + a] == 0, xzero = hcnt[(size_t)a] == 0;
+            int verdict = 0;
+            if (regular[(size_t)a] && rzero) verdict = 1;
+            else if (!regular[(size_t)a] && rzero && !xzero) verdict = 2;
+            if (!verdict) {
+                left.push_back(c);
+                continue;
+            }
+            outS[(size_t)c] = verdict;
+            st[5 + verdict]++;
+            for (int r = 0; r < n; r++) outX[(size_t)r * K + c] = hx[(size_t)r * ka + a];
+        }
+        act.swap(left);
+    }
+    for (int r = 0; r < n; r++) memcpy(X + (i64)r * ldx, outX.data() + (size_t)r * K, (size_t)K * sizeof(int));
+    memcpy(status, outS.data(), (size_t)K * sizeof(int));
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- polynomials of A applied to vectors, and Wiedemann's solve (horner.hpp; engine extension) ----
+SPASM_API int spasm_amd_poly_apply(spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const spasm_ZZp *V, i64 ldv,
+                                   spasm_ZZp *X, i64 ldx)
+{
+    return abi_call("spasm_amd_poly_apply", -1, [&] {
+        wied_stats_reset();
+        poly_apply_check(op, trans, K, deg, coef, ldc, V, ldv, X, ldx);
+        const size_t n = (size_t)op->A.n, kk = (size_t)K;
+        if (n == 0) return 0;
+        DeviceGuard g(op);
+        hipStream_t s = nullptr;
+        DevBuf<int> dV, dX;
+        dV.alloc(n * kk);
+        dX.alloc(n * kk);
+        HIPCHK(hipMemcpy2DAsync(dV.p, kk * sizeof(int), V, (size_t)ldv * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+        int products = 0;
+        const int launches = poly_apply_dev(op, trans, K, deg, coef, ldc, dV.p, K, dX.p, K, s, &products);
+        std::vector<int> out(n * kk);
+        HIPCHK(hipMemcpyAsync(out.data(), dX.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        i64 *st = g_wied_stats;
+        st[0] = (i64)n;
+        st[1] = K;
+        st[3] = products;
+        st[4] = launches;
+        for (size_t r = 0; r < n; r++) memcpy(X + (i64)r * ldx, out.data() + r * kk, kk * sizeof(int));
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_poly_apply_dev(spasm_amd_spmv *op, int trans, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, const spasm_ZZp *V, i64 ldv,
+                                       spasm_ZZp *X, i64 ldx, void *stream)
+{
+    return abi_call("spasm_amd_poly_apply_dev", -1, [&] {
+        wied_stats_reset();
+        poly_apply_check(op, trans, K, deg, coef, ldc, V, ldv, X, ldx);
+        if (op->A.n == 0) return 0;
+        DeviceGuard g(op);
+        int products = 0;
+        const int launches = poly_apply_dev(op, trans, K, deg, coef, ldc, V, ldv, X, ldx, (hipStream_t)stream, &products);
+        i64 *st = g_wied_stats;
+        st[0] = op->A.n;
+        st[1] = K;
+        st[3] = products;
+        st[4] = launches;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_wiedemann_solve(const struct spasm_csr *A, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                                        const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_wiedemann_solve", -1, [&] {
+        DeviceGuard g;
+        wied_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        wied_check(A->n, A->m, trans, K, B, ldb, X, ldx, status);
+        if (A->n == 0) { wied_empty(K, status); return 0; }
+        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_solve"));
+        if (trans) op->build_transpose();
+        wied_run(trans ? op->tr : op->fwd, op->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_spmv_wiedemann_solve(spasm_amd_spmv *op, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                                             const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_spmv_wiedemann_solve", -1, [&] {
+        wied_stats_reset();
+        if (!op) throw EngineError("NULL operator");
+        wied_check(op->A.n, op->A.m, trans, K, B, ldb, X, ldx, status);
+        if (op->A.n == 0) { wied_empty(K, status); return 0; }
+        DeviceGuard g(op);
+        if (trans) op->build_transpose();
+        wied_run(trans ? op->tr : op->fwd, op->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
+                                             const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_dcsr_wiedemann_solve", -1, [&] {
+        wied_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        wied_check(D->n, D->m, trans, K, B, ldb, X, ldx, status);
+        if (D->n == 0) { wied_empty(K, status); return 0; }
+        DeviceGuard g(D);
+        // x A = b is A^T x = b: the transpose stays on the device for the length of the call
+        std::unique_ptr<spasm_amd_dcsr> T;
+        if (trans) T.reset(dcsr_transpose(D, "transpose"));
+        SpmvView view;
+        dcsr_square_view(trans ? T.get() : D, view, nullptr);
+        wied_run(view, D->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_wiedemann_stats(i64 *out)
+{
+    if (out) memcpy(out, g_wied_stats, sizeof g_wied_stats);
 }
 
 } // extern "C"
