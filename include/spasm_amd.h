@@ -758,6 +758,13 @@ void spasm_amd_solver_dense_info(const spasm_amd_solver *S, i64 *out);
 /* Per-round records of the most recent spasm_echelonize call on this thread. */
 int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_rounds);
 
+/* The dense eliminations of the most recent spasm_echelonize call on this thread (read-only counters; all zero when the call never
+ * reached a dense finish).  out[8] = eliminations run; of the LAST one: its kind (1 = int8 matrix cores, one base-256 digit, p < 2^8;
+ * 2 = int8, two digits, p < 2^16; 3 = f64 panels, p <= 2^24 or forced; 4 = rank-1 updates, p > 2^24), rows, columns, block width
+ * (columns updated at once: the int8 block; 64 for the f64 panels; 1 for the rank-1 updates); tall-and-skinny finishes; panels of
+ * the tall panel kernel redone in place; spare.  out == NULL is ignored. */
+void spasm_amd_dense_stats(i64 *out);
+
 /* The device's field arithmetic (csrc/zp.hpp, the restatement of spasm_ZZp.c as SpaSM.jl gives it, src/SpaSM.jl:383-390) on n
  * test vectors: a, b, c are balanced residues; out receives 8 ints per vector: a*b, a*b+c, a+b, a-b, -a, a^-1 (0 for a = 0),
  * a*b through the scatter kernels' lazy product + short reduction, 64*a*b through a lazy accumulator + the same reduction.

@@ -1676,6 +1676,20 @@ def last_rounds(max_rounds=4096):
     return [buf[i].as_dict() for i in range(min(n, max_rounds))]
 
 
+DENSE_STATS = ("eliminations", "kind", "rows", "cols", "block", "tall_finishes", "panels_redone", "spare")
+DENSE_KINDS = {0: None, 1: "i8_one_digit", 2: "i8_two_digits", 3: "f64_panels", 4: "rank1_updates"}
+
+
+def dense_stats():
+    """Counters of the dense eliminations of the last echelonize call of this thread (spasm_amd_dense_stats), keyed by DENSE_STATS;
+    `kind` (of the last elimination) is one of DENSE_KINDS' names, None when the call reached no dense finish."""
+    out = (C.c_int64 * 8)()
+    _abi.lib().spasm_amd_dense_stats(out)
+    d = {k: int(v) for k, v in zip(DENSE_STATS, out)}
+    d["kind"] = DENSE_KINDS[d["kind"]]
+    return d
+
+
 # The engine's progress text goes to stderr / logcallback like libspasm's; the reference hides it
 # by redirecting the process's stderr around the ccall unless verbose (src/SpaSM.jl:838-858).
 _LOGFUNC = C.CFUNCTYPE(C.c_int, C.c_char_p)

@@ -116,6 +116,7 @@ template <typename DT, class RowSource>
 int dense_finish_tall(RowSource &src, int R, int C, i64 ldc, const int *clist, const int *row_orig, const ZpField &F, HostU &U, hipStream_t s)
 {
     TallStats ts;
+    g_dense_stats[5]++;
     const double t0 = spasm_wtime();
     const int R1 = tall_first_slab(R, C);
     ts.R1 = R1;

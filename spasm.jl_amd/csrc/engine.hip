@@ -1874,6 +1874,15 @@ void check_input(const struct spasm_csr *A, const char *who)
 
 thread_local std::vector<spasm_amd_round_stats> g_last_rounds;
 thread_local int g_multi_finish = 0; // how the last spasm_amd_echelonize_multi finished (spasm_amd_multi_last_finish)
+// the dense eliminations of the last echelonize call of this thread (spasm_amd_dense_stats): how many, then of the LAST one its
+// kind (1 int8 one digit, 2 int8 two digits, 3 f64 panels, 4 rank-1 updates), rows, columns, block width (KB; 64 for the f64
+// panels, 1 for the rank-1 updates); tall-and-skinny finishes, panels the tall panels redid in place, spare
+thread_local i64 g_dense_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+inline void dense_stats_note(int kind, int R, int C, int block)
+{
+    g_dense_stats[0]++;
+    g_dense_stats[1] = kind; g_dense_stats[2] = R; g_dense_stats[3] = C; g_dense_stats[4] = block;
+}
 
 i64 read_bytes_of(const RoundCounters &c, int m) { return 8 * (i64)c.nnz_reduced + 16 * (i64)c.segments + 4 * (i64)m; }
 
@@ -2389,6 +2398,8 @@ bool dense_eliminate_i8(DevBuf<DT> &D, int R, int C, i64 ldc, const ZpField &F, 
     HIPCHK(hipMemcpyAsync(&hst, st.p, sizeof hst, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (hst.pad) throw EngineError("dense finish: a grid barrier of the panel kernel timed out (the device is shared with another process?)");
+    dense_stats_note(ND, R, C, KB);
+    g_dense_stats[6] += redone;
     if (tall) spasm_logf("[echelonize/dense] tall panels: %lld resident rows elect, %lld follow; %d of %d panels redone in place%s\n", (long long)R_res,
                          (long long)R - (long long)R_res, redone, npanels_done,
                          redone >= 4 && 2 * redone > npanels_done ? ", the others in place from the start" : "");
@@ -2511,7 +2522,9 @@ int dense_eliminate(DevBuf<DT> &D, int R, int C, i64 ldc, const int *clist, cons
                 }
             }
             HIPCHK(hipStreamSynchronize(s)); // Lm / Upan go out of scope
+            dense_stats_note(3, R, C, DPB);
         } else {
+            dense_stats_note(4, R, C, 1);
             for (int c = 0; c < C; c++) {
                 hipLaunchKernelGGL(k_dense_find, dim3(1), dim3(1024), 0, s, c, R, D.p, (i64d)ldc, is_piv.p, pivrow_of_col.p, st.p);
                 hipLaunchKernelGGL(k_dense_scale, dim3(cdiv(rc, 256)), dim3(256), 0, s, c, R, C, F, D.p, (i64d)ldc, is_piv.p, prow.p, fcol.p, st.p);
@@ -3063,6 +3076,7 @@ struct spasm_lu *do_echelonize(const struct spasm_csr *A, struct echelonize_opts
     const double t0 = spasm_wtime();
     spasm_logf("[echelonize] Start on %d x %d matrix with %lld nnz\n", n, m, (long long)spasm_nnz(A));
     g_last_rounds.clear();
+    memset(g_dense_stats, 0, sizeof g_dense_stats);
     // Fields of echelonize_opts (reference src/SpaSM.jl:332, :339, :340, :342) this engine has no use for say so when they are set
     // away from spasm_echelonize_init_opts' values: they tune libspasm's dense strategies (rows per dense block of its FFPACK
     // calls; when its randomized low-rank mode starts and with which row weights) and the completion of L -- the dense finish
@@ -9934,6 +9948,11 @@ SPASM_API int spasm_amd_last_rounds(struct spasm_amd_round_stats *out, int max_r
     const int n = (int)g_last_rounds.size();
     for (int i = 0; i < n && i < max_rounds; i++) out[i] = g_last_rounds[(size_t)i];
     return n;
+}
+
+SPASM_API void spasm_amd_dense_stats(i64 *out)
+{
+    if (out) memcpy(out, g_dense_stats, sizeof g_dense_stats);
 }
 
 } // extern "C"

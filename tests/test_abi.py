@@ -184,3 +184,15 @@ def test_dense_shard_steps_out_of_order_are_errors_not_crashes():
     assert not lib.spasm_amd_dshard_fetch_U(None, None, None, None)
     assert not lib.spasm_amd_dshard_open(None, 0, 2) and "null plan" in _abi.last_error()
     lib.spasm_amd_dshard_close(None)
+
+
+def test_dense_stats_counters_are_bound_and_read_only(S):
+    """spasm_amd_dense_stats: eight counters of the dense eliminations of the last echelonize call of this thread; a NULL pointer
+    is ignored; reading them needs no device and changes nothing."""
+    lib = S._abi.lib()
+    assert S._abi.SIGNATURES["spasm_amd_dense_stats"] == (None, [C.POINTER(C.c_int64)])
+    lib.spasm_amd_dense_stats(None)
+    assert len(S.api.DENSE_STATS) == 8 and len(set(S.api.DENSE_STATS)) == 8
+    st = S.dense_stats()
+    assert list(st) == list(S.api.DENSE_STATS) and st == S.dense_stats()
+    assert st["kind"] in S.api.DENSE_KINDS.values() and all(isinstance(v, int) and v >= 0 for k, v in st.items() if k != "kind")
