@@ -5503,40 +5503,89 @@ struct SpmvView {
         part.alloc((size_t)nseg * 64);
         HIPCHK(hipStreamSynchronize(s)); // the host vectors go out of scope
     }
+
+    // a view of rows_ rows from device row pointers p[0 .. rows_]: they serve as starts, the lengths are their differences
+    void from_row_pointers(int rows_, int cols_, const i64d *p, const int2 *ent_, hipStream_t s)
+    {
+        rows = rows_;
+        cols = cols_;
+        start = p;
+        ent = ent_;
+        tlen.alloc((size_t)rows + 1);
+        if (rows > 0) {
+            hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(rows, 256)), dim3(256), 0, s, rows, p, tlen.p);
+            HIPCHK(hipGetLastError());
+        }
+        len = tlen.p;
+        std::vector<i64d> hp((size_t)rows + 1);
+        HIPCHK(hipMemcpyAsync(hp.data(), p, hp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        std::vector<i64> hl((size_t)rows);
+        for (int i = 0; i < rows; i++) hl[(size_t)i] = hp[(size_t)i + 1] - hp[(size_t)i];
+        bin(hl, s);
+    }
+
+    // The launches of one product with KW columns, in their order: sum(team, partial, nitems, items, segbeg, part) for each
+    // non-empty class (team and partial are std::integral_constants: the TEAM and PARTIAL of SPMV_TEAM_SUM), then
+    // combine(nlong, rows, off, part) after the segments of the long rows.  Returns the number of launches.
+    template <int KW, class Sum, class Combine> int for_classes(Sum &&sum, Combine &&combine) const
+    {
+        typedef std::integral_constant<int, 64> wave;
+        int launches = 0;
+        if (nshort > 0) {
+            sum(std::integral_constant<int, spmv_short_team(KW)>(), std::false_type(), nshort, short_all ? nullptr : short_rows.p, nullptr, nullptr);
+            launches++;
+        }
+        if (nmid > 0) {
+            sum(wave(), std::false_type(), nmid, mid_rows.p, nullptr, nullptr);
+            launches++;
+        }
+        if (nlong > 0) {
+            sum(wave(), std::true_type(), nseg, seg_row.p, seg_beg.p, part.p);
+            combine(nlong, long_rows.p, long_off.p, part.p);
+            launches += 2;
+        }
+        return launches;
+    }
 };
 
+// the width KW of a chunk of k >= 1 columns: the next power of two
+int spmv_kw(int k)
+{
+    int kw = 1;
+    while (kw < k) kw <<= 1;
+    return kw;
+}
+
+// f(std::integral_constant<int, KW>) for kw = KW in 1, 2, 4, .., 64
+template <class Fn> auto dispatch_kw(int kw, Fn &&f)
+{
+    switch (kw) {
+    case 1: return f(std::integral_constant<int, 1>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 4: return f(std::integral_constant<int, 4>());
+    case 8: return f(std::integral_constant<int, 8>());
+    case 16: return f(std::integral_constant<int, 16>());
+    case 32: return f(std::integral_constant<int, 32>());
+    default: return f(std::integral_constant<int, 64>());
+    }
+}
+
+// Y <- A X + Y: one team per work item, 256 lanes a workgroup, no grid cap
 template <bool SMALL, int KW>
 void spmv_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, i64 ldx, int *Y, i64 ldy, hipStream_t s)
 {
-    constexpr int TS = spmv_short_team(KW);
     const int hp = (int)F.halfp, mhp = (int)F.mhalfp;
-    if (V.nshort > 0)
-        hipLaunchKernelGGL((k_spmv<SMALL, KW, TS, false>), dim3(cdiv((i64)V.nshort * TS, 256)), dim3(256), 0, s, V.nshort,
-                           V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, nullptr);
-    if (V.nmid > 0)
-        hipLaunchKernelGGL((k_spmv<SMALL, KW, 64, false>), dim3(cdiv((i64)V.nmid * 64, 256)), dim3(256), 0, s, V.nmid, V.mid_rows.p, nullptr, V.start,
-                           V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, nullptr);
-    if (V.nlong > 0) {
-        hipLaunchKernelGGL((k_spmv<SMALL, KW, 64, true>), dim3(cdiv((i64)V.nseg * 64, 256)), dim3(256), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p, V.start,
-                           V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, V.part.p);
-        hipLaunchKernelGGL(k_spmv_combine, dim3(cdiv((i64)V.nlong * KW, 256)), dim3(256), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p, KW, kc,
-                           F, Y, (i64d)ldy);
-    }
+    V.for_classes<KW>(
+        [&](auto team, auto partial, int nitems, const int *items, const int *segbeg, int *part) {
+            constexpr int TEAM = decltype(team)::value;
+            hipLaunchKernelGGL((k_spmv<SMALL, KW, TEAM, decltype(partial)::value>), dim3(cdiv((i64)nitems * TEAM, 256)), dim3(256), 0, s, nitems, items,
+                               segbeg, V.start, V.len, V.ent, F, hp, mhp, kc, X, (i64d)ldx, Y, (i64d)ldy, part);
+        },
+        [&](int nlong, const int *rows, const int *off, const int *part) {
+            hipLaunchKernelGGL(k_spmv_combine, dim3(cdiv((i64)nlong * KW, 256)), dim3(256), 0, s, nlong, rows, off, part, KW, kc, F, Y, (i64d)ldy);
+        });
     HIPCHK(hipGetLastError());
-}
-
-template <bool SMALL>
-void spmv_chunk(const SpmvView &V, const ZpField &F, int kw, int kc, const int *X, i64 ldx, int *Y, i64 ldy, hipStream_t s)
-{
-    switch (kw) {
-    case 1: spmv_launch<SMALL, 1>(V, F, kc, X, ldx, Y, ldy, s); break;
-    case 2: spmv_launch<SMALL, 2>(V, F, kc, X, ldx, Y, ldy, s); break;
-    case 4: spmv_launch<SMALL, 4>(V, F, kc, X, ldx, Y, ldy, s); break;
-    case 8: spmv_launch<SMALL, 8>(V, F, kc, X, ldx, Y, ldy, s); break;
-    case 16: spmv_launch<SMALL, 16>(V, F, kc, X, ldx, Y, ldy, s); break;
-    case 32: spmv_launch<SMALL, 32>(V, F, kc, X, ldx, Y, ldy, s); break;
-    default: spmv_launch<SMALL, 64>(V, F, kc, X, ldx, Y, ldy, s); break;
-    }
 }
 
 // the ping-pong buffers and the projection sums of one Krylov sequence (krylov.hpp; the section at the end of this file)
@@ -5572,22 +5621,7 @@ struct spasm_amd_spmv {
         hipStream_t s = nullptr;
         Scanner scan;
         device_transpose(A, A.n, nullptr, nullptr, 0, scan, s, T);
-        tr.rows = A.m;
-        tr.cols = A.n;
-        tr.start = T.Tp.p;
-        tr.tlen.alloc((size_t)A.m + 1);
-        if (A.m > 0) {
-            hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(A.m, 256)), dim3(256), 0, s, A.m, T.Tp.p, tr.tlen.p);
-            HIPCHK(hipGetLastError());
-        }
-        tr.len = tr.tlen.p;
-        tr.ent = T.Tent.p;
-        std::vector<i64d> tp((size_t)A.m + 1);
-        HIPCHK(hipMemcpyAsync(tp.data(), T.Tp.p, tp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        std::vector<i64> hl((size_t)A.m);
-        for (int i = 0; i < A.m; i++) hl[(size_t)i] = tp[(size_t)i + 1] - tp[(size_t)i];
-        tr.bin(hl, s);
+        tr.from_row_pointers(A.m, A.n, T.Tp.p, T.Tent.p, s);
         have_t = true;
     }
 
@@ -5597,12 +5631,11 @@ struct spasm_amd_spmv {
         if (trans) build_transpose();
         const SpmvView &V = trans ? tr : fwd;
         for (int k0 = 0; k0 < k; k0 += 64) {
-            const int rem = k - k0;
-            int kw = 1;
-            while (kw < rem && kw < 64) kw <<= 1;
-            const int kc = rem < kw ? rem : kw;
-            if (F.small) spmv_chunk<true>(V, F, kw, kc, X + k0, ldx, Y + k0, ldy, s);
-            else spmv_chunk<false>(V, F, kw, kc, X + k0, ldx, Y + k0, ldy, s);
+            const int kc = std::min(k - k0, 64);
+            dispatch_kw(spmv_kw(kc), [&](auto KW) {
+                if (F.small) spmv_launch<true, KW()>(V, F, kc, X + k0, ldx, Y + k0, ldy, s);
+                else spmv_launch<false, KW()>(V, F, kc, X + k0, ldx, Y + k0, ldy, s);
+            });
         }
     }
 
@@ -6477,31 +6510,16 @@ struct spasm_amd_trsolve {
         HIPCHK(hipGetLastError());
     }
 
-    template <bool SMALL>
-    void run_kw(int kw, int kc, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
-    {
-        switch (kw) {
-        case 1: run<SMALL, 1>(kc, B, ldb, X, ldx, ok, s); break;
-        case 2: run<SMALL, 2>(kc, B, ldb, X, ldx, ok, s); break;
-        case 4: run<SMALL, 4>(kc, B, ldb, X, ldx, ok, s); break;
-        case 8: run<SMALL, 8>(kc, B, ldb, X, ldx, ok, s); break;
-        case 16: run<SMALL, 16>(kc, B, ldb, X, ldx, ok, s); break;
-        case 32: run<SMALL, 32>(kc, B, ldb, X, ldx, ok, s); break;
-        default: run<SMALL, 64>(kc, B, ldb, X, ldx, ok, s); break;
-        }
-    }
-
     // X, residual in B and ok for k right-hand sides on device arrays, enqueued on s (k > 0)
     void apply_dev(int k, int *B, i64 ldb, int *X, i64 ldx, unsigned char *ok, hipStream_t s)
     {
         HIPCHK(hipMemsetAsync(ok, 1, (size_t)k, s));
         for (int k0 = 0; k0 < k; k0 += 64) {
-            const int rem = k - k0;
-            int kw = 1;
-            while (kw < rem && kw < 64) kw <<= 1;
-            const int kc = rem < kw ? rem : kw;
-            if (F.small) run_kw<true>(kw, kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
-            else run_kw<false>(kw, kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
+            const int kc = std::min(k - k0, 64);
+            dispatch_kw(spmv_kw(kc), [&](auto KW) {
+                if (F.small) run<true, KW()>(kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
+                else run<false, KW()>(kc, B + k0, ldb, X + k0, ldx, ok + k0, s);
+            });
         }
     }
 
@@ -10786,43 +10804,52 @@ thread_local i64 g_minpoly_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 void minpoly_stats_reset() { memset(g_minpoly_stats, 0, sizeof g_minpoly_stats); }
 
+// the grid of a step kernel: KRY_BS lanes a workgroup, at most cap workgroups (its teams stride)
+dim3 step_grid(i64 lanes, int cap) { return dim3((unsigned)std::max(1, std::min(cdiv(lanes, KRY_BS), cap))); }
+
+int step_grid_cap()
+{
+    int dev = 0, cu = 256;
+    HIPCHK(hipGetDevice(&dev));
+    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    return cu * KRY_WG_PER_CU;
+}
+
+// Y <- A X with the epilogue epi on every entry of Y (spmv_step.hpp); Y is not read.  Returns the launches.
+template <bool SMALL, int KW, class Epi>
+int spmv_step_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, i64d ldx, int *Y, i64d ldy, const Epi &epi, int cap, hipStream_t s)
+{
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp;
+    const int launches = V.for_classes<KW>(
+        [&](auto team, auto partial, int nitems, const int *items, const int *segbeg, int *part) {
+            constexpr int TEAM = decltype(team)::value;
+            hipLaunchKernelGGL((k_spmv_step<SMALL, KW, TEAM, decltype(partial)::value, Epi>), step_grid((i64)nitems * TEAM, cap), dim3(KRY_BS), 0, s, nitems,
+                               items, segbeg, V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, part, epi);
+        },
+        [&](int nlong, const int *rows, const int *off, const int *part) {
+            hipLaunchKernelGGL((k_spmv_step_combine<KW, Epi>), step_grid((i64)nlong * KW, cap), dim3(KRY_BS), 0, s, nlong, rows, off, part, kc, F, hp, mhp,
+                               Y, ldy, epi);
+        });
+    HIPCHK(hipGetLastError());
+    return launches;
+}
+
 template <bool SMALL, int KW>
 int krylov_launch(const SpmvView &V, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
                   hipStream_t s)
 {
-    constexpr int TS = spmv_short_team(KW);
     const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
-    auto grid = [&](i64 lanes) { return dim3((unsigned)std::max(1, std::min(cdiv(lanes, KRY_BS), cap))); };
     int launches = 0;
     HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
     if (n > 0) {
-        hipLaunchKernelGGL((k_krylov_dot<KW>), grid((i64)n * KW), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+        hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)n * KW, cap), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
         launches++;
     }
     const int *X = X0;
     i64d ldx = (i64d)ldx0;
     int *Y = W.w0.p;
     for (i64 i = 1; i < len && n > 0; i++) {
-        long long *ap = W.acc.p + i * KW;
-        if (V.nshort > 0) {
-            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, TS, false>), grid((i64)V.nshort * TS), dim3(KRY_BS), 0, s, V.nshort,
-                               V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, nullptr, U,
-                               (i64d)ldu, ap);
-            launches++;
-        }
-        if (V.nmid > 0) {
-            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, 64, false>), grid((i64)V.nmid * 64), dim3(KRY_BS), 0, s, V.nmid, V.mid_rows.p, nullptr, V.start,
-                               V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, nullptr, U, (i64d)ldu, ap);
-            launches++;
-        }
-        if (V.nlong > 0) {
-            hipLaunchKernelGGL((k_krylov_step<SMALL, KW, 64, true>), grid((i64)V.nseg * 64), dim3(KRY_BS), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p, V.start,
-                               V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, (i64d)KW, V.part.p, U, (i64d)ldu, ap);
-            hipLaunchKernelGGL((k_krylov_combine<KW>), grid((i64)V.nlong * KW), dim3(KRY_BS), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p, kc, F,
-                               hp, mhp, Y, (i64d)KW, U, (i64d)ldu, ap);
-            launches += 2;
-        }
-        HIPCHK(hipGetLastError());
+        launches += spmv_step_launch<SMALL, KW>(V, F, kc, X, ldx, Y, (i64d)KW, KrylovEpi{U, (i64d)ldu, W.acc.p + i * KW}, cap, s);
         X = Y;
         ldx = KW;
         Y = Y == W.w0.p ? W.w1.p : W.w0.p;
@@ -10833,38 +10860,21 @@ int krylov_launch(const SpmvView &V, const ZpField &F, int kc, i64 len, const in
     return launches + 1;
 }
 
-template <bool SMALL>
-int krylov_chunk(int kw, const SpmvView &V, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
-                 hipStream_t s)
-{
-    switch (kw) {
-    case 1: return krylov_launch<SMALL, 1>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    case 2: return krylov_launch<SMALL, 2>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    case 4: return krylov_launch<SMALL, 4>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    case 8: return krylov_launch<SMALL, 8>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    case 16: return krylov_launch<SMALL, 16>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    case 32: return krylov_launch<SMALL, 32>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    default: return krylov_launch<SMALL, 64>(V, F, kc, len, U, ldu, X0, ldx0, W, S, cap, s);
-    }
-}
-
 // S[i * K + c] = sum_r U[r, c] * (A^i V)[r, c], 0 <= i < len, on device arrays, enqueued on s; no host synchronization.  V is the
 // view of a square matrix; 1 <= K <= 64, len >= 1.  Returns the launches.
 int krylov_run(const SpmvView &V, const ZpField &F, int K, i64 len, const int *U, i64 ldu, const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
 {
-    int kw = 1;
-    while (kw < K) kw <<= 1;
-    int dev = 0, cu = 256;
-    HIPCHK(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    const int kw = spmv_kw(K), cap = step_grid_cap();
     const size_t words = (size_t)V.rows * kw;
     if (len > 1) {
         W.w0.ensure(words);
         if (len > 2) W.w1.ensure(words);
     }
     W.acc.ensure((size_t)len * kw);
-    const int cap = cu * KRY_WG_PER_CU;
-    return F.small ? krylov_chunk<true>(kw, V, F, K, len, U, ldu, X, ldx, W, S, cap, s) : krylov_chunk<false>(kw, V, F, K, len, U, ldu, X, ldx, W, S, cap, s);
+    return dispatch_kw(kw, [&](auto KW) {
+        return F.small ? krylov_launch<true, KW()>(V, F, K, len, U, ldu, X, ldx, W, S, cap, s)
+                       : krylov_launch<false, KW()>(V, F, K, len, U, ldu, X, ldx, W, S, cap, s);
+    });
 }
 
 void krylov_check(const spasm_amd_spmv *op, int trans, int K, i64 len, const void *U, i64 ldu, const void *V, i64 ldv, const void *S)
@@ -11177,22 +11187,7 @@ void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int 
 }
 
 // a view of the resident entries of a square matrix (n > 0): the row pointers serve as starts, the lengths are their differences
-void dcsr_square_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s)
-{
-    view.rows = view.cols = D->n;
-    view.start = D->p.p;
-    view.ent = D->ent.p;
-    view.tlen.alloc((size_t)D->n + 1);
-    hipLaunchKernelGGL(k_spmv_len_from_ptr, dim3(cdiv(D->n, 256)), dim3(256), 0, s, D->n, D->p.p, view.tlen.p);
-    HIPCHK(hipGetLastError());
-    view.len = view.tlen.p;
-    std::vector<i64d> hp((size_t)D->n + 1);
-    HIPCHK(hipMemcpyAsync(hp.data(), D->p.p, hp.size() * sizeof(i64d), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::vector<i64> hl((size_t)D->n);
-    for (int i = 0; i < D->n; i++) hl[(size_t)i] = hp[(size_t)i + 1] - hp[(size_t)i];
-    view.bin(hl, s);
-}
+void dcsr_square_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->n, D->p.p, D->ent.p, s); }
 
 void minpoly_check_out(const spasm_ZZp *U, const spasm_ZZp *X, const spasm_ZZp *coef, const int *deg)
 {
@@ -11368,9 +11363,7 @@ template <bool SMALL, int KW>
 int horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout, i64 ldyo,
                   KrylovWork &W, long long *cnt, int cap, hipStream_t s)
 {
-    constexpr int TS = spmv_short_team(KW);
     const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
-    auto grid = [&](i64 lanes) { return dim3((unsigned)std::max(1, std::min(cdiv(lanes, KRY_BS), cap))); };
     int launches = 0;
     const int *X = X0;
     i64d ldx = (i64d)ldx0;
@@ -11381,27 +11374,10 @@ int horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const i
         long long *cp = last ? cnt : nullptr;
         const int *Ti = T + (size_t)i * KW;
         if (!X) {
-            hipLaunchKernelGGL((k_horner_scale<KW>), grid((i64)n * KW), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, Ti, B, (i64d)ldb, Y, ldy, cp);
+            hipLaunchKernelGGL((k_horner_scale<KW>), step_grid((i64)n * KW, cap), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, Ti, B, (i64d)ldb, Y, ldy, cp);
             launches++;
         } else {
-            if (V.nshort > 0) {
-                hipLaunchKernelGGL((k_horner_step<SMALL, KW, TS, false>), grid((i64)V.nshort * TS), dim3(KRY_BS), 0, s, V.nshort,
-                                   V.short_all ? nullptr : V.short_rows.p, nullptr, V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, nullptr, Ti, B,
-                                   (i64d)ldb, cp);
-                launches++;
-            }
-            if (V.nmid > 0) {
-                hipLaunchKernelGGL((k_horner_step<SMALL, KW, 64, false>), grid((i64)V.nmid * 64), dim3(KRY_BS), 0, s, V.nmid, V.mid_rows.p, nullptr,
-                                   V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, nullptr, Ti, B, (i64d)ldb, cp);
-                launches++;
-            }
-            if (V.nlong > 0) {
-                hipLaunchKernelGGL((k_horner_step<SMALL, KW, 64, true>), grid((i64)V.nseg * 64), dim3(KRY_BS), 0, s, V.nseg, V.seg_row.p, V.seg_beg.p,
-                                   V.start, V.len, V.ent, F, hp, mhp, kc, X, ldx, Y, ldy, V.part.p, Ti, B, (i64d)ldb, nullptr);
-                hipLaunchKernelGGL((k_horner_combine<KW>), grid((i64)V.nlong * KW), dim3(KRY_BS), 0, s, V.nlong, V.long_rows.p, V.long_off.p, V.part.p,
-                                   kc, F, hp, mhp, Y, ldy, Ti, B, (i64d)ldb, cp);
-                launches += 2;
-            }
+            launches += spmv_step_launch<SMALL, KW>(V, F, kc, X, ldx, Y, ldy, HornerEpi{Ti, B, (i64d)ldb, cp}, cap, s);
         }
         HIPCHK(hipGetLastError());
         X = Y;
@@ -11410,45 +11386,21 @@ int horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const i
     return launches;
 }
 
-template <bool SMALL>
-int horner_chunk(int kw, const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout,
-                 i64 ldyo, KrylovWork &W, long long *cnt, int cap, hipStream_t s)
-{
-    switch (kw) {
-    case 1: return horner_launch<SMALL, 1>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    case 2: return horner_launch<SMALL, 2>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    case 4: return horner_launch<SMALL, 4>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    case 8: return horner_launch<SMALL, 8>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    case 16: return horner_launch<SMALL, 16>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    case 32: return horner_launch<SMALL, 32>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    default: return horner_launch<SMALL, 64>(V, F, kc, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
-    }
-}
-
-int horner_kw(int K)
-{
-    int kw = 1;
-    while (kw < K) kw <<= 1;
-    return kw;
-}
-
-// rows >= 1 Horner steps on device arrays, enqueued on s; no host synchronization.  T is the device table, rows x horner_kw(K)
+// rows >= 1 Horner steps on device arrays, enqueued on s; no host synchronization.  T is the device table, rows x spmv_kw(K)
 // canonical residues.  Returns the launches.
 int horner_run(const SpmvView &V, const ZpField &F, int K, int rows, const int *T, const int *B, i64 ldb, const int *X0, i64 ldx0, int *Yout, i64 ldyo,
                KrylovWork &W, long long *cnt, hipStream_t s)
 {
-    const int kw = horner_kw(K);
-    int dev = 0, cu = 256;
-    HIPCHK(hipGetDevice(&dev));
-    if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cu <= 0) cu = 256;
+    const int kw = spmv_kw(K), cap = step_grid_cap();
     const size_t words = (size_t)V.rows * kw;
     if (rows > 1) {
         W.w0.ensure(words);
         if (rows > 2) W.w1.ensure(words);
     }
-    const int cap = cu * KRY_WG_PER_CU;
-    return F.small ? horner_chunk<true>(kw, V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s)
-                   : horner_chunk<false>(kw, V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    return dispatch_kw(kw, [&](auto KW) {
+        return F.small ? horner_launch<true, KW()>(V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s)
+                       : horner_launch<false, KW()>(V, F, K, rows, T, B, ldb, X0, ldx0, Yout, ldyo, W, cnt, cap, s);
+    });
 }
 
 inline uint64_t wied_residue(int x, uint64_t p)
@@ -11465,7 +11417,7 @@ int poly_table(const ZpField &F, int K, const int *deg, const spasm_ZZp *coef, i
 {
     int D = -1;
     for (int c = 0; c < K; c++) D = std::max(D, deg[c]);
-    const int kw = horner_kw(K);
+    const int kw = spmv_kw(K);
     tab.assign((size_t)(D + 1) * kw, 0);
     const uint64_t p = (uint64_t)F.p;
     for (int c = 0; c < K; c++)
@@ -11577,7 +11529,7 @@ void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i6
     st[0] = n;
     st[1] = K;
     for (int t = 0; t < ntries && !act.empty(); t++) {
-        const int ka = (int)act.size(), kw = horner_kw(ka);
+        const int ka = (int)act.size(), kw = spmv_kw(ka);
         const size_t nk = (size_t)n * ka;
         // the undecided columns, packed; a column keeps the u of its original index
         const int *Us = U;

@@ -2,20 +2,14 @@
 // resident exact product (spmv.hpp), and their shortest linear recurrences by Berlekamp-Massey (spasm_amd_krylov_sequence,
 // spasm_amd_berlekamp_massey, spasm_amd_minpoly).  No elimination, no fill-in: memory is O(nnz + n * K).
 //
-// The Krylov step.  k_krylov_step is k_spmv on the same row classes and entry streams (SpmvView: short, medium, long in segments of
-// SPMV_SEG) with two differences.  Y is written and never read: the step computes Y <- A X, so there is no memset and no
-// read-modify-write.  And the lane that owns y[row, v] forms zp_mul(u[row, v], y), a canonical residue, which is summed into
-// acc[v] of this step: first over the rows the lane's team walks (the grid is capped at a few workgroups per CU and a team strides
-// over the work items), then over the lanes of the wave that hold column v (shuffles), then over the waves of the workgroup (LDS),
-// and then ONE 64-bit integer add per (workgroup, column) goes to global memory (a vector atomic; skipped when the sum is 0).
-// For the long rows y is complete only in the combine kernel, so the projection is taken there.
+// The Krylov step is k_spmv_step / k_spmv_step_combine of spmv_step.hpp with KrylovEpi: the lane that owns y[row, v] stores y and
+// contributes zp_mul(u[row, v], y), a canonical residue, to acc[v] of this step (krylov_project; for the long rows in the combine).
 //
 // Bound of the projection: a term is a canonical residue, |term| <= halfp < 2^31, and there are at most 2^31 rows, so every
-// partial sum and the total stay below 2^31 * halfp < 2^62 in an i64.  The sum is an integer: it does not depend on the order in
-// which lanes, waves, workgroups and atomics add, so two runs give the same bits.  k_krylov_finish brings it to the balanced
-// residue with zp_reduce, whose float quotient is within 1 because |sum| / p <= 2^30.  The bounds of the product itself are those
-// of spmv.hpp (a lane takes at most SPMV_SEG lazy terms).  Unreduced entries of U and of the first X (the caller's V) are reduced
-// where they are read, as k_spmv does with X.
+// partial sum and the total stay below 2^31 * halfp < 2^62 in an i64.  k_krylov_finish brings the sum to the balanced residue with
+// zp_reduce, whose float quotient is within 1 because |sum| / p <= 2^30.  The bounds of the product itself are those of spmv.hpp
+// (a lane takes at most SPMV_SEG lazy terms).  Unreduced entries of U and of the first X (the caller's V) are reduced where they
+// are read (zp_residue).
 //
 // Berlekamp-Massey.  One workgroup of BM_BS lanes per sequence.  The connection polynomial C and the previous one B are two arrays
 // of dmax + 1 words (dmax = len: L never exceeds the number of terms read), in LDS when 2 * (dmax + 1) <= BM_LDS_WORDS (158 KiB of
@@ -38,38 +32,11 @@
 // f(x) = x^L * C(1 / x), f[k] = C[L - k]: the zero sequence gives f = 1, the sequence 1, 0, 0, 0 gives f = x.
 #pragma once
 #include <hip/hip_runtime.h>
-#include <type_traits>
 #include "zp.hpp"
-#include "spmv.hpp"
+#include "spmv_step.hpp"
 
-constexpr int KRY_BS = 256;                  // lanes of a workgroup of the Krylov kernels (KW divides it)
-constexpr int KRY_WG_PER_CU = 8;             // the grid of a step is capped at this many workgroups per CU
 constexpr int BM_BS = 512;                   // lanes of a Berlekamp-Massey workgroup
 constexpr int BM_LDS_WORDS = 158 * 1024 / 4; // words C and B may take in LDS: 2 * (dmax + 1) <= 40448, dmax <= 20223
-
-// The workgroup's sum of t over the lanes of each column (the column of a lane is threadIdx.x % KW, KW a power of two that divides
-// 64) is added to accp[column].  Every lane of the workgroup calls it, with t = 0 where it owns nothing.  |t| < 2^62 (above).
-template <int KW> __device__ __forceinline__ void krylov_project(long long t, long long *accp)
-{
-    constexpr int NW = KRY_BS / 64;
-    __shared__ long long s_red[NW * KW];
-#pragma unroll
-    for (int o = KW; o < 64; o <<= 1) t += __shfl_xor(t, o, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane < KW) s_red[wave * KW + lane] = t;
-    __syncthreads();
-    if (threadIdx.x < KW) {
-        long long s = 0;
-#pragma unroll
-        for (int w = 0; w < NW; w++) s += s_red[w * KW + threadIdx.x];
-        if (s != 0) atomicAdd((unsigned long long *)(accp + threadIdx.x), (unsigned long long)s);
-    }
-}
-
-__device__ __forceinline__ int krylov_residue(const ZpField &F, int hp, int mhp, int x)
-{
-    return (x < mhp || x > hp) ? zp_reduce(F, (int64_t)x) : x;
-}
 
 // s_0: accp[v] += sum_r U[r, v] * X[r, v]; one lane per (row, column), striding over the rows
 template <int KW>
@@ -81,88 +48,24 @@ __global__ __launch_bounds__(KRY_BS) void k_krylov_dot(int n, int kc, ZpField F,
     long long t = 0;
     if (v < kc)
         for (i64d r = (i64d)blockIdx.x * RPB + threadIdx.x / KW; r < n; r += (i64d)gridDim.x * RPB)
-            t += zp_mul(F, krylov_residue(F, hp, mhp, U[r * ldu + v]), krylov_residue(F, hp, mhp, X[r * ldx + v]));
+            t += zp_mul(F, zp_residue(F, hp, mhp, U[r * ldu + v]), zp_residue(F, hp, mhp, X[r * ldx + v]));
     krylov_project<KW>(t, accp);
 }
 
-// One team of TEAM lanes per work item, as in k_spmv; a team strides over the items of its class.  Not PARTIAL: Y[row, v] <- the
-// row's sum (Y is not read) and accp[v] += U[row, v] * Y[row, v].  PARTIAL: part[it * KW + v] <- the segment's sum, no projection.
-template <bool SMALL, int KW, int TEAM, bool PARTIAL>
-__global__ __launch_bounds__(KRY_BS) void k_krylov_step(int nitems, const int *__restrict__ items, const int *__restrict__ segbeg,
-                                                        const i64d *__restrict__ start, const int *__restrict__ len, const int2 *__restrict__ ent,
-                                                        ZpField F, int hp, int mhp, int kc, const int *__restrict__ X, i64d ldx, int *__restrict__ Y,
-                                                        i64d ldy, int *__restrict__ part, const int *__restrict__ U, i64d ldu,
-                                                        long long *__restrict__ accp)
-{
-    static_assert(TEAM % KW == 0 && 64 % TEAM == 0, "team shape");
-    constexpr int E = TEAM / KW, TPB = KRY_BS / TEAM;
-    typedef typename ZpAcc<SMALL>::type acc_t;
-    typedef typename std::conditional<SMALL, int, long long>::type sum_t;
-    const int tl = threadIdx.x % TEAM;
-    const int v = tl % KW, e = tl / KW;
-    const bool vok = v < kc;
-    long long t = 0;
-    // whole teams leave the loop together: the shuffles stay inside a team
-    for (i64d it = (i64d)blockIdx.x * TPB + threadIdx.x / TEAM; it < nitems; it += (i64d)gridDim.x * TPB) {
-        const int row = items ? items[it] : (int)it;
-        const i64d st = start[row];
-        int lo = 0, hi = len[row];
-        if (PARTIAL) {
-            lo = segbeg[it];
-            hi = min(hi, lo + SPMV_SEG);
-        }
-        acc_t acc = 0;
-        for (int k0 = lo + e; k0 < hi; k0 += SPMV_UNROLL * E) {
-            int2 a[SPMV_UNROLL];
-#pragma unroll
-            for (int u = 0; u < SPMV_UNROLL; u++) {
-                const int k = k0 + u * E;
-                a[u] = k < hi ? ent[st + k] : make_int2(0, 0);
-            }
-            int xv[SPMV_UNROLL];
-#pragma unroll
-            for (int u = 0; u < SPMV_UNROLL; u++) xv[u] = (vok && k0 + u * E < hi) ? X[(i64d)a[u].x * ldx + v] : 0;
-#pragma unroll
-            for (int u = 0; u < SPMV_UNROLL; u++) acc += ZpAcc<SMALL>::mul_lazy(F, a[u].y, krylov_residue(F, hp, mhp, xv[u]));
-        }
-        sum_t r;
-        if (SMALL) r = (sum_t)zp_reduce(F, (int64_t)acc);
-        else r = (sum_t)acc;
-#pragma unroll
-        for (int o = KW; o < TEAM; o <<= 1) r += __shfl_xor(r, o, TEAM);
-        if (e == 0 && vok) {
-            const int y = zp_reduce(F, (int64_t)r);
-            if (PARTIAL) {
-                part[it * KW + v] = y;
-            } else {
-                Y[(i64d)row * ldy + v] = y;
-                t += zp_mul(F, krylov_residue(F, hp, mhp, U[(i64d)row * ldu + v]), y);
-            }
-        }
+// the epilogue of a Krylov step (spmv_step.hpp): Y[row, v] <- y and the term U[row, v] * y of acc[v]; always projected
+struct KrylovEpi {
+    const int *U;
+    i64d ldu;
+    long long *acc;
+    __device__ int coef(int) const { return 0; }
+    __device__ long long own(const ZpField &F, int hp, int mhp, int, int row, int v, int y, int *yp) const
+    {
+        *yp = y;
+        return zp_mul(F, zp_residue(F, hp, mhp, U[(i64d)row * ldu + v]), y);
     }
-    if (!PARTIAL) krylov_project<KW>(t, accp);
-}
-
-// the long rows: row rows[l] owns the segments off[l] .. off[l+1]-1; one lane per (row, column); y is complete here, so is u * y
-template <int KW>
-__global__ __launch_bounds__(KRY_BS) void k_krylov_combine(int nlong, const int *__restrict__ rows, const int *__restrict__ off,
-                                                           const int *__restrict__ part, int kc, ZpField F, int hp, int mhp, int *__restrict__ Y,
-                                                           i64d ldy, const int *__restrict__ U, i64d ldu, long long *__restrict__ accp)
-{
-    constexpr int RPB = KRY_BS / KW;
-    const int v = threadIdx.x % KW;
-    long long t = 0;
-    if (v < kc)
-        for (i64d l = (i64d)blockIdx.x * RPB + threadIdx.x / KW; l < nlong; l += (i64d)gridDim.x * RPB) {
-            int64_t s = 0; // |s| <= (2^31 / SPMV_SEG) * 2^31 < 2^48: exact
-            for (int it = off[l]; it < off[l + 1]; it++) s += part[(i64d)it * KW + v];
-            const int row = rows[l];
-            const int y = zp_reduce(F, s);
-            Y[(i64d)row * ldy + v] = y;
-            t += zp_mul(F, krylov_residue(F, hp, mhp, U[(i64d)row * ldu + v]), y);
-        }
-    krylov_project<KW>(t, accp);
-}
+    __device__ bool projects() const { return true; }
+    __device__ long long *sums() const { return acc; }
+};
 
 // S[i * k + c] <- the balanced residue of acc[i * kw + c]
 __global__ void k_krylov_finish(i64d total, int k, int kw, ZpField F, const long long *__restrict__ acc, int *__restrict__ S)
@@ -202,7 +105,7 @@ __global__ __launch_bounds__(BM_BS) void k_berlekamp_massey(BmArgs a)
     for (int i = 0; i < len; i++) {
         // ---- discrepancy
         acc_t acc = 0;
-        for (int j = tid; j <= L; j += BM_BS) acc += ZpAcc<SMALL>::mul_lazy(F, P[j], krylov_residue(F, hp, mhp, s[(i64d)(i - j) * a.lds]));
+        for (int j = tid; j <= L; j += BM_BS) acc += ZpAcc<SMALL>::mul_lazy(F, P[j], zp_residue(F, hp, mhp, s[(i64d)(i - j) * a.lds]));
         long long r;
         if (SMALL) r = (long long)zp_reduce(F, (int64_t)acc);
         else r = (long long)acc;

@@ -25,59 +25,73 @@ constexpr int SPMV_UNROLL = 4;    // entries (and gathers) in flight per lane
 
 constexpr int spmv_short_team(int kw) { return kw * 8 < 64 ? kw * 8 : 64; }
 
-// One team of TEAM lanes per work item.  Work item it is row items[it] (items == nullptr: row it).  PARTIAL: the item is the
-// segment [segbeg[it], segbeg[it] + SPMV_SEG) of that row and its sum goes to part[it * KW + v]; otherwise the row is taken
-// whole and Y[row * ldy + v] <- sum + Y[row * ldy + v].  Columns v >= kc of the KW-wide chunk are idle.
+// The place of a lane in its team of TEAM lanes: it takes the entries e, e + E, .. (E = TEAM / KW) of the team's row and column v
+// of the KW-wide chunk; columns v >= kc are idle.
+template <int KW, int TEAM> struct SpmvLane {
+    static_assert(TEAM % KW == 0 && 64 % TEAM == 0, "team shape");
+    int v, e;
+    bool vok;
+    __device__ __forceinline__ SpmvLane(int kc) : v(threadIdx.x % TEAM % KW), e(threadIdx.x % TEAM / KW), vok(v < kc) {}
+};
+
+template <bool SMALL> using spmv_sum_t = typename std::conditional<SMALL, int, long long>::type;
+
+// The row sum of one work item, the ONE gather loop of the resident product: k_spmv below and the step kernels of spmv_step.hpp
+// (Krylov, Horner) are shells around it, and the accumulator bounds above are those of this loop.  Work item it is row items[it]
+// (items == nullptr: row it), taken whole, or with PARTIAL its segment [segbeg[it], segbeg[it] + SPMV_SEG).  SPMV_TEAM_SUM(row, r, it)
+// declares row and r in the scope of the kernel that names it: r is the team's sum for the lane's column, congruent to
+// (A X)[row, v] and inside the domain of zp_reduce, not yet reduced; every lane of the team gets it.  A whole team comes here or
+// none does: the shuffles stay inside a team.  It reads the kernel's own SMALL, KW, TEAM, PARTIAL, its view arguments (items,
+// segbeg, start, len, ent), F, hp, mhp, X, ldx and its SpmvLane L.
+// Besides row and r it leaves E, st, lo, hi and acc in that scope: a kernel that takes it uses those names for nothing else, and
+// takes it once (a block around it would hide them, but the whole-row k_spmv then compile to other registers than before).
+// It is text and not a function on purpose.  A function is optimised on its own before it is inlined, and the compiler then
+// factors the four lazy terms of the loop differently (one v_mul_lo_u32 where there were four v_mul_i32_i24) and the segment
+// kernels take 1-2 more VGPRs; as text every kernel compiles to the instructions it had when it carried its own copy of the loop.
+#define SPMV_TEAM_SUM(row, r, it)                                                                                        \
+    constexpr int E = TEAM / KW;                                                                                         \
+    const int row = items ? items[it] : (int)it;                                                                         \
+    const i64d st = start[row];                                                                                          \
+    int lo = 0, hi = len[row];                                                                                           \
+    if (PARTIAL) {                                                                                                       \
+        lo = segbeg[it];                                                                                                 \
+        hi = min(hi, lo + SPMV_SEG);                                                                                     \
+    }                                                                                                                    \
+    typename ZpAcc<SMALL>::type acc = 0;                                                                                 \
+    for (int k0 = lo + L.e; k0 < hi; k0 += SPMV_UNROLL * E) {                                                            \
+        int2 a[SPMV_UNROLL];                                                                                             \
+        _Pragma("unroll") for (int u = 0; u < SPMV_UNROLL; u++) {                                                        \
+            const int k = k0 + u * E;                                                                                    \
+            a[u] = k < hi ? ent[st + k] : make_int2(0, 0);                                                               \
+        }                                                                                                                \
+        int xv[SPMV_UNROLL];                                                                                             \
+        _Pragma("unroll") for (int u = 0; u < SPMV_UNROLL; u++)                                                          \
+            xv[u] = (L.vok && k0 + u * E < hi) ? X[(i64d)a[u].x * ldx + L.v] : 0;                                        \
+        _Pragma("unroll") for (int u = 0; u < SPMV_UNROLL; u++)                                                          \
+            acc += ZpAcc<SMALL>::mul_lazy(F, a[u].y, zp_residue(F, hp, mhp, xv[u]));                                     \
+    }                                                                                                                    \
+    spmv_sum_t<SMALL> r;                                                                                                 \
+    if (SMALL) r = zp_reduce(F, (int64_t)acc);                                                                           \
+    else r = acc;                                                                                                        \
+    _Pragma("unroll") for (int o = KW; o < TEAM; o <<= 1) r += __shfl_xor(r, o, TEAM)
+
+// One team of TEAM lanes per work item (SPMV_TEAM_SUM).  PARTIAL: the segment's sum goes to part[it * KW + v]; otherwise
+// Y[row * ldy + v] <- sum + Y[row * ldy + v].
 template <bool SMALL, int KW, int TEAM, bool PARTIAL>
 __global__ __launch_bounds__(256) void k_spmv(int nitems, const int *__restrict__ items, const int *__restrict__ segbeg,
                                               const i64d *__restrict__ start, const int *__restrict__ len, const int2 *__restrict__ ent, ZpField F,
                                               int hp, int mhp, int kc, const int *__restrict__ X, i64d ldx, int *__restrict__ Y, i64d ldy,
                                               int *__restrict__ part)
 {
-    static_assert(TEAM % KW == 0 && 64 % TEAM == 0, "team shape");
-    constexpr int E = TEAM / KW;
-    typedef typename ZpAcc<SMALL>::type acc_t;
-    typedef typename std::conditional<SMALL, int, long long>::type sum_t;
     const int it = (int)(((i64d)blockIdx.x * blockDim.x + threadIdx.x) / TEAM);
-    if (it >= nitems) return; // whole teams leave together: the shuffles below stay inside a team
-    const int tl = threadIdx.x % TEAM;
-    const int v = tl % KW, e = tl / KW;
-    const bool vok = v < kc;
-    const int row = items ? items[it] : it;
-    const i64d st = start[row];
-    int lo = 0, hi = len[row];
+    if (it >= nitems) return; // whole teams leave together
+    const SpmvLane<KW, TEAM> L(kc);
+    SPMV_TEAM_SUM(row, r, it);
+    if (L.e != 0 || !L.vok) return;
     if (PARTIAL) {
-        lo = segbeg[it];
-        hi = min(hi, lo + SPMV_SEG);
-    }
-    acc_t acc = 0;
-    for (int k0 = lo + e; k0 < hi; k0 += SPMV_UNROLL * E) {
-        int2 a[SPMV_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) {
-            const int k = k0 + u * E;
-            a[u] = k < hi ? ent[st + k] : make_int2(0, 0);
-        }
-        int xv[SPMV_UNROLL];
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) xv[u] = (vok && k0 + u * E < hi) ? X[(i64d)a[u].x * ldx + v] : 0;
-#pragma unroll
-        for (int u = 0; u < SPMV_UNROLL; u++) {
-            int x = xv[u];
-            if (x < mhp || x > hp) x = zp_reduce(F, x);   // unreduced input: rare, and exact either way
-            acc += ZpAcc<SMALL>::mul_lazy(F, a[u].y, x); // (a padding slot is (0, 0): its lazy product is 0)
-        }
-    }
-    sum_t r;
-    if (SMALL) r = (sum_t)zp_reduce(F, (int64_t)acc);
-    else r = (sum_t)acc;
-#pragma unroll
-    for (int o = KW; o < TEAM; o <<= 1) r += __shfl_xor(r, o, TEAM);
-    if (e != 0 || !vok) return;
-    if (PARTIAL) {
-        part[(i64d)it * KW + v] = zp_reduce(F, (int64_t)r);
+        part[(i64d)it * KW + L.v] = zp_reduce(F, (int64_t)r);
     } else {
-        int *yp = Y + (i64d)row * ldy + v;
+        int *yp = Y + (i64d)row * ldy + L.v;
         *yp = zp_reduce(F, (int64_t)r + (int64_t)*yp);
     }
 }

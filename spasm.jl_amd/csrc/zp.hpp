@@ -80,6 +80,10 @@ ZP_HD int zp_reduce(const ZpField &F, int64_t x)
     return (int)r;
 }
 
+// a word of a caller's array, which need not be reduced, as a canonical residue: reduced where it is read, and only when it is
+// outside [mhp, hp] = [(int)mhalfp, (int)halfp] (rare, and exact either way)
+ZP_HD int zp_residue(const ZpField &F, int hp, int mhp, int x) { return (x < mhp || x > hp) ? zp_reduce(F, (int64_t)x) : x; }
+
 ZP_HD int zp_add(const ZpField &F, int a, int b) { return zp_normalize(F, (int64_t)a + (int64_t)b); }
 ZP_HD int zp_sub(const ZpField &F, int a, int b) { return zp_normalize(F, (int64_t)a - (int64_t)b); }
 ZP_HD int zp_neg(const ZpField &F, int a) { return zp_normalize(F, -(int64_t)a); }

@@ -54,6 +54,14 @@ def test_one_by_one_and_zero_matrix(S, p):
     # one vector given as a 1-d array
     got = run_seq(S, M, p, U[:, 0].copy(), V[:, 0].copy(), 5)
     assert got.shape == (5, 1) and got[:, 0].tolist() == W.ref_sequence(M, U[:, :1], V[:, :1], 5, p)[:, 0].tolist()
+    # every row is short, so the short class runs over the row range without a list: every chunk width KW of that launch, on the
+    # permutation-like matrix of the worst-case test below at n = 300 with random entries (several teams a workgroup, several
+    # workgroups; a wrong row or team stride moves an entry)
+    n = 300
+    P = W.Mat(n, n, np.arange(n + 1), rng.permutation(n), rng.integers(1, p, size=n))
+    for K in (1, 2, 4, 8, 16, 32, 64):
+        U, V = rand_bal(rng, (n, K), p), rand_bal(rng, (n, K), p)
+        assert run_seq(S, P, p, U, V, 4).tolist() == W.ref_sequence(P, U, V, 4, p).tolist(), K
     # the zero matrix: s_0 = u . v, then zeros
     n = 300
     Z = W.Mat.from_rows([[] for _ in range(n)], n)
@@ -65,7 +73,7 @@ def test_one_by_one_and_zero_matrix(S, p):
 
 
 @pytest.mark.parametrize("trans", (False, True))
-@pytest.mark.parametrize("K", (1, 3, 8, 64))
+@pytest.mark.parametrize("K", (1, 2, 3, 8, 16, 32, 64))   # every chunk width KW = 1, 2, 4, .., 64 of the step kernel
 @pytest.mark.parametrize("p", PRIMES)
 def test_short_and_medium_rows_many_workgroups(S, p, K, trans):
     rng = np.random.default_rng(1000 * K + p % 997 + int(trans))
@@ -84,7 +92,9 @@ def test_short_and_medium_rows_many_workgroups(S, p, K, trans):
 
 
 @pytest.mark.parametrize("trans", (False, True))
-@pytest.mark.parametrize("p,K", [(3, 8), (127, 1), (P16, 8), (P31, 3), (P32, 8), (P32, 64)])
+@pytest.mark.parametrize("p,K", [(3, 8), (127, 1), (P16, 8), (P31, 3), (P32, 8), (P32, 64),
+                                 # the other widths of either accumulator: i32 (p < 2^16) with KW = 2, 4, 16, 32, 64, i64 with 1, 2, 16, 32
+                                 (P16, 2), (3, 4), (127, 16), (P16, 32), (3, 64), (P32, 1), (P31, 2), (P32, 16), (P31, 32)])
 def test_long_rows_carry_the_projection_in_the_combine(S, p, K, trans):
     rng = np.random.default_rng(77 + K + p % 991)
     n = 40000

@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 
 P16, P31, P32 = 65521, 2**31 - 1, 4294967291
 PRIMES = (3, P16, 65537, P31, P32)
-KS = (1, 3, 8, 33, 64)
+KS = (1, 2, 3, 8, 16, 32, 33, 64)   # every chunk width KW = 1, 2, 4, .., 64 of the step kernel; 3 and 33 leave columns idle
 SENTINEL = 0x5A5A5A5A
 N = 32770
 SPECIAL = {0: 0, 1: 1, 2: 32, 3: 33, 4: 16384, 5: 16385, 6: 2 * 16384 + 1, 7: 0}   # row -> length; the other rows are short

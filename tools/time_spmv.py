@@ -1,6 +1,7 @@
 """Times the exact products on BASELINE config 3 (1M x 1M, 20 entries per row, p = 65521): A X and x A through the resident
 operator (spasm_amd_spmv_apply_dev on torch device tensors) for k = 1, 8, 32, by device events over --reps applies after a
-warm-up, and the one-shot spasm_Axpy (host arrays, upload included) by the host clock.  Prints one JSON line.
+warm-up, and the one-shot spasm_Axpy (host arrays, upload included) by the host clock.  Prints one JSON line and, with --out,
+appends it to that file.
 
 Algorithmic bytes of one apply: 8 nnz (the (j, x) entries) + 12 rows (row start and length) + 4k (cols + 2 rows) (X read once,
 Y read and written); GB/s against 8 TB/s, the MI355X's HBM peak.  Kernel times: run under `rocprofv3 --kernel-trace --stats`."""
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--ks", default="1,8,32")
+    ap.add_argument("--out", default=None)
     a = ap.parse_args()
     p = a.prime
     A = S.synth_csr(1, a.n, a.n, row_nnz=a.row_nnz, prime=p, seed=0x5A5A0003)
@@ -59,7 +61,11 @@ def main():
         S.axpy(A, x, y)
         walls.append((time.perf_counter() - t0) * 1e3)
     out["one_shot_spasm_Axpy_ms"] = round(float(np.median(walls)), 2)
-    print(json.dumps(out))
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write(line + "\n")
 
 
 if __name__ == "__main__":
