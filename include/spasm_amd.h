@@ -1029,6 +1029,71 @@ int spasm_amd_dcsr_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int K, co
                                    const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status);
 void spasm_amd_wiedemann_stats(i64 *out);   /* of the last poly_apply / Wiedemann solve call of this thread */
 
+/* ---- Engine extension: rank and determinant mod p without fill-in by preconditioned Wiedemann (csrc/precond.hpp) ----
+ * A rank and a determinant that use no elimination kernel: memory O(nnz + (n + m) * K), n, m < 2^24.  A is n x m (n rows).  With
+ * random diagonals D2 (n x n) and E = D1^2 (m x m), all entries non-zero, B = E A^T D2 A is m x m; for a square A, B = D A.  The
+ * projected sequence of B comes from the resident product with the diagonal scale folded into the step's launch, its recurrences
+ * from Berlekamp-Massey on the device, the lcm f over the K projections and the split f = x^e g, g(0) != 0, from the host.
+ *   CONTRACT      rank: the result deg g is a lower bound, always: deg g <= rank(A) whatever p, K and the seed (f divides the
+ *                 minimal polynomial of B; B is invertible on im B^e by Fitting's decomposition, so deg g <= dim im B^e <=
+ *                 rank(B) <= rank(A)).  deg g = rank(A) is likely, with a probability that grows with p (the published bound
+ *                 wants p >> n^2; over GF(3) the bound falls short often) and never certain, except that *certain = 1 when the
+ *                 result equals min(n, m).  det: status 1 is certain: either deg f = n, then f is the characteristic polynomial
+ *                 of D A and det A = (-1)^n f(0) / prod d_i, or x divides f, then A is singular and det A = 0.  status 0 says
+ *                 nothing (the value is 0 then).
+ *   precond_diagonal  the diagonals of try seed.  The words of one diagonal differ from each other as long as that is possible
+ *                 (the first p - 1 of them), so that D I = D has a minimal polynomial of full degree whenever n < p: word
+ *                 (which, i), 0 <= i < len, is 1 + P_b(i mod N) with N = p - 1, b = i div N and P_b a pseudo-random permutation
+ *                 of 0 .. N - 1: split x into two halves of h = ceil(bits(N - 1) / 2) bits (h >= 1), x = L * 2^h + R, and run
+ *                 four Feistel rounds r = 0 .. 3, (L, R) <- (R, L xor (w & (2^h - 1))), w the splitmix64 output (the mixer
+ *                 of minpoly_vectors) of the state
+ *                   seed + 0x9E3779B97F4A7C15 * ((which + 1) * 2^60 + b * 2^20 + r * 2^16 + R)  mod 2^64;
+ *                 x <- L * 2^h + R, and the four rounds are repeated on x while x >= N.  which = 0 is D2 (and the D of the
+ *                 determinant), which = 1 is E: the SQUARE mod p of that word (its words may repeat: w and p - w share a
+ *                 square).  Every word lies in 1 .. p - 1 and is returned as a balanced residue.  The states differ from those
+ *                 of minpoly_vectors, whose indices 2 * (r * K + c) + t + 1 stay below 2^32.  The same seed gives the same
+ *                 bytes.  Needs no device.
+ *   precond_sequence  op is a resident operator; d_left, d_right, U, V, S are HOST arrays (any int32 is reduced where it is read).
+ *                 mode 0: op is square, S[i * K + c] = sum_r U[r, c] * ((D A)^i V)[r, c] with D = diag(d_left) (n words; d_right
+ *                 is not read); one launch set per step.  mode 1: S[i * K + c] = sum_r U[r, c] * ((E A^T D2 A)^i V)[r, c] with
+ *                 D2 = diag(d_left) (n words), E = diag(d_right) (m words); U and V are m x K (ldu, ldv >= K); two launch sets
+ *                 per step, on the two views of the operator.  0 <= i < len, balanced residues, 1 <= K <= 64.  len == 0 writes
+ *                 nothing; an operator without rows or columns needs no launch.
+ *   wiedemann_rank, spmv_wiedemann_rank, dcsr_wiedemann_rank
+ *                 A host matrix, a resident operator, a resident matrix (on its device; its transpose is made on the device
+ *                 and lives for the call).  K == 0 means 8, tries <= 0 means 3, maxdeg <= 0 (or > min(n, m)) means min(n, m).
+ *                 Try t uses U, V = minpoly_vectors(m, K, seed + t) and precond_diagonal(n, seed + t, 0), (m, seed + t, 1), and
+ *                 runs 2 * maxdeg + 2 terms, that is 2 * (2 * maxdeg + 1) products with A -- not 2 * maxdeg terms as minpoly:
+ *                 B may have a nilpotent part, whose factor x takes f one degree beyond deg g (deg f <= min(n, m) + 1 always,
+ *                 because B = P Q with P m x n, Q n x m: its minimal polynomial divides x times that of Q P).  *rank is the largest deg g over the tries; the tries stop
+ *                 once it reaches min(n, m).  A projection or an lcm with deg g > maxdeg is refused ("degree bound too
+ *                 small").  n == 0 or m == 0: rank 0, certain 1, no device.
+ *   wiedemann_det, spmv_wiedemann_det, dcsr_wiedemann_det
+ *                 A must be square.  Try t runs the 2 * n terms (2 * n - 1 products) of D A with D = precond_diagonal(n,
+ *                 seed + t, 0) and U, V = minpoly_vectors(n, K, seed + t); the first try with deg f = n or f(0) = 0 ends the
+ *                 call with *status = 1; after the last try *status = 0 and *det = 0.  prod d_i and its inverse are exact host
+ *                 arithmetic.  The empty matrix has determinant 1, status 1, and needs no device.
+ *   stats         of the last of these calls of this thread: out[10] = n, m, K, tries used, products with A (per try
+ *                 2 * (2 * maxdeg + 1) for rank, 2 * n - 1 for det; (len - 1) * (1 + mode) for precond_sequence), launches,
+ *                 degree of f, multiplicity of x in f (of the try that set the result), device microseconds of the sequences
+ *                 and of Berlekamp-Massey (HIP events).  Every call clears what it does not fill.
+ *   deterministic two runs give the same bytes
+ *   errors        a NULL operator / matrix / array, a matrix that is not square (det, mode 0: "not square (3 x 2)"), K outside
+ *                 0 .. 64 (1 .. 64 for precond_sequence: "K out of range"), mode or which outside 0 .. 1, ldu or ldv < K, a
+ *                 prime outside 3 .. 0xFFFFFFFB, n or m >= 2^24, "degree bound too small", no device ("no HIP device"), out of
+ *                 memory: -1, NO output word is written, spasm_amd_last_error() names the cause.  The argument errors are found
+ *                 before a device is looked for (for a host matrix; an operator or a resident matrix has one already). */
+int spasm_amd_precond_diagonal(int len, uint64_t seed, int which, i64 prime, spasm_ZZp *d);
+int spasm_amd_precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_ZZp *d_left, const spasm_ZZp *d_right,
+                               const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S);
+int spasm_amd_wiedemann_rank(const struct spasm_csr *A, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain);
+int spasm_amd_spmv_wiedemann_rank(spasm_amd_spmv *op, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain);
+int spasm_amd_dcsr_wiedemann_rank(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain);
+int spasm_amd_wiedemann_det(const struct spasm_csr *A, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+int spasm_amd_spmv_wiedemann_det(spasm_amd_spmv *op, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+int spasm_amd_dcsr_wiedemann_det(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+void spasm_amd_precond_stats(i64 *out);   /* of the last preconditioned Wiedemann call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -341,6 +341,15 @@ SIGNATURES = {
     "spasm_amd_spmv_wiedemann_solve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_dcsr_wiedemann_solve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_wiedemann_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_precond_diagonal": (C.c_int32, [C.c_int32, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p]),
+    "spasm_amd_precond_sequence": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_wiedemann_rank": (C.c_int32, [_P(CsrStruct), C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int32)]),
+    "spasm_amd_spmv_wiedemann_rank": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int32)]),
+    "spasm_amd_dcsr_wiedemann_rank": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, _P(C.c_int64), _P(C.c_int32)]),
+    "spasm_amd_wiedemann_det": (C.c_int32, [_P(CsrStruct), C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_spmv_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_dcsr_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_precond_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -2321,3 +2321,114 @@ def wiedemann_stats():
 SpMV.poly_apply = poly_apply
 SpMV.wiedemann_solve = wiedemann_solve
 DeviceCSR.wiedemann_solve = wiedemann_solve
+
+
+# ---------------------------------------------------------------------------------------------
+# Rank and determinant by preconditioned Wiedemann  (spasm_amd_wiedemann_rank*, _wiedemann_det*, _precond_*; csrc/precond.hpp)
+# ---------------------------------------------------------------------------------------------
+PRECOND_STATS = ("n", "m", "K", "tries", "products", "launches", "degree", "x_multiplicity", "sequence_device_us", "bm_device_us")
+
+
+def _precond_target(A, stem):
+    """(who, function, handle) of the entry point of `stem` for a CSR, an SpMV or a DeviceCSR"""
+    lib = _abi.lib()
+    if isinstance(A, CSR):
+        who, arg = f"spasm_amd_{stem}", A.data
+    elif isinstance(A, SpMV):
+        if not A._op:
+            raise SpasmError("the operator is closed")
+        who, arg = f"spasm_amd_spmv_{stem}", A._op
+    elif isinstance(A, DeviceCSR):
+        who, arg = f"spasm_amd_dcsr_{stem}", A._need()
+    else:
+        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    return who, getattr(lib, who), arg
+
+
+def wiedemann_rank(A, K=8, seed=0, tries=3, maxdeg=None):
+    """wiedemann_rank(A, K=8, seed=0, tries=3, maxdeg=None) -> (rank, certain): the rank of the n x m matrix A mod p by
+    preconditioned Wiedemann, without elimination or fill-in.  A is a CSR (spasm_amd_wiedemann_rank), an SpMV operator
+    (spasm_amd_spmv_wiedemann_rank) or a DeviceCSR (spasm_amd_dcsr_wiedemann_rank).  The result is a lower bound, always; it equals
+    the rank with a probability that grows with p, and certain is True only when it reaches min(n, m).  `tries` seeds seed,
+    seed + 1, .. are used and the largest bound is returned.  maxdeg bounds the rank looked for (None: min(n, m)); a larger one
+    is refused ("degree bound too small")."""
+    who, fn, arg = _precond_target(A, "wiedemann_rank")
+    rank, certain = C.c_int64(0), C.c_int32(0)
+    with _quiet(True):
+        rc = fn(arg, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), 0 if maxdeg is None else int(maxdeg), C.byref(rank), C.byref(certain))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return int(rank.value), bool(certain.value)
+
+
+def wiedemann_det(A, K=8, seed=0, tries=3):
+    """wiedemann_det(A, K=8, seed=0, tries=3) -> (det, status): the determinant of the square matrix A mod p as a balanced residue
+    by preconditioned Wiedemann, without elimination or fill-in.  A is a CSR (spasm_amd_wiedemann_det), an SpMV operator
+    (spasm_amd_spmv_wiedemann_det) or a DeviceCSR (spasm_amd_dcsr_wiedemann_det).  status 1: det is certain; status 0: undecided
+    after `tries` tries with the seeds seed, seed + 1, .. (det is 0 then and says nothing)."""
+    who, fn, arg = _precond_target(A, "wiedemann_det")
+    det, status = C.c_int32(0), C.c_int32(0)
+    with _quiet(True):
+        rc = fn(arg, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), C.byref(det), C.byref(status))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return int(det.value), int(status.value)
+
+
+def precond_diagonal(length, seed, which, prime):
+    """The int32 diagonal of `length` non-zero balanced residues that try `seed` of wiedemann_rank / wiedemann_det uses
+    (spasm_amd_precond_diagonal): which = 0 the left one (D2, or D of the determinant), which = 1 the right one (E = D1^2)."""
+    d = np.zeros(int(length), dtype=np.int32)
+    rc = _abi.lib().spasm_amd_precond_diagonal(int(length), int(seed) & 0xFFFFFFFFFFFFFFFF, int(which), int(prime), d.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_precond_diagonal failed")
+    return d
+
+
+def precond_sequence(op, mode, d_left, d_right, U, V, length):
+    """precond_sequence(op, mode, d_left, d_right, U, V, length) -> S of shape (length, K): the projected sequence
+    S[i, c] = sum_r U[r, c] * (B^i V)[r, c] mod p of the preconditioned operator with the caller's diagonals
+    (spasm_amd_precond_sequence).  mode 0: B = diag(d_left) A, A square (d_right may be None).  mode 1: B = diag(d_right) A^T
+    diag(d_left) A for the n x m matrix A of the SpMV operator op; d_left has n words, d_right m, U and V are m x K.  All int32
+    numpy arrays, any int32 is reduced where it is read."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n, m = op.shape
+    length = int(length)
+    if length < 0:
+        raise ValueError("length must not be negative")
+    for a, name in ((U, "U"), (V, "V")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.ndim != 2 or a.shape[0] != m or a.shape != U.shape:
+            raise TypeError(f"{name} must be an int32 numpy array of shape ({m}, K)")
+    k = U.shape[1]
+    Uc, Vc = np.ascontiguousarray(U), np.ascontiguousarray(V)
+    diag = []
+    for a, name, size in ((d_left, "d_left", n), (d_right, "d_right", m)):
+        if a is None:
+            diag.append(None)
+            continue
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32 or a.shape != (size,):
+            raise TypeError(f"{name} must be an int32 numpy array of {size} words")
+        diag.append(np.ascontiguousarray(a))
+    S = np.zeros((length, k), dtype=np.int32)
+    rc = _abi.lib().spasm_amd_precond_sequence(op._op, int(mode), int(k), length, None if diag[0] is None else diag[0].ctypes.data,
+                                               None if diag[1] is None else diag[1].ctypes.data, Uc.ctypes.data, k, Vc.ctypes.data, k, S.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_precond_sequence failed")
+    return S
+
+
+def precond_stats():
+    """Counters of the last preconditioned Wiedemann call of this thread (spasm_amd_precond_stats), keyed by PRECOND_STATS."""
+    out = (C.c_int64 * 10)()
+    _abi.lib().spasm_amd_precond_stats(out)
+    return {k: int(v) for k, v in zip(PRECOND_STATS, out)}
+
+
+SpMV.wiedemann_rank = wiedemann_rank
+SpMV.wiedemann_det = wiedemann_det
+SpMV.precond_sequence = precond_sequence
+DeviceCSR.wiedemann_rank = wiedemann_rank
+DeviceCSR.wiedemann_det = wiedemann_det

@@ -11741,3 +11741,475 @@ SPASM_API void spasm_amd_wiedemann_stats(i64 *out)
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Rank and determinant without fill-in by preconditioned Wiedemann (precond.hpp): the projected sequences of D A and of
+// E A^T D2 A, Berlekamp-Massey on the device, the lcm over the K projections and the factor x^e on the host.
+// ------------------------------------------------------------------------------------------------
+#include "precond.hpp"
+
+namespace {
+
+// n, m, K, tries used, products with A, launches, degree of f, multiplicity of x in f, device us of the sequences, device us of
+// Berlekamp-Massey
+thread_local i64 g_precond_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+void precond_stats_reset() { memset(g_precond_stats, 0, sizeof g_precond_stats); }
+
+// The diagonals of the preconditioners.  The words of one diagonal differ from each other as long as that is possible (the
+// first p - 1 of them): D I = D must have a minimal polynomial of full degree for the determinant of the identity to be certain,
+// and independent words repeat with the probability of the birthday problem (64 of 126: all but certainly).  So word (which, i)
+// is 1 + P_b(i mod N), N = p - 1, b = i div N, with P_b a pseudo-random permutation of 0 .. N - 1: four Feistel rounds on two
+// halves of h = ceil(bits(N - 1) / 2) bits, (L, R) <- (R, L xor (w & (2^h - 1))), w the splitmix64 output of the state
+// seed + 0x9E3779B97F4A7C15 * ((which + 1) * 2^60 + b * 2^20 + r * 2^16 + R) in round r, repeated while the result is >= N (a
+// permutation of 0 .. 2^(2h) - 1 walked along its cycle back into 0 .. N - 1: a permutation of these; 2^(2h) < 4 N).  which = 1
+// squares the word mod p.  The multiplier is odd, so distinct indices give distinct states, and the indices of minpoly_vectors
+// stay below 2^32 (2 * n * K + 1 <= 2^31 + 1 for n < 2^24, K <= 64) while these start at 2^60.
+void precond_diagonal(int len, uint64_t seed, int which, i64 prime, int *d)
+{
+    const uint64_t p = (uint64_t)prime, N = p - 1;
+    int bits = 0;
+    while (bits < 32 && ((N - 1) >> bits) != 0) bits++;
+    const int h = std::max(1, (bits + 1) / 2);
+    const uint64_t mask = ((uint64_t)1 << h) - 1;
+    for (int i = 0; i < len; i++) {
+        const uint64_t base = (((uint64_t)which + 1) << 60) + (((uint64_t)i / N) << 20);
+        uint64_t x = (uint64_t)i % N;
+        do {
+            uint64_t L = x >> h, R = x & mask;
+            for (uint64_t r = 0; r < 4; r++) {
+                const uint64_t t = L ^ (minpoly_mix(seed + 0x9E3779B97F4A7C15ULL * (base + (r << 16) + R)) & mask);
+                L = R;
+                R = t;
+            }
+            x = (L << h) | R;
+        } while (x >= N);
+        uint64_t w = 1 + x;
+        if (which == 1) w = w * w % p;
+        d[i] = wied_balanced(w, p);
+    }
+}
+
+// The sequence of the preconditioned operator on device arrays.  Tr == NULL: D A on the view Fw of a square matrix, dl its
+// diagonal, the iterates ping-pong in W.w0 / W.w1.  Else E A^T D2 A: Fw and Tr are the two views of the n x m matrix, dl = D2
+// (n words), dr = E (m words), W.w0 holds the n x KW intermediate and W.w1 the m x KW iterate.
+template <bool SMALL, int KW>
+int precond_launch(const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int kc, i64 len, const int *dl, const int *dr, const int *U, i64 ldu,
+                   const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap, hipStream_t s)
+{
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, dim = Tr ? Fw.cols : Fw.rows;
+    int launches = 0;
+    HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
+    hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+    launches++;
+    const int *X = X0;
+    i64d ldx = (i64d)ldx0;
+    int *Y = W.w0.p;
+    for (i64 i = 1; i < len; i++) {
+        long long *acc = W.acc.p + i * KW;
+        if (Tr) {
+            launches += spmv_step_launch<SMALL, KW>(Fw, F, kc, X, ldx, W.w0.p, (i64d)KW, DiagEpi{dl, nullptr, 0, nullptr}, cap, s);
+            launches += spmv_step_launch<SMALL, KW>(*Tr, F, kc, W.w0.p, (i64d)KW, W.w1.p, (i64d)KW, DiagEpi{dr, U, (i64d)ldu, acc}, cap, s);
+            X = W.w1.p;
+        } else {
+            launches += spmv_step_launch<SMALL, KW>(Fw, F, kc, X, ldx, Y, (i64d)KW, DiagEpi{dl, U, (i64d)ldu, acc}, cap, s);
+            X = Y;
+            Y = Y == W.w0.p ? W.w1.p : W.w0.p;
+        }
+        ldx = KW;
+    }
+    const i64 total = len * kc;
+    hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, kc, KW, F, W.acc.p, S);
+    HIPCHK(hipGetLastError());
+    return launches + 1;
+}
+
+// S[i * K + c] = sum_r U[r, c] * (B^i V)[r, c], 0 <= i < len, B = D A (Tr == NULL) or E A^T D2 A, on device arrays, enqueued on
+// s; no host synchronization.  Both dimensions of the matrix are positive, 1 <= K <= 64, len >= 1.  Returns the launches.
+int precond_run(const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int K, i64 len, const int *dl, const int *dr, const int *U, i64 ldu,
+                const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
+{
+    const int kw = spmv_kw(K), cap = step_grid_cap();
+    if (len > 1) {
+        W.w0.ensure((size_t)Fw.rows * kw);
+        if (Tr) W.w1.ensure((size_t)Fw.cols * kw);
+        else if (len > 2) W.w1.ensure((size_t)Fw.rows * kw);
+    }
+    W.acc.ensure((size_t)len * kw);
+    return dispatch_kw(kw, [&](auto KW) {
+        return F.small ? precond_launch<true, KW()>(Fw, Tr, F, K, len, dl, dr, U, ldu, X, ldx, W, S, cap, s)
+                       : precond_launch<false, KW()>(Fw, Tr, F, K, len, dl, dr, U, ldu, X, ldx, W, S, cap, s);
+    });
+}
+
+// What one try of rank or determinant leaves on the host: the lcm f of the K Berlekamp-Massey polynomials.
+struct PrecondTry {
+    DevBuf<int> dU, dV, dl, dr, dS, d_coef, d_deg, gwork;
+    KrylovWork W;
+    std::vector<int> hu, hv, hd, hc, diag;
+    SpgEvents ev;
+};
+
+// One try with the seed `seed`: the diagonals and vectors of the seed go up, the sequence of len terms and Berlekamp-Massey run,
+// and the lcm over K comes back.  g (may be NULL) receives the left diagonal as residues in [0, p).  A projection whose
+// polynomial has more than md roots away from 0 is refused, and so is such an lcm.
+HPoly precond_try(PrecondTry &T, const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int K, uint64_t seed, int len, int md, std::vector<uint64_t> *g)
+{
+    const int n = Fw.rows, dim = Tr ? Fw.cols : Fw.rows;
+    const uint64_t p = (uint64_t)F.p;
+    hipStream_t s = nullptr;
+    const size_t nk = (size_t)dim * K;
+    T.hu.resize(nk);
+    T.hv.resize(nk);
+    minpoly_vectors(dim, K, seed, F.p, T.hu.data(), T.hv.data());
+    T.dU.ensure(nk);
+    T.dV.ensure(nk);
+    T.dl.ensure((size_t)n);
+    HIPCHK(hipMemcpyAsync(T.dU.p, T.hu.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(T.dV.p, T.hv.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
+    T.diag.resize((size_t)n + (size_t)(Tr ? dim : 0));
+    precond_diagonal(n, seed, 0, F.p, T.diag.data());
+    HIPCHK(hipMemcpyAsync(T.dl.p, T.diag.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (g) {
+        g->resize((size_t)n);
+        for (int i = 0; i < n; i++) (*g)[(size_t)i] = wied_residue(T.diag[(size_t)i], p);
+    }
+    if (Tr) {
+        precond_diagonal(dim, seed, 1, F.p, T.diag.data() + n);
+        T.dr.ensure((size_t)dim);
+        HIPCHK(hipMemcpyAsync(T.dr.p, T.diag.data() + n, (size_t)dim * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    const i64 ldc = (i64)len + 1;
+    T.dS.ensure((size_t)len * K);
+    T.d_coef.ensure((size_t)K * (size_t)ldc);
+    T.d_deg.ensure((size_t)K);
+    HIPCHK(hipEventRecord(T.ev.e[0], s));
+    const int launches = precond_run(Fw, Tr, F, K, len, T.dl.p, T.dr.p, T.dU.p, K, T.dV.p, K, T.W, T.dS.p, s);
+    HIPCHK(hipEventRecord(T.ev.e[1], s));
+    bm_device(F, K, len, T.dS.p, K, bm_class(len, 0), T.d_coef.p, ldc, T.d_deg.p, T.gwork, s);
+    HIPCHK(hipEventRecord(T.ev.e[2], s));
+    T.hd.resize((size_t)K);
+    T.hc.resize((size_t)K * (size_t)ldc);
+    HIPCHK(hipMemcpyAsync(T.hd.data(), T.d_deg.p, T.hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(T.hc.data(), T.d_coef.p, T.hc.size() * sizeof(int), hipMemcpyDeviceToHost, s)); // the K polynomials in one copy
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = g_precond_stats;
+    st[3]++;
+    st[4] += (i64)(len - 1) * (Tr ? 2 : 1);
+    st[5] += launches + 1;
+    st[8] += (i64)(T.ev.ms(0, 1) * 1000.0);
+    st[9] += (i64)(T.ev.ms(1, 2) * 1000.0);
+    HPoly r(1, 1);
+    for (int c = 0; c < K; c++) {
+        const int d = T.hd[(size_t)c];
+        const HPoly f = hpoly_load(T.hc.data() + (size_t)c * (size_t)ldc, d + 1, p);
+        size_t e = 0;
+        while (f[e] == 0) e++; // f is monic: its leading word ends the loop
+        if ((i64)f.size() - 1 - (i64)e > md) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d with x^%d, maxdeg %d)", c, d, (int)e, md);
+            throw EngineError(msg);
+        }
+        r = hpoly_lcm(r, f, p);
+    }
+    size_t e = 0;
+    while (r[e] == 0) e++;
+    if ((i64)r.size() - 1 - (i64)e > md) throw EngineError("degree bound too small (the lcm of the projections exceeds maxdeg)");
+    return r;
+}
+
+int precond_tries(int tries) { return tries <= 0 ? 3 : tries; }
+
+void precond_limits(int n, int m)
+{
+    if (n >= (1 << 24) || m >= (1 << 24)) throw EngineError("preconditioned Wiedemann limited to n, m < 2^24");
+}
+
+// The rank behind the three entries: Fw and Tr are the two views of the n x m matrix, n > 0, m > 0.
+void precond_rank_run(const SpmvView &Fw, const SpmvView &Tr, const ZpField &F, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
+{
+    const int n = Fw.rows, m = Fw.cols, mn = std::min(n, m);
+    const int md = (maxdeg <= 0 || maxdeg > mn) ? mn : maxdeg;
+    // 2 * md + 2 terms: f = x^e g may have one more degree than its g (see the header)
+    const int len = 2 * md + 2;
+    bm_check_len(F, len);
+    i64 *st = g_precond_stats;
+    st[0] = n;
+    st[1] = m;
+    st[2] = K;
+    PrecondTry T;
+    i64 best = -1;
+    const int ntries = precond_tries(tries);
+    for (int t = 0; t < ntries && best < mn; t++) {
+        const HPoly f = precond_try(T, Fw, &Tr, F, K, seed + (uint64_t)t, len, md, nullptr);
+        size_t e = 0;
+        while (f[e] == 0) e++;
+        const i64 bound = (i64)f.size() - 1 - (i64)e;
+        if (bound > best) {
+            best = bound;
+            st[6] = (i64)f.size() - 1;
+            st[7] = (i64)e;
+        }
+    }
+    *rank = best;
+    *certain = best == mn;
+}
+
+// The determinant behind the three entries: V is the view of the square matrix, n > 0.
+void precond_det_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    const int n = V.rows;
+    const uint64_t p = (uint64_t)F.p;
+    const int len = 2 * n;
+    bm_check_len(F, len);
+    i64 *st = g_precond_stats;
+    st[0] = n;
+    st[1] = n;
+    st[2] = K;
+    PrecondTry T;
+    std::vector<uint64_t> d;
+    const int ntries = precond_tries(tries);
+    for (int t = 0; t < ntries; t++) {
+        const HPoly f = precond_try(T, V, nullptr, F, K, seed + (uint64_t)t, len, n, &d);
+        size_t e = 0;
+        while (f[e] == 0) e++;
+        st[6] = (i64)f.size() - 1;
+        st[7] = (i64)e;
+        if (e > 0) { // x divides a divisor of the minimal polynomial of D A: A is singular
+            *det = 0;
+            *status = 1;
+            return;
+        }
+        if ((int)f.size() - 1 == n) { // f is the characteristic polynomial of D A: det(D A) = (-1)^n f(0)
+            uint64_t prod = 1;
+            for (uint64_t w : d) prod = prod * w % p;
+            uint64_t v = f[0] * hinv(prod, p) % p;
+            if (n & 1) v = (p - v) % p;
+            *det = wied_balanced(v, p);
+            *status = 1;
+            return;
+        }
+    }
+    *det = 0;
+    *status = 0;
+}
+
+// the view of a resident matrix (n, m > 0)
+void dcsr_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->m, D->p.p, D->ent.p, s); }
+
+void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_ZZp *dl, const spasm_ZZp *dr, const spasm_ZZp *U, i64 ldu,
+                      const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    if (!op) throw EngineError("NULL operator");
+    if (mode != 0 && mode != 1) throw EngineError("mode must be 0 (D A) or 1 (E A^T D2 A)");
+    const int n = op->A.n, m = op->A.m;
+    if (mode == 0) minpoly_square(n, m);
+    if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
+    if (len < 0 || (i64)len * 64 >= ((i64)1 << 31) || ldu < K || ldv < K) throw EngineError("bad arguments (0 <= len < 2^25, ldu >= K, ldv >= K)");
+    if (len == 0) return;
+    if (!S || (m > 0 && (!U || !V)) || (n > 0 && !dl) || (mode == 1 && m > 0 && !dr)) throw EngineError("NULL array");
+    const uint64_t p = (uint64_t)op->F.p;
+    if (n == 0 || m == 0) { // the operator is zero: s_0 = U^T V on the host, every later term is 0
+        memset(S, 0, (size_t)len * K * sizeof(int));
+        for (int c = 0; c < K; c++) {
+            uint64_t a = 0;
+            for (i64 r = 0; r < m; r++) a = (a + wied_residue(U[r * ldu + c], p) * wied_residue(V[r * ldv + c], p)) % p;
+            S[c] = wied_balanced(a, p);
+        }
+        return;
+    }
+    DeviceGuard g(op);
+    if (mode == 1) op->build_transpose();
+    const size_t dim = (size_t)m, kk = (size_t)K;
+    hipStream_t s = nullptr;
+    DevBuf<int> dU, dV, dS, ddl, ddr;
+    KrylovWork W;
+    dU.alloc(dim * kk);
+    dV.alloc(dim * kk);
+    dS.alloc((size_t)len * kk);
+    ddl.alloc((size_t)n);
+    HIPCHK(hipMemcpy2DAsync(dU.p, kk * sizeof(int), U, (size_t)ldu * sizeof(int), kk * sizeof(int), dim, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(dV.p, kk * sizeof(int), V, (size_t)ldv * sizeof(int), kk * sizeof(int), dim, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ddl.p, dl, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (mode == 1) {
+        ddr.alloc(dim);
+        HIPCHK(hipMemcpyAsync(ddr.p, dr, dim * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    const int launches = precond_run(op->fwd, mode == 1 ? &op->tr : nullptr, op->F, K, len, ddl.p, ddr.p, dU.p, K, dV.p, K, W, dS.p, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> out((size_t)len * kk);
+    HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = g_precond_stats;
+    st[0] = n;
+    st[1] = m;
+    st[2] = K;
+    st[4] = (i64)(len - 1) * (mode == 1 ? 2 : 1);
+    st[5] = launches;
+    st[8] = (i64)(ev.ms(0, 1) * 1000.0);
+    memcpy(S, out.data(), out.size() * sizeof(int));
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- rank and determinant by preconditioned Wiedemann (precond.hpp; engine extension) ----
+SPASM_API int spasm_amd_precond_diagonal(int len, uint64_t seed, int which, i64 prime, spasm_ZZp *d)
+{
+    return abi_call("spasm_amd_precond_diagonal", -1, [&] {
+        precond_stats_reset();
+        if (len < 0 || (which != 0 && which != 1)) throw EngineError("bad arguments (len >= 0, which 0 or 1)");
+        if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+        if (len > 0 && !d) throw EngineError("NULL array");
+        precond_diagonal(len, seed, which, prime, d);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_ZZp *d_left, const spasm_ZZp *d_right,
+                                         const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    return abi_call("spasm_amd_precond_sequence", -1, [&] {
+        precond_stats_reset();
+        precond_sequence(op, mode, K, len, d_left, d_right, U, ldu, V, ldv, S);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_wiedemann_rank(const struct spasm_csr *A, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
+{
+    return abi_call("spasm_amd_wiedemann_rank", -1, [&] {
+        DeviceGuard g;
+        precond_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        K = minpoly_K(K);
+        if (!rank || !certain) throw EngineError("NULL array");
+        precond_limits(A->n, A->m);
+        if (A->n == 0 || A->m == 0) { *rank = 0; *certain = 1; return 0; }
+        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_rank"));
+        op->build_transpose();
+        i64 r = 0;
+        int c = 0;
+        precond_rank_run(op->fwd, op->tr, op->F, K, seed, tries, maxdeg, &r, &c);
+        *rank = r;
+        *certain = c;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_spmv_wiedemann_rank(spasm_amd_spmv *op, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
+{
+    return abi_call("spasm_amd_spmv_wiedemann_rank", -1, [&] {
+        precond_stats_reset();
+        if (!op) throw EngineError("NULL operator");
+        K = minpoly_K(K);
+        if (!rank || !certain) throw EngineError("NULL array");
+        precond_limits(op->A.n, op->A.m);
+        if (op->A.n == 0 || op->A.m == 0) { *rank = 0; *certain = 1; return 0; }
+        DeviceGuard g(op);
+        op->build_transpose();
+        i64 r = 0;
+        int c = 0;
+        precond_rank_run(op->fwd, op->tr, op->F, K, seed, tries, maxdeg, &r, &c);
+        *rank = r;
+        *certain = c;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_wiedemann_rank(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
+{
+    return abi_call("spasm_amd_dcsr_wiedemann_rank", -1, [&] {
+        precond_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        K = minpoly_K(K);
+        if (!rank || !certain) throw EngineError("NULL array");
+        precond_limits(D->n, D->m);
+        if (D->n == 0 || D->m == 0) { *rank = 0; *certain = 1; return 0; }
+        DeviceGuard g(D);
+        // the transpose stays on the device for the length of the call
+        std::unique_ptr<spasm_amd_dcsr> T(dcsr_transpose(D, "transpose"));
+        SpmvView fwd, tr;
+        dcsr_view(D, fwd, nullptr);
+        dcsr_view(T.get(), tr, nullptr);
+        i64 r = 0;
+        int c = 0;
+        precond_rank_run(fwd, tr, D->F, K, seed, tries, maxdeg, &r, &c);
+        *rank = r;
+        *certain = c;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_wiedemann_det(const struct spasm_csr *A, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_wiedemann_det", -1, [&] {
+        DeviceGuard g;
+        precond_stats_reset();
+        if (const char *bad = batch_check(A)) throw EngineError(bad);
+        minpoly_square(A->n, A->m);
+        K = minpoly_K(K);
+        if (!det || !status) throw EngineError("NULL array");
+        precond_limits(A->n, A->m);
+        if (A->n == 0) { *det = 1; *status = 1; return 0; }
+        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_det"));
+        spasm_ZZp v = 0;
+        int st = 0;
+        precond_det_run(op->fwd, op->F, K, seed, tries, &v, &st);
+        *det = v;
+        *status = st;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_spmv_wiedemann_det(spasm_amd_spmv *op, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_spmv_wiedemann_det", -1, [&] {
+        precond_stats_reset();
+        if (!op) throw EngineError("NULL operator");
+        minpoly_square(op->A.n, op->A.m);
+        K = minpoly_K(K);
+        if (!det || !status) throw EngineError("NULL array");
+        precond_limits(op->A.n, op->A.m);
+        if (op->A.n == 0) { *det = 1; *status = 1; return 0; }
+        DeviceGuard g(op);
+        spasm_ZZp v = 0;
+        int st = 0;
+        precond_det_run(op->fwd, op->F, K, seed, tries, &v, &st);
+        *det = v;
+        *status = st;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_dcsr_wiedemann_det(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_dcsr_wiedemann_det", -1, [&] {
+        precond_stats_reset();
+        if (!D) throw EngineError("NULL matrix");
+        minpoly_square(D->n, D->m);
+        K = minpoly_K(K);
+        if (!det || !status) throw EngineError("NULL array");
+        precond_limits(D->n, D->m);
+        if (D->n == 0) { *det = 1; *status = 1; return 0; }
+        DeviceGuard g(D);
+        SpmvView view;
+        dcsr_square_view(D, view, nullptr);
+        spasm_ZZp v = 0;
+        int st = 0;
+        precond_det_run(view, D->F, K, seed, tries, &v, &st);
+        *det = v;
+        *status = st;
+        return 0;
+    });
+}
+
+SPASM_API void spasm_amd_precond_stats(i64 *out)
+{
+    if (out) memcpy(out, g_precond_stats, sizeof g_precond_stats);
+}
+
+} // extern "C"
