@@ -2152,6 +2152,21 @@ def minpoly_vectors(n, K, seed, prime):
     return U, V
 
 
+def _family_target(A, stem):
+    """(who, function, handle, rows) of the entry point of `stem` for a CSR, an SpMV or a DeviceCSR"""
+    if isinstance(A, CSR):
+        who, arg, n = f"spasm_amd_{stem}", A.data, A.n
+    elif isinstance(A, SpMV):
+        if not A._op:
+            raise SpasmError("the operator is closed")
+        who, arg, n = f"spasm_amd_spmv_{stem}", A._op, A.shape[0]
+    elif isinstance(A, DeviceCSR):
+        who, arg, n = f"spasm_amd_dcsr_{stem}", A._need(), A.shape[0]
+    else:
+        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    return who, getattr(_abi.lib(), who), arg, n
+
+
 def minpoly(A, K=8, seed=0, maxdeg=None, U=None, V=None):
     """minpoly(A, K=8, seed=0, maxdeg=None, U=None, V=None) -> numpy int32 array: the lcm of the minimal polynomials of K
     projections u^T A^i v of the Krylov sequence of the square matrix A, monic, low degree first, balanced residues.  A is a CSR
@@ -2160,17 +2175,7 @@ def minpoly(A, K=8, seed=0, maxdeg=None, U=None, V=None):
     polynomial has a larger degree is refused ("degree bound too small").
     The result always divides the minimal polynomial of A and equals it with a probability that grows with p and K.  If its
     constant term is 0, A is singular (certain).  If its degree is n, it is the characteristic polynomial."""
-    lib = _abi.lib()
-    if isinstance(A, CSR):
-        who, fn, arg, n = "spasm_amd_minpoly", lib.spasm_amd_minpoly, A.data, A.n
-    elif isinstance(A, SpMV):
-        if not A._op:
-            raise SpasmError("the operator is closed")
-        who, fn, arg, n = "spasm_amd_spmv_minpoly", lib.spasm_amd_spmv_minpoly, A._op, A.shape[0]
-    elif isinstance(A, DeviceCSR):
-        who, fn, arg, n = "spasm_amd_dcsr_minpoly", lib.spasm_amd_dcsr_minpoly, A._need(), A.shape[0]
-    else:
-        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    who, fn, arg, n = _family_target(A, "minpoly")
     K = int(K)
     kk = 8 if K == 0 else K
     ptrs = []
@@ -2280,17 +2285,7 @@ def wiedemann_solve(A, B, trans=False, seed=0, tries=3, maxdeg=None, U=None):
     column:  1  solved, A x = b verified on the device;  2  the column of X is a non-zero vector of the kernel of A (A is singular:
     certain; nothing is said about b);  0  undecided after `tries` tries with the seeds seed, seed + 1, .. (the column of X is
     zero).  U (n x K) fixes the projection vectors and allows one try only.  maxdeg bounds the degree of the polynomials (None: n)."""
-    lib = _abi.lib()
-    if isinstance(A, CSR):
-        who, fn, arg, n = "spasm_amd_wiedemann_solve", lib.spasm_amd_wiedemann_solve, A.data, A.n
-    elif isinstance(A, SpMV):
-        if not A._op:
-            raise SpasmError("the operator is closed")
-        who, fn, arg, n = "spasm_amd_spmv_wiedemann_solve", lib.spasm_amd_spmv_wiedemann_solve, A._op, A.shape[0]
-    elif isinstance(A, DeviceCSR):
-        who, fn, arg, n = "spasm_amd_dcsr_wiedemann_solve", lib.spasm_amd_dcsr_wiedemann_solve, A._need(), A.shape[0]
-    else:
-        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
+    who, fn, arg, n = _family_target(A, "wiedemann_solve")
     if not isinstance(B, np.ndarray) or B.dtype != np.int32 or B.ndim not in (1, 2) or B.shape[0] != n:
         raise TypeError(f"B must be an int32 numpy array of shape ({n},) or ({n}, K)")
     k = 1 if B.ndim == 1 else B.shape[1]
@@ -2329,22 +2324,6 @@ DeviceCSR.wiedemann_solve = wiedemann_solve
 PRECOND_STATS = ("n", "m", "K", "tries", "products", "launches", "degree", "x_multiplicity", "sequence_device_us", "bm_device_us")
 
 
-def _precond_target(A, stem):
-    """(who, function, handle) of the entry point of `stem` for a CSR, an SpMV or a DeviceCSR"""
-    lib = _abi.lib()
-    if isinstance(A, CSR):
-        who, arg = f"spasm_amd_{stem}", A.data
-    elif isinstance(A, SpMV):
-        if not A._op:
-            raise SpasmError("the operator is closed")
-        who, arg = f"spasm_amd_spmv_{stem}", A._op
-    elif isinstance(A, DeviceCSR):
-        who, arg = f"spasm_amd_dcsr_{stem}", A._need()
-    else:
-        raise TypeError("a CSR, an SpMV or a DeviceCSR expected")
-    return who, getattr(lib, who), arg
-
-
 def wiedemann_rank(A, K=8, seed=0, tries=3, maxdeg=None):
     """wiedemann_rank(A, K=8, seed=0, tries=3, maxdeg=None) -> (rank, certain): the rank of the n x m matrix A mod p by
     preconditioned Wiedemann, without elimination or fill-in.  A is a CSR (spasm_amd_wiedemann_rank), an SpMV operator
@@ -2352,7 +2331,7 @@ def wiedemann_rank(A, K=8, seed=0, tries=3, maxdeg=None):
     the rank with a probability that grows with p, and certain is True only when it reaches min(n, m).  `tries` seeds seed,
     seed + 1, .. are used and the largest bound is returned.  maxdeg bounds the rank looked for (None: min(n, m)); a larger one
     is refused ("degree bound too small")."""
-    who, fn, arg = _precond_target(A, "wiedemann_rank")
+    who, fn, arg, _ = _family_target(A, "wiedemann_rank")
     rank, certain = C.c_int64(0), C.c_int32(0)
     with _quiet(True):
         rc = fn(arg, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), 0 if maxdeg is None else int(maxdeg), C.byref(rank), C.byref(certain))
@@ -2366,7 +2345,7 @@ def wiedemann_det(A, K=8, seed=0, tries=3):
     by preconditioned Wiedemann, without elimination or fill-in.  A is a CSR (spasm_amd_wiedemann_det), an SpMV operator
     (spasm_amd_spmv_wiedemann_det) or a DeviceCSR (spasm_amd_dcsr_wiedemann_det).  status 1: det is certain; status 0: undecided
     after `tries` tries with the seeds seed, seed + 1, .. (det is 0 then and says nothing)."""
-    who, fn, arg = _precond_target(A, "wiedemann_det")
+    who, fn, arg, _ = _family_target(A, "wiedemann_det")
     det, status = C.c_int32(0), C.c_int32(0)
     with _quiet(True):
         rc = fn(arg, int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), C.byref(det), C.byref(status))

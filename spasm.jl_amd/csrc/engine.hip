@@ -10796,6 +10796,7 @@ SPASM_API void spasm_amd_charpoly_split_stats(i64 *out)
 // product, Berlekamp-Massey on the device, and the lcm over the K projections on the host.
 // ------------------------------------------------------------------------------------------------
 #include "krylov.hpp"
+#include "precond.hpp"
 
 namespace {
 
@@ -10834,25 +10835,43 @@ int spmv_step_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, 
     return launches;
 }
 
+// The operator B of a projected sequence.  No diagonal: B = A, fwd the view of a square matrix.  dl alone: B = D A, dl the n words
+// of D.  tr: B = E A^T D2 A, fwd and tr the two views of the n x m matrix, dl = D2 (n words), dr = E (m words).
+struct SeqOperator {
+    const SpmvView *fwd = nullptr, *tr = nullptr;
+    const int *dl = nullptr, *dr = nullptr;
+    int dim() const { return tr ? fwd->cols : fwd->rows; }
+};
+
+// One step is one launch set (KrylovEpi, or DiagEpi with dl) whose iterates ping-pong in W.w0 / W.w1, or with tr two sets: W.w0
+// holds the n x KW intermediate and W.w1 the m x KW iterate.
 template <bool SMALL, int KW>
-int krylov_launch(const SpmvView &V, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
-                  hipStream_t s)
+int sequence_launch(const SeqOperator &op, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
+                    hipStream_t s)
 {
-    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, dim = op.dim();
     int launches = 0;
     HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
-    if (n > 0) {
-        hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)n * KW, cap), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+    if (dim > 0) {
+        hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
         launches++;
     }
     const int *X = X0;
     i64d ldx = (i64d)ldx0;
     int *Y = W.w0.p;
-    for (i64 i = 1; i < len && n > 0; i++) {
-        launches += spmv_step_launch<SMALL, KW>(V, F, kc, X, ldx, Y, (i64d)KW, KrylovEpi{U, (i64d)ldu, W.acc.p + i * KW}, cap, s);
-        X = Y;
+    for (i64 i = 1; i < len && dim > 0; i++) {
+        long long *acc = W.acc.p + i * KW;
+        if (op.tr) {
+            launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, W.w0.p, (i64d)KW, DiagEpi{op.dl, nullptr, 0, nullptr}, cap, s);
+            launches += spmv_step_launch<SMALL, KW>(*op.tr, F, kc, W.w0.p, (i64d)KW, W.w1.p, (i64d)KW, DiagEpi{op.dr, U, (i64d)ldu, acc}, cap, s);
+            X = W.w1.p;
+        } else {
+            if (op.dl) launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, Y, (i64d)KW, DiagEpi{op.dl, U, (i64d)ldu, acc}, cap, s);
+            else launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, Y, (i64d)KW, KrylovEpi{U, (i64d)ldu, acc}, cap, s);
+            X = Y;
+            Y = Y == W.w0.p ? W.w1.p : W.w0.p;
+        }
         ldx = KW;
-        Y = Y == W.w0.p ? W.w1.p : W.w0.p;
     }
     const i64 total = len * kc;
     hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, kc, KW, F, W.acc.p, S);
@@ -10860,20 +10879,19 @@ int krylov_launch(const SpmvView &V, const ZpField &F, int kc, i64 len, const in
     return launches + 1;
 }
 
-// S[i * K + c] = sum_r U[r, c] * (A^i V)[r, c], 0 <= i < len, on device arrays, enqueued on s; no host synchronization.  V is the
-// view of a square matrix; 1 <= K <= 64, len >= 1.  Returns the launches.
-int krylov_run(const SpmvView &V, const ZpField &F, int K, i64 len, const int *U, i64 ldu, const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
+// S[i * K + c] = sum_r U[r, c] * (B^i X)[r, c], 0 <= i < len, on device arrays, enqueued on s; no host synchronization.
+// 1 <= K <= 64, len >= 1.  Returns the launches.
+int sequence_run(const SeqOperator &op, const ZpField &F, int K, i64 len, const int *U, i64 ldu, const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
 {
     const int kw = spmv_kw(K), cap = step_grid_cap();
-    const size_t words = (size_t)V.rows * kw;
     if (len > 1) {
-        W.w0.ensure(words);
-        if (len > 2) W.w1.ensure(words);
+        W.w0.ensure((size_t)op.fwd->rows * kw);
+        if (op.tr || len > 2) W.w1.ensure((size_t)op.dim() * kw);
     }
     W.acc.ensure((size_t)len * kw);
     return dispatch_kw(kw, [&](auto KW) {
-        return F.small ? krylov_launch<true, KW()>(V, F, K, len, U, ldu, X, ldx, W, S, cap, s)
-                       : krylov_launch<false, KW()>(V, F, K, len, U, ldu, X, ldx, W, S, cap, s);
+        return F.small ? sequence_launch<true, KW()>(op, F, K, len, U, ldu, X, ldx, W, S, cap, s)
+                       : sequence_launch<false, KW()>(op, F, K, len, U, ldu, X, ldx, W, S, cap, s);
     });
 }
 
@@ -10902,6 +10920,11 @@ int bm_class(int len, int where)
         throw EngineError(msg);
     }
     return where == 2 || !fits ? 2 : 1;
+}
+
+void check_prime(i64 prime)
+{
+    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
 }
 
 void bm_check_len(const ZpField &F, i64 len)
@@ -10946,7 +10969,7 @@ void berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime
 {
     minpoly_stats_reset();
     if (count < 0) throw EngineError("count < 0");
-    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    check_prime(prime);
     const ZpField F = zp_field_make(prime);
     bm_check_len(F, len);
     if (lds < count) throw EngineError("lds < count");
@@ -10983,15 +11006,29 @@ void berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime
 // ---- polynomials over GF(p) on the host, as residues in [0, p), low degree first, no zero leading word (the zero polynomial is empty)
 typedef std::vector<uint64_t> HPoly;
 
+// any int32 -> its residue in [0, p); a residue in [0, p) -> the balanced one
+inline uint64_t hresidue(int x, uint64_t p)
+{
+    const int64_t r = (int64_t)x % (int64_t)p;
+    return (uint64_t)(r < 0 ? r + (int64_t)p : r);
+}
+
+inline int hbalanced(uint64_t w, uint64_t p) { return (int)(w > p / 2 ? (int64_t)w - (int64_t)p : (int64_t)w); }
+
 HPoly hpoly_load(const int *f, int len, uint64_t p)
 {
     HPoly a((size_t)len);
-    for (int k = 0; k < len; k++) {
-        int64_t r = (int64_t)f[k] % (int64_t)p;
-        a[(size_t)k] = (uint64_t)(r < 0 ? r + (int64_t)p : r);
-    }
+    for (int k = 0; k < len; k++) a[(size_t)k] = hresidue(f[k], p);
     while (!a.empty() && a.back() == 0) a.pop_back();
     return a;
+}
+
+// the multiplicity of x in f (not zero: its leading word ends the loop)
+size_t hpoly_valuation(const HPoly &f)
+{
+    size_t e = 0;
+    while (f[e] == 0) e++;
+    return e;
 }
 
 uint64_t hinv(uint64_t a, uint64_t p)
@@ -11053,7 +11090,7 @@ HPoly hpoly_lcm(HPoly a, HPoly b, uint64_t p)
 
 void hpoly_store(const HPoly &a, uint64_t p, int *out)
 {
-    for (size_t k = 0; k < a.size(); k++) out[k] = (int)(a[k] > p / 2 ? (int64_t)a[k] - (int64_t)p : (int64_t)a[k]);
+    for (size_t k = 0; k < a.size(); k++) out[k] = hbalanced(a[k], p);
 }
 
 void poly_lcm(int count, const int *len, const spasm_ZZp *const *f, i64 prime, spasm_ZZp *out, int *outlen)
@@ -11061,7 +11098,7 @@ void poly_lcm(int count, const int *len, const spasm_ZZp *const *f, i64 prime, s
     if (count < 0) throw EngineError("count < 0");
     if (!out || !outlen) throw EngineError("NULL array");
     if (count > 0 && (!len || !f)) throw EngineError("NULL array");
-    if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+    check_prime(prime);
     const uint64_t p = (uint64_t)prime;
     std::vector<HPoly> poly;
     i64 total = 0;
@@ -11108,8 +11145,7 @@ void minpoly_vectors(int n, int K, uint64_t seed, i64 prime, int *U, int *V)
         int *dst = t ? V : U;
         if (!dst) continue;
         for (i64 e = 0; e < (i64)n * K; e++) {
-            const uint64_t w = minpoly_mix(seed + 0x9E3779B97F4A7C15ULL * (2 * (uint64_t)e + (uint64_t)t + 1)) % p;
-            dst[e] = (int)(w > p / 2 ? (int64_t)w - (int64_t)p : (int64_t)w);
+            dst[e] = hbalanced(minpoly_mix(seed + 0x9E3779B97F4A7C15ULL * (2 * (uint64_t)e + (uint64_t)t + 1)) % p, p);
         }
     }
 }
@@ -11120,14 +11156,59 @@ int minpoly_K(int K)
     return K == 0 ? 8 : K;
 }
 
+// the degree bound of a caller: maxdeg where it lies in 1 .. n, else n
+int degree_bound(int maxdeg, int n) { return (maxdeg <= 0 || maxdeg > n) ? n : maxdeg; }
+
+// 2 * md terms determine a recurrence of degree <= md; two more terms show a degree above md as L > md (see the header)
+int sequence_terms(int md, int n) { return md < n ? 2 * md + 2 : 2 * n; }
+
+// The stage every Wiedemann driver shares: the projected sequence of len terms, Berlekamp-Massey on its K columns, and the K
+// polynomials on the host.  The buffers are kept from one try to the next.
+struct SeqRecurrences {
+    DevBuf<int> dS, d_coef, d_deg, gwork;
+    KrylovWork W;
+    SpgEvents ev;
+    std::vector<int> deg, coef; // the K degrees; K rows of ldh words
+    size_t ldh = 0;
+    struct Run {
+        int launches, bm_class; // the launches include Berlekamp-Massey's one
+        i64 sequence_us, bm_us;
+    };
+
+    // U and X are packed n x K device arrays.  Synchronizes s.  The polynomials come back in one copy of K rows by
+    // (largest degree + 1) words.
+    Run run(const SeqOperator &op, const ZpField &F, int K, int len, const int *U, const int *X, hipStream_t s)
+    {
+        const i64 ldc = (i64)len + 1;
+        const int cls = bm_class(len, 0);
+        dS.ensure((size_t)len * K);
+        d_coef.ensure((size_t)K * (size_t)ldc);
+        d_deg.ensure((size_t)K);
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        const int launches = sequence_run(op, F, K, len, U, K, X, K, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        bm_device(F, K, len, dS.p, K, cls, d_coef.p, ldc, d_deg.p, gwork, s);
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        deg.resize((size_t)K);
+        HIPCHK(hipMemcpyAsync(deg.data(), d_deg.p, deg.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        ldh = (size_t)*std::max_element(deg.begin(), deg.end()) + 1;
+        coef.resize((size_t)K * ldh);
+        HIPCHK(hipMemcpy2D(coef.data(), ldh * sizeof(int), d_coef.p, (size_t)ldc * sizeof(int), ldh * sizeof(int), (size_t)K, hipMemcpyDeviceToHost));
+        return {launches + 1, cls, (i64)(ev.ms(0, 1) * 1000.0), (i64)(ev.ms(1, 2) * 1000.0)};
+    }
+
+    // the polynomial of projection c: monic, of degree deg[c]
+    HPoly poly(int c, uint64_t p) const { return hpoly_load(coef.data() + (size_t)c * ldh, deg[(size_t)c] + 1, p); }
+};
+
 // The lcm of the minimal polynomials of the K projected sequences of the square matrix behind view V.
 void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *X, spasm_ZZp *coef, int *deg)
 {
-    const int n = V.rows;
-    const int md = (maxdeg <= 0 || maxdeg > n) ? n : maxdeg;
+    const int n = V.rows, md = degree_bound(maxdeg, n);
+    const uint64_t p = (uint64_t)F.p;
     if (n >= (1 << 24)) throw EngineError("minimal polynomial limited to n < 2^24");
-    // 2 * md terms determine a recurrence of degree <= md; two more terms show a degree above md as L > md (see the header)
-    const int len = md < n ? 2 * md + 2 : 2 * n;
+    const int len = sequence_terms(md, n);
     bm_check_len(F, len);
     hipStream_t s = nullptr;
     std::vector<int> hu, hv;
@@ -11138,62 +11219,40 @@ void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int 
         U = hu.data();
         X = hv.data();
     }
-    DevBuf<int> dU, dV, dS, d_coef, d_deg, gwork;
-    KrylovWork W;
+    DevBuf<int> dU, dV;
     const size_t nk = (size_t)n * K;
     dU.alloc(nk);
     dV.alloc(nk);
-    dS.alloc((size_t)len * K);
-    const i64 ldc = (i64)len + 1;
-    d_coef.alloc((size_t)K * (size_t)ldc);
-    d_deg.alloc((size_t)K);
     HIPCHK(hipMemcpyAsync(dU.p, U, nk * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(dV.p, X, nk * sizeof(int), hipMemcpyHostToDevice, s));
-    SpgEvents ev;
-    HIPCHK(hipEventRecord(ev.e[0], s));
-    const int launches = krylov_run(V, F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
-    HIPCHK(hipEventRecord(ev.e[1], s));
-    const int cls = bm_class(len, 0);
-    bm_device(F, K, len, dS.p, K, cls, d_coef.p, ldc, d_deg.p, gwork, s);
-    HIPCHK(hipEventRecord(ev.e[2], s));
-    std::vector<int> hd((size_t)K);
-    HIPCHK(hipMemcpyAsync(hd.data(), d_deg.p, hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+    SeqRecurrences R;
+    const SeqRecurrences::Run run = R.run({&V}, F, K, len, dU.p, dV.p, s);
     i64 *st = g_minpoly_stats;
     st[0] = n;
     st[1] = K;
     st[2] = len - 1;
-    st[3] = launches + 1;
-    st[4] = cls;
-    st[6] = (i64)(ev.ms(0, 1) * 1000.0);
-    st[7] = (i64)(ev.ms(1, 2) * 1000.0);
+    st[3] = run.launches;
+    st[4] = run.bm_class;
+    st[6] = run.sequence_us;
+    st[7] = run.bm_us;
     for (int c = 0; c < K; c++)
-        if (hd[(size_t)c] > md) {
+        if (R.deg[(size_t)c] > md) {
             char msg[128];
-            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d, maxdeg %d)", c, hd[(size_t)c], md);
+            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d, maxdeg %d)", c, R.deg[(size_t)c], md);
             throw EngineError(msg);
         }
     HPoly r(1, 1);
-    std::vector<int> hc((size_t)md + 1);
     for (int c = 0; c < K; c++) {
-        const int d = hd[(size_t)c];
-        HIPCHK(hipMemcpy(hc.data(), d_coef.p + (size_t)c * (size_t)ldc, ((size_t)d + 1) * sizeof(int), hipMemcpyDeviceToHost));
-        r = hpoly_lcm(r, hpoly_load(hc.data(), d + 1, (uint64_t)F.p), (uint64_t)F.p);
+        r = hpoly_lcm(r, R.poly(c, p), p);
         if ((i64)r.size() - 1 > md) throw EngineError("degree bound too small (the lcm of the projections exceeds maxdeg)");
     }
     st[5] = (i64)r.size() - 1;
-    hpoly_store(r, (uint64_t)F.p, coef);
+    hpoly_store(r, p, coef);
     *deg = (int)r.size() - 1;
 }
 
-// a view of the resident entries of a square matrix (n > 0): the row pointers serve as starts, the lengths are their differences
-void dcsr_square_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->n, D->p.p, D->ent.p, s); }
-
-void minpoly_check_out(const spasm_ZZp *U, const spasm_ZZp *X, const spasm_ZZp *coef, const int *deg)
-{
-    if (!coef || !deg) throw EngineError("NULL array");
-    if ((U == nullptr) != (X == nullptr)) throw EngineError("U and V must both be given or both be NULL");
-}
+// the view of a resident matrix (n, m > 0): the row pointers serve as starts, the lengths are their differences
+void dcsr_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->m, D->p.p, D->ent.p, s); }
 
 void minpoly_square(int n, int m)
 {
@@ -11201,6 +11260,77 @@ void minpoly_square(int n, int m)
     char msg[96];
     snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
     throw EngineError(msg);
+}
+
+// The matrix of a family entry: a host CSR, an SpMV operator or a resident matrix.  check() reads n, m and F without a device;
+// views() takes the device (put back when this goes) and builds the views that are asked for.  It owns what it had to make:
+// the temporary operator of a CSR, the transpose of a resident matrix, the views of a resident matrix.
+struct Operand {
+    std::unique_ptr<DeviceGuard> guard; // first: whatever lives on the device goes before it
+    const spasm_csr *A = nullptr;
+    spasm_amd_spmv *op = nullptr;
+    const spasm_amd_dcsr *D = nullptr;
+    const char *who = nullptr; // the entry's name, for the messages of the temporary operator
+    enum { CSR, SPMV, DCSR } kind;
+    std::unique_ptr<spasm_amd_spmv> tmp;
+    std::unique_ptr<spasm_amd_dcsr> T;
+    SpmvView vf, vt;
+    int n = 0, m = 0;
+    ZpField F;
+    const SpmvView *fwd = nullptr, *tr = nullptr;
+
+    Operand(const spasm_csr *A_, const char *who_) : A(A_), who(who_), kind(CSR) {}
+    Operand(spasm_amd_spmv *op_) : op(op_), kind(SPMV) {}
+    Operand(const spasm_amd_dcsr *D_) : D(D_), kind(DCSR) {}
+
+    void check()
+    {
+        if (kind == CSR) {
+            if (const char *bad = batch_check(A)) throw EngineError(bad);
+            n = A->n, m = A->m, F = zp_field_make(A->field->p);
+        } else if (kind == SPMV) {
+            if (!op) throw EngineError("NULL operator");
+            n = op->A.n, m = op->A.m, F = op->F;
+        } else {
+            if (!D) throw EngineError("NULL matrix");
+            n = D->n, m = D->m, F = D->F;
+        }
+    }
+
+    void views(bool forward, bool transposed)
+    {
+        if (kind == CSR) {
+            guard.reset(new DeviceGuard());
+            tmp.reset(spmv_create(A, who));
+            op = tmp.get();
+        } else if (kind == SPMV) {
+            guard.reset(new DeviceGuard(op));
+        } else {
+            guard.reset(new DeviceGuard(D));
+            // the transpose stays on the device for the length of the call
+            if (transposed) T.reset(dcsr_transpose(D, "transpose"));
+            if (forward) dcsr_view(D, vf, nullptr);
+            if (transposed) dcsr_view(T.get(), vt, nullptr);
+            fwd = &vf, tr = &vt;
+            return;
+        }
+        if (transposed) op->build_transpose();
+        fwd = &op->fwd, tr = &op->tr;
+    }
+};
+
+int minpoly_entry(Operand &&o, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *X, spasm_ZZp *coef, int *deg)
+{
+    minpoly_stats_reset();
+    o.check();
+    minpoly_square(o.n, o.m);
+    K = minpoly_K(K);
+    if (!coef || !deg) throw EngineError("NULL array");
+    if ((U == nullptr) != (X == nullptr)) throw EngineError("U and V must both be given or both be NULL");
+    if (o.n == 0) { coef[0] = 1; *deg = 0; return 0; }
+    o.views(true, false);
+    minpoly_run(*o.fwd, o.F, K, seed, maxdeg, U, X, coef, deg);
+    return 0;
 }
 
 } // namespace
@@ -11230,7 +11360,7 @@ SPASM_API int spasm_amd_krylov_sequence(spasm_amd_spmv *op, int trans, int K, in
         }
         SpgEvents ev;
         HIPCHK(hipEventRecord(ev.e[0], s));
-        const int launches = krylov_run(view, op->F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
+        const int launches = sequence_run({&view}, op->F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
         HIPCHK(hipEventRecord(ev.e[1], s));
         std::vector<int> out((size_t)len * kk);
         HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -11256,7 +11386,7 @@ SPASM_API int spasm_amd_krylov_sequence_dev(spasm_amd_spmv *op, int trans, int K
         DeviceGuard g(op);
         if (trans) op->build_transpose();
         hipStream_t s = (hipStream_t)stream;
-        const int launches = krylov_run(trans ? op->tr : op->fwd, op->F, K, len, U, ldu, V, ldv, op->kry, S, s);
+        const int launches = sequence_run({trans ? &op->tr : &op->fwd}, op->F, K, len, U, ldu, V, ldv, op->kry, S, s);
         if (!stream) HIPCHK(hipStreamSynchronize(s));
         i64 *st = g_minpoly_stats;
         st[0] = op->A.n;
@@ -11281,7 +11411,7 @@ SPASM_API int spasm_amd_minpoly_vectors(int n, int K, uint64_t seed, i64 prime, 
 {
     return abi_call("spasm_amd_minpoly_vectors", -1, [&] {
         if (n < 0 || K < 1 || K > 64) throw EngineError("bad arguments (n >= 0, 1 <= K <= 64)");
-        if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+        check_prime(prime);
         minpoly_vectors(n, K, seed, prime, U, V);
         return 0;
     });
@@ -11289,50 +11419,17 @@ SPASM_API int spasm_amd_minpoly_vectors(int n, int K, uint64_t seed, i64 prime, 
 
 SPASM_API int spasm_amd_minpoly(const struct spasm_csr *A, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
 {
-    return abi_call("spasm_amd_minpoly", -1, [&] {
-        DeviceGuard g;
-        minpoly_stats_reset();
-        if (const char *bad = batch_check(A)) throw EngineError(bad);
-        minpoly_square(A->n, A->m);
-        K = minpoly_K(K);
-        minpoly_check_out(U, V, coef, deg);
-        if (A->n == 0) { coef[0] = 1; *deg = 0; return 0; }
-        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_minpoly"));
-        minpoly_run(op->fwd, op->F, K, seed, maxdeg, U, V, coef, deg);
-        return 0;
-    });
+    return abi_call("spasm_amd_minpoly", -1, [&] { return minpoly_entry(Operand(A, "spasm_amd_minpoly"), K, seed, maxdeg, U, V, coef, deg); });
 }
 
 SPASM_API int spasm_amd_spmv_minpoly(spasm_amd_spmv *op, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
 {
-    return abi_call("spasm_amd_spmv_minpoly", -1, [&] {
-        minpoly_stats_reset();
-        if (!op) throw EngineError("NULL operator");
-        DeviceGuard g(op);
-        minpoly_square(op->A.n, op->A.m);
-        K = minpoly_K(K);
-        minpoly_check_out(U, V, coef, deg);
-        if (op->A.n == 0) { coef[0] = 1; *deg = 0; return 0; }
-        minpoly_run(op->fwd, op->F, K, seed, maxdeg, U, V, coef, deg);
-        return 0;
-    });
+    return abi_call("spasm_amd_spmv_minpoly", -1, [&] { return minpoly_entry(Operand(op), K, seed, maxdeg, U, V, coef, deg); });
 }
 
 SPASM_API int spasm_amd_dcsr_minpoly(const spasm_amd_dcsr *D, int K, uint64_t seed, int maxdeg, const spasm_ZZp *U, const spasm_ZZp *V, spasm_ZZp *coef, int *deg)
 {
-    return abi_call("spasm_amd_dcsr_minpoly", -1, [&] {
-        minpoly_stats_reset();
-        if (!D) throw EngineError("NULL matrix");
-        DeviceGuard g(D);
-        minpoly_square(D->n, D->m);
-        K = minpoly_K(K);
-        minpoly_check_out(U, V, coef, deg);
-        if (D->n == 0) { coef[0] = 1; *deg = 0; return 0; }
-        SpmvView view;
-        dcsr_square_view(D, view, nullptr);
-        minpoly_run(view, D->F, K, seed, maxdeg, U, V, coef, deg);
-        return 0;
-    });
+    return abi_call("spasm_amd_dcsr_minpoly", -1, [&] { return minpoly_entry(Operand(D), K, seed, maxdeg, U, V, coef, deg); });
 }
 
 SPASM_API void spasm_amd_minpoly_stats(i64 *out)
@@ -11403,14 +11500,6 @@ int horner_run(const SpmvView &V, const ZpField &F, int K, int rows, const int *
     });
 }
 
-inline uint64_t wied_residue(int x, uint64_t p)
-{
-    const int64_t r = (int64_t)x % (int64_t)p;
-    return (uint64_t)(r < 0 ? r + (int64_t)p : r);
-}
-
-inline int wied_balanced(uint64_t w, uint64_t p) { return (int)(w > p / 2 ? (int64_t)w - (int64_t)p : (int64_t)w); }
-
 // the table of spasm_amd_poly_apply in W.htab: row s holds the coefficients of degree D - s, D = max(deg); zeros above a
 // column's degree.  Returns D (-1: every polynomial is zero).
 int poly_table(const ZpField &F, int K, const int *deg, const spasm_ZZp *coef, i64 ldc, std::vector<int> &tab)
@@ -11421,7 +11510,7 @@ int poly_table(const ZpField &F, int K, const int *deg, const spasm_ZZp *coef, i
     tab.assign((size_t)(D + 1) * kw, 0);
     const uint64_t p = (uint64_t)F.p;
     for (int c = 0; c < K; c++)
-        for (int j = 0; j <= deg[c]; j++) tab[(size_t)(D - j) * kw + c] = wied_balanced(wied_residue(coef[(i64)c * ldc + j], p), p);
+        for (int j = 0; j <= deg[c]; j++) tab[(size_t)(D - j) * kw + c] = hbalanced(hresidue(coef[(i64)c * ldc + j], p), p);
     return D;
 }
 
@@ -11506,24 +11595,20 @@ void wied_empty(int K, int *status)
 void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg, const spasm_ZZp *U,
               spasm_ZZp *X, i64 ldx, int *status)
 {
-    const int n = V.rows;
+    const int n = V.rows, md = degree_bound(maxdeg, n), len = sequence_terms(md, n);
     const uint64_t p = (uint64_t)F.p;
-    const int md = (maxdeg <= 0 || maxdeg > n) ? n : maxdeg;
-    // 2 * md terms determine a recurrence of degree <= md; two more terms show a degree above md as L > md (see the header)
-    const int len = md < n ? 2 * md + 2 : 2 * n;
     bm_check_len(F, len);
     const int ntries = U ? 1 : (tries <= 0 ? 3 : tries);
-    const i64 ldc = (i64)len + 1;
-    const int cls = bm_class(len, 0);
     hipStream_t s = nullptr;
     std::vector<int> outX((size_t)n * K, 0), outS((size_t)K, 0), act((size_t)K);
     for (int c = 0; c < K; c++) act[(size_t)c] = c;
-    std::vector<int> hu, pu, pb, hx, hc((size_t)md + 1), hd, tab;
+    std::vector<int> hu, pu, pb, hx, tab;
     std::vector<long long> hcnt;
     std::vector<char> regular;
-    DevBuf<int> dU, dB, dS, d_coef, d_deg, gwork, dX, dR, dT;
+    DevBuf<int> dU, dB, dX, dR, dT;
     DevBuf<long long> dcnt;
-    KrylovWork W;
+    SeqRecurrences R;
+    KrylovWork &W = R.W;
     SpgEvents ev;
     i64 *st = g_wied_stats;
     st[0] = n;
@@ -11549,27 +11634,17 @@ void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i6
         dB.ensure(nk);
         dX.ensure(nk);
         dR.ensure((size_t)n * kw);
-        dS.ensure((size_t)len * ka);
-        d_coef.ensure((size_t)ka * (size_t)ldc);
-        d_deg.ensure((size_t)ka);
         dcnt.ensure((size_t)2 * kw);
         HIPCHK(hipMemcpyAsync(dU.p, pu.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(dB.p, pb.data(), nk * sizeof(int), hipMemcpyHostToDevice, s));
-        HIPCHK(hipEventRecord(ev.e[0], s));
-        int launches = krylov_run(V, F, ka, len, dU.p, ka, dB.p, ka, W, dS.p, s);
-        bm_device(F, ka, len, dS.p, ka, cls, d_coef.p, ldc, d_deg.p, gwork, s);
-        launches++;
-        HIPCHK(hipEventRecord(ev.e[1], s));
-        hd.resize((size_t)ka);
-        HIPCHK(hipMemcpyAsync(hd.data(), d_deg.p, hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
+        const SeqRecurrences::Run run = R.run({&V}, F, ka, len, dU.p, dB.p, s);
         st[2] = t + 1;
         st[3] += len - 1;
-        st[4] += launches;
-        st[8] += (i64)(ev.ms(0, 1) * 1000.0);
+        st[4] += run.launches;
+        st[8] += run.sequence_us + run.bm_us;
         int Lmax = 0;
         for (int a = 0; a < ka; a++) {
-            const int L = hd[(size_t)a];
+            const int L = R.deg[(size_t)a];
             if (L > md) {
                 char msg[128];
                 snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d, maxdeg %d)", act[(size_t)a], L, md);
@@ -11584,25 +11659,23 @@ void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i6
         tab.assign((size_t)(rows + 1) * kw, 0);
         regular.assign((size_t)ka, 0);
         for (int a = 0; a < ka; a++) {
-            const int L = hd[(size_t)a];
-            HIPCHK(hipMemcpy(hc.data(), d_coef.p + (size_t)a * (size_t)ldc, ((size_t)L + 1) * sizeof(int), hipMemcpyDeviceToHost));
-            const uint64_t f0 = wied_residue(hc[0], p);
-            const uint64_t scale = f0 ? (p - hinv(f0, p)) % p : 1;
+            const HPoly f = R.poly(a, p);
+            const int L = (int)f.size() - 1;
+            const uint64_t f0 = f[0], scale = f0 ? (p - hinv(f0, p)) % p : 1;
             regular[(size_t)a] = f0 != 0;
-            for (int j = 0; j < L; j++)
-                tab[(size_t)(rows - 1 - j) * kw + a] = wied_balanced(wied_residue(hc[(size_t)j + 1], p) * scale % p, p);
+            for (int j = 0; j < L; j++) tab[(size_t)(rows - 1 - j) * kw + a] = hbalanced(f[(size_t)j + 1] * scale % p, p);
             tab[(size_t)rows * kw + a] = f0 ? -1 : 0;
         }
         dT.ensure(tab.size());
         HIPCHK(hipMemcpyAsync(dT.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)2 * kw * sizeof(long long), s));
-        HIPCHK(hipEventRecord(ev.e[2], s));
-        launches = 0;
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        int launches = 0;
         if (rows == 0) HIPCHK(hipMemsetAsync(dX.p, 0, nk * sizeof(int), s));
         else launches += horner_run(V, F, ka, rows, dT.p, dB.p, ka, nullptr, 0, dX.p, ka, W, dcnt.p, s);
         // the certificate: R <- op(A) X + r B, with the non-zero counts of X (above) and of R
         launches += horner_run(V, F, ka, 1, dT.p + (size_t)rows * kw, dB.p, ka, dX.p, ka, dR.p, kw, W, dcnt.p + kw, s);
-        HIPCHK(hipEventRecord(ev.e[3], s));
+        HIPCHK(hipEventRecord(ev.e[1], s));
         hcnt.resize((size_t)2 * kw);
         hx.resize(nk);
         HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt.p, hcnt.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
@@ -11610,7 +11683,7 @@ void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i6
         HIPCHK(hipStreamSynchronize(s));
         st[3] += std::max(rows - 1, 0) + 1;
         st[4] += launches;
-        st[9] += (i64)(ev.ms(2, 3) * 1000.0);
+        st[9] += (i64)(ev.ms(0, 1) * 1000.0);
         std::vector<int> left;
         for (int a = 0; a < ka; a++) {
             const int c = act[(size_t)a];
@@ -11630,6 +11703,18 @@ void wied_run(const SpmvView &V, const ZpField &F, int K, const spasm_ZZp *B, i6
     }
     for (int r = 0; r < n; r++) memcpy(X + (i64)r * ldx, outX.data() + (size_t)r * K, (size_t)K * sizeof(int));
     memcpy(status, outS.data(), (size_t)K * sizeof(int));
+}
+
+int wied_entry(Operand &&o, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg, const spasm_ZZp *U, spasm_ZZp *X, i64 ldx,
+               int *status)
+{
+    wied_stats_reset();
+    o.check();
+    wied_check(o.n, o.m, trans, K, B, ldb, X, ldx, status);
+    if (o.n == 0) { wied_empty(K, status); return 0; }
+    o.views(!trans, trans != 0); // x A = b is A^T x = b
+    wied_run(trans ? *o.tr : *o.fwd, o.F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
+    return 0;
 }
 
 } // namespace
@@ -11688,51 +11773,20 @@ SPASM_API int spasm_amd_poly_apply_dev(spasm_amd_spmv *op, int trans, int K, con
 SPASM_API int spasm_amd_wiedemann_solve(const struct spasm_csr *A, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
                                         const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
 {
-    return abi_call("spasm_amd_wiedemann_solve", -1, [&] {
-        DeviceGuard g;
-        wied_stats_reset();
-        if (const char *bad = batch_check(A)) throw EngineError(bad);
-        wied_check(A->n, A->m, trans, K, B, ldb, X, ldx, status);
-        if (A->n == 0) { wied_empty(K, status); return 0; }
-        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_solve"));
-        if (trans) op->build_transpose();
-        wied_run(trans ? op->tr : op->fwd, op->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
-        return 0;
-    });
+    return abi_call("spasm_amd_wiedemann_solve", -1,
+                    [&] { return wied_entry(Operand(A, "spasm_amd_wiedemann_solve"), trans, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status); });
 }
 
 SPASM_API int spasm_amd_spmv_wiedemann_solve(spasm_amd_spmv *op, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
                                              const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
 {
-    return abi_call("spasm_amd_spmv_wiedemann_solve", -1, [&] {
-        wied_stats_reset();
-        if (!op) throw EngineError("NULL operator");
-        wied_check(op->A.n, op->A.m, trans, K, B, ldb, X, ldx, status);
-        if (op->A.n == 0) { wied_empty(K, status); return 0; }
-        DeviceGuard g(op);
-        if (trans) op->build_transpose();
-        wied_run(trans ? op->tr : op->fwd, op->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
-        return 0;
-    });
+    return abi_call("spasm_amd_spmv_wiedemann_solve", -1, [&] { return wied_entry(Operand(op), trans, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status); });
 }
 
 SPASM_API int spasm_amd_dcsr_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, int maxdeg,
                                              const spasm_ZZp *U, spasm_ZZp *X, i64 ldx, int *status)
 {
-    return abi_call("spasm_amd_dcsr_wiedemann_solve", -1, [&] {
-        wied_stats_reset();
-        if (!D) throw EngineError("NULL matrix");
-        wied_check(D->n, D->m, trans, K, B, ldb, X, ldx, status);
-        if (D->n == 0) { wied_empty(K, status); return 0; }
-        DeviceGuard g(D);
-        // x A = b is A^T x = b: the transpose stays on the device for the length of the call
-        std::unique_ptr<spasm_amd_dcsr> T;
-        if (trans) T.reset(dcsr_transpose(D, "transpose"));
-        SpmvView view;
-        dcsr_square_view(trans ? T.get() : D, view, nullptr);
-        wied_run(view, D->F, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status);
-        return 0;
-    });
+    return abi_call("spasm_amd_dcsr_wiedemann_solve", -1, [&] { return wied_entry(Operand(D), trans, K, B, ldb, seed, tries, maxdeg, U, X, ldx, status); });
 }
 
 SPASM_API void spasm_amd_wiedemann_stats(i64 *out)
@@ -11746,8 +11800,6 @@ SPASM_API void spasm_amd_wiedemann_stats(i64 *out)
 // Rank and determinant without fill-in by preconditioned Wiedemann (precond.hpp): the projected sequences of D A and of
 // E A^T D2 A, Berlekamp-Massey on the device, the lcm over the K projections and the factor x^e on the host.
 // ------------------------------------------------------------------------------------------------
-#include "precond.hpp"
-
 namespace {
 
 // n, m, K, tries used, products with A, launches, degree of f, multiplicity of x in f, device us of the sequences, device us of
@@ -11786,73 +11838,21 @@ void precond_diagonal(int len, uint64_t seed, int which, i64 prime, int *d)
         } while (x >= N);
         uint64_t w = 1 + x;
         if (which == 1) w = w * w % p;
-        d[i] = wied_balanced(w, p);
+        d[i] = hbalanced(w, p);
     }
 }
 
-// The sequence of the preconditioned operator on device arrays.  Tr == NULL: D A on the view Fw of a square matrix, dl its
-// diagonal, the iterates ping-pong in W.w0 / W.w1.  Else E A^T D2 A: Fw and Tr are the two views of the n x m matrix, dl = D2
-// (n words), dr = E (m words), W.w0 holds the n x KW intermediate and W.w1 the m x KW iterate.
-template <bool SMALL, int KW>
-int precond_launch(const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int kc, i64 len, const int *dl, const int *dr, const int *U, i64 ldu,
-                   const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap, hipStream_t s)
-{
-    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, dim = Tr ? Fw.cols : Fw.rows;
-    int launches = 0;
-    HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
-    hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
-    launches++;
-    const int *X = X0;
-    i64d ldx = (i64d)ldx0;
-    int *Y = W.w0.p;
-    for (i64 i = 1; i < len; i++) {
-        long long *acc = W.acc.p + i * KW;
-        if (Tr) {
-            launches += spmv_step_launch<SMALL, KW>(Fw, F, kc, X, ldx, W.w0.p, (i64d)KW, DiagEpi{dl, nullptr, 0, nullptr}, cap, s);
-            launches += spmv_step_launch<SMALL, KW>(*Tr, F, kc, W.w0.p, (i64d)KW, W.w1.p, (i64d)KW, DiagEpi{dr, U, (i64d)ldu, acc}, cap, s);
-            X = W.w1.p;
-        } else {
-            launches += spmv_step_launch<SMALL, KW>(Fw, F, kc, X, ldx, Y, (i64d)KW, DiagEpi{dl, U, (i64d)ldu, acc}, cap, s);
-            X = Y;
-            Y = Y == W.w0.p ? W.w1.p : W.w0.p;
-        }
-        ldx = KW;
-    }
-    const i64 total = len * kc;
-    hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, kc, KW, F, W.acc.p, S);
-    HIPCHK(hipGetLastError());
-    return launches + 1;
-}
-
-// S[i * K + c] = sum_r U[r, c] * (B^i V)[r, c], 0 <= i < len, B = D A (Tr == NULL) or E A^T D2 A, on device arrays, enqueued on
-// s; no host synchronization.  Both dimensions of the matrix are positive, 1 <= K <= 64, len >= 1.  Returns the launches.
-int precond_run(const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int K, i64 len, const int *dl, const int *dr, const int *U, i64 ldu,
-                const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
-{
-    const int kw = spmv_kw(K), cap = step_grid_cap();
-    if (len > 1) {
-        W.w0.ensure((size_t)Fw.rows * kw);
-        if (Tr) W.w1.ensure((size_t)Fw.cols * kw);
-        else if (len > 2) W.w1.ensure((size_t)Fw.rows * kw);
-    }
-    W.acc.ensure((size_t)len * kw);
-    return dispatch_kw(kw, [&](auto KW) {
-        return F.small ? precond_launch<true, KW()>(Fw, Tr, F, K, len, dl, dr, U, ldu, X, ldx, W, S, cap, s)
-                       : precond_launch<false, KW()>(Fw, Tr, F, K, len, dl, dr, U, ldu, X, ldx, W, S, cap, s);
-    });
-}
-
-// What one try of rank or determinant leaves on the host: the lcm f of the K Berlekamp-Massey polynomials.
+// what the tries of rank or determinant keep from one to the next
 struct PrecondTry {
-    DevBuf<int> dU, dV, dl, dr, dS, d_coef, d_deg, gwork;
-    KrylovWork W;
-    std::vector<int> hu, hv, hd, hc, diag;
-    SpgEvents ev;
+    DevBuf<int> dU, dV, dl, dr;
+    std::vector<int> hu, hv, diag;
+    SeqRecurrences R;
 };
 
 // One try with the seed `seed`: the diagonals and vectors of the seed go up, the sequence of len terms and Berlekamp-Massey run,
-// and the lcm over K comes back.  g (may be NULL) receives the left diagonal as residues in [0, p).  A projection whose
-// polynomial has more than md roots away from 0 is refused, and so is such an lcm.
+// and the lcm over K comes back.  Tr == NULL: D A on the view Fw of a square matrix; else E A^T D2 A on the two views of the
+// n x m matrix.  g (may be NULL) receives the left diagonal as residues in [0, p).  A projection whose polynomial has more than
+// md roots away from 0 is refused, and so is such an lcm.
 HPoly precond_try(PrecondTry &T, const SpmvView &Fw, const SpmvView *Tr, const ZpField &F, int K, uint64_t seed, int len, int md, std::vector<uint64_t> *g)
 {
     const int n = Fw.rows, dim = Tr ? Fw.cols : Fw.rows;
@@ -11872,49 +11872,32 @@ HPoly precond_try(PrecondTry &T, const SpmvView &Fw, const SpmvView *Tr, const Z
     HIPCHK(hipMemcpyAsync(T.dl.p, T.diag.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     if (g) {
         g->resize((size_t)n);
-        for (int i = 0; i < n; i++) (*g)[(size_t)i] = wied_residue(T.diag[(size_t)i], p);
+        for (int i = 0; i < n; i++) (*g)[(size_t)i] = hresidue(T.diag[(size_t)i], p);
     }
     if (Tr) {
         precond_diagonal(dim, seed, 1, F.p, T.diag.data() + n);
         T.dr.ensure((size_t)dim);
         HIPCHK(hipMemcpyAsync(T.dr.p, T.diag.data() + n, (size_t)dim * sizeof(int), hipMemcpyHostToDevice, s));
     }
-    const i64 ldc = (i64)len + 1;
-    T.dS.ensure((size_t)len * K);
-    T.d_coef.ensure((size_t)K * (size_t)ldc);
-    T.d_deg.ensure((size_t)K);
-    HIPCHK(hipEventRecord(T.ev.e[0], s));
-    const int launches = precond_run(Fw, Tr, F, K, len, T.dl.p, T.dr.p, T.dU.p, K, T.dV.p, K, T.W, T.dS.p, s);
-    HIPCHK(hipEventRecord(T.ev.e[1], s));
-    bm_device(F, K, len, T.dS.p, K, bm_class(len, 0), T.d_coef.p, ldc, T.d_deg.p, T.gwork, s);
-    HIPCHK(hipEventRecord(T.ev.e[2], s));
-    T.hd.resize((size_t)K);
-    T.hc.resize((size_t)K * (size_t)ldc);
-    HIPCHK(hipMemcpyAsync(T.hd.data(), T.d_deg.p, T.hd.size() * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(T.hc.data(), T.d_coef.p, T.hc.size() * sizeof(int), hipMemcpyDeviceToHost, s)); // the K polynomials in one copy
-    HIPCHK(hipStreamSynchronize(s));
+    const SeqRecurrences::Run run = T.R.run({&Fw, Tr, T.dl.p, T.dr.p}, F, K, len, T.dU.p, T.dV.p, s);
     i64 *st = g_precond_stats;
     st[3]++;
     st[4] += (i64)(len - 1) * (Tr ? 2 : 1);
-    st[5] += launches + 1;
-    st[8] += (i64)(T.ev.ms(0, 1) * 1000.0);
-    st[9] += (i64)(T.ev.ms(1, 2) * 1000.0);
+    st[5] += run.launches;
+    st[8] += run.sequence_us;
+    st[9] += run.bm_us;
     HPoly r(1, 1);
     for (int c = 0; c < K; c++) {
-        const int d = T.hd[(size_t)c];
-        const HPoly f = hpoly_load(T.hc.data() + (size_t)c * (size_t)ldc, d + 1, p);
-        size_t e = 0;
-        while (f[e] == 0) e++; // f is monic: its leading word ends the loop
+        const HPoly f = T.R.poly(c, p);
+        const size_t e = hpoly_valuation(f);
         if ((i64)f.size() - 1 - (i64)e > md) {
             char msg[160];
-            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d with x^%d, maxdeg %d)", c, d, (int)e, md);
+            snprintf(msg, sizeof msg, "degree bound too small (projection %d has degree %d with x^%d, maxdeg %d)", c, T.R.deg[(size_t)c], (int)e, md);
             throw EngineError(msg);
         }
         r = hpoly_lcm(r, f, p);
     }
-    size_t e = 0;
-    while (r[e] == 0) e++;
-    if ((i64)r.size() - 1 - (i64)e > md) throw EngineError("degree bound too small (the lcm of the projections exceeds maxdeg)");
+    if ((i64)r.size() - 1 - (i64)hpoly_valuation(r) > md) throw EngineError("degree bound too small (the lcm of the projections exceeds maxdeg)");
     return r;
 }
 
@@ -11929,7 +11912,7 @@ void precond_limits(int n, int m)
 void precond_rank_run(const SpmvView &Fw, const SpmvView &Tr, const ZpField &F, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
 {
     const int n = Fw.rows, m = Fw.cols, mn = std::min(n, m);
-    const int md = (maxdeg <= 0 || maxdeg > mn) ? mn : maxdeg;
+    const int md = degree_bound(maxdeg, mn);
     // 2 * md + 2 terms: f = x^e g may have one more degree than its g (see the header)
     const int len = 2 * md + 2;
     bm_check_len(F, len);
@@ -11942,8 +11925,7 @@ void precond_rank_run(const SpmvView &Fw, const SpmvView &Tr, const ZpField &F, 
     const int ntries = precond_tries(tries);
     for (int t = 0; t < ntries && best < mn; t++) {
         const HPoly f = precond_try(T, Fw, &Tr, F, K, seed + (uint64_t)t, len, md, nullptr);
-        size_t e = 0;
-        while (f[e] == 0) e++;
+        const size_t e = hpoly_valuation(f);
         const i64 bound = (i64)f.size() - 1 - (i64)e;
         if (bound > best) {
             best = bound;
@@ -11971,8 +11953,7 @@ void precond_det_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, 
     const int ntries = precond_tries(tries);
     for (int t = 0; t < ntries; t++) {
         const HPoly f = precond_try(T, V, nullptr, F, K, seed + (uint64_t)t, len, n, &d);
-        size_t e = 0;
-        while (f[e] == 0) e++;
+        const size_t e = hpoly_valuation(f);
         st[6] = (i64)f.size() - 1;
         st[7] = (i64)e;
         if (e > 0) { // x divides a divisor of the minimal polynomial of D A: A is singular
@@ -11985,7 +11966,7 @@ void precond_det_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, 
             for (uint64_t w : d) prod = prod * w % p;
             uint64_t v = f[0] * hinv(prod, p) % p;
             if (n & 1) v = (p - v) % p;
-            *det = wied_balanced(v, p);
+            *det = hbalanced(v, p);
             *status = 1;
             return;
         }
@@ -11993,9 +11974,6 @@ void precond_det_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, 
     *det = 0;
     *status = 0;
 }
-
-// the view of a resident matrix (n, m > 0)
-void dcsr_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->m, D->p.p, D->ent.p, s); }
 
 void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_ZZp *dl, const spasm_ZZp *dr, const spasm_ZZp *U, i64 ldu,
                       const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
@@ -12013,8 +11991,8 @@ void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_
         memset(S, 0, (size_t)len * K * sizeof(int));
         for (int c = 0; c < K; c++) {
             uint64_t a = 0;
-            for (i64 r = 0; r < m; r++) a = (a + wied_residue(U[r * ldu + c], p) * wied_residue(V[r * ldv + c], p)) % p;
-            S[c] = wied_balanced(a, p);
+            for (i64 r = 0; r < m; r++) a = (a + hresidue(U[r * ldu + c], p) * hresidue(V[r * ldv + c], p)) % p;
+            S[c] = hbalanced(a, p);
         }
         return;
     }
@@ -12037,7 +12015,7 @@ void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_
     }
     SpgEvents ev;
     HIPCHK(hipEventRecord(ev.e[0], s));
-    const int launches = precond_run(op->fwd, mode == 1 ? &op->tr : nullptr, op->F, K, len, ddl.p, ddr.p, dU.p, K, dV.p, K, W, dS.p, s);
+    const int launches = sequence_run({&op->fwd, mode == 1 ? &op->tr : nullptr, ddl.p, ddr.p}, op->F, K, len, dU.p, K, dV.p, K, W, dS.p, s);
     HIPCHK(hipEventRecord(ev.e[1], s));
     std::vector<int> out((size_t)len * kk);
     HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -12052,6 +12030,41 @@ void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_
     memcpy(S, out.data(), out.size() * sizeof(int));
 }
 
+int rank_entry(Operand &&o, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
+{
+    precond_stats_reset();
+    o.check();
+    K = minpoly_K(K);
+    if (!rank || !certain) throw EngineError("NULL array");
+    precond_limits(o.n, o.m);
+    if (o.n == 0 || o.m == 0) { *rank = 0; *certain = 1; return 0; }
+    o.views(true, true);
+    i64 r = 0;
+    int c = 0;
+    precond_rank_run(*o.fwd, *o.tr, o.F, K, seed, tries, maxdeg, &r, &c);
+    *rank = r;
+    *certain = c;
+    return 0;
+}
+
+int det_entry(Operand &&o, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    precond_stats_reset();
+    o.check();
+    minpoly_square(o.n, o.m);
+    K = minpoly_K(K);
+    if (!det || !status) throw EngineError("NULL array");
+    precond_limits(o.n, o.m);
+    if (o.n == 0) { *det = 1; *status = 1; return 0; }
+    o.views(true, false);
+    spasm_ZZp v = 0;
+    int st = 0;
+    precond_det_run(*o.fwd, o.F, K, seed, tries, &v, &st);
+    *det = v;
+    *status = st;
+    return 0;
+}
+
 } // namespace
 
 extern "C" {
@@ -12062,7 +12075,7 @@ SPASM_API int spasm_amd_precond_diagonal(int len, uint64_t seed, int which, i64 
     return abi_call("spasm_amd_precond_diagonal", -1, [&] {
         precond_stats_reset();
         if (len < 0 || (which != 0 && which != 1)) throw EngineError("bad arguments (len >= 0, which 0 or 1)");
-        if (prime <= 2 || prime > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
+        check_prime(prime);
         if (len > 0 && !d) throw EngineError("NULL array");
         precond_diagonal(len, seed, which, prime, d);
         return 0;
@@ -12081,130 +12094,32 @@ SPASM_API int spasm_amd_precond_sequence(spasm_amd_spmv *op, int mode, int K, in
 
 SPASM_API int spasm_amd_wiedemann_rank(const struct spasm_csr *A, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
 {
-    return abi_call("spasm_amd_wiedemann_rank", -1, [&] {
-        DeviceGuard g;
-        precond_stats_reset();
-        if (const char *bad = batch_check(A)) throw EngineError(bad);
-        K = minpoly_K(K);
-        if (!rank || !certain) throw EngineError("NULL array");
-        precond_limits(A->n, A->m);
-        if (A->n == 0 || A->m == 0) { *rank = 0; *certain = 1; return 0; }
-        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_rank"));
-        op->build_transpose();
-        i64 r = 0;
-        int c = 0;
-        precond_rank_run(op->fwd, op->tr, op->F, K, seed, tries, maxdeg, &r, &c);
-        *rank = r;
-        *certain = c;
-        return 0;
-    });
+    return abi_call("spasm_amd_wiedemann_rank", -1, [&] { return rank_entry(Operand(A, "spasm_amd_wiedemann_rank"), K, seed, tries, maxdeg, rank, certain); });
 }
 
 SPASM_API int spasm_amd_spmv_wiedemann_rank(spasm_amd_spmv *op, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
 {
-    return abi_call("spasm_amd_spmv_wiedemann_rank", -1, [&] {
-        precond_stats_reset();
-        if (!op) throw EngineError("NULL operator");
-        K = minpoly_K(K);
-        if (!rank || !certain) throw EngineError("NULL array");
-        precond_limits(op->A.n, op->A.m);
-        if (op->A.n == 0 || op->A.m == 0) { *rank = 0; *certain = 1; return 0; }
-        DeviceGuard g(op);
-        op->build_transpose();
-        i64 r = 0;
-        int c = 0;
-        precond_rank_run(op->fwd, op->tr, op->F, K, seed, tries, maxdeg, &r, &c);
-        *rank = r;
-        *certain = c;
-        return 0;
-    });
+    return abi_call("spasm_amd_spmv_wiedemann_rank", -1, [&] { return rank_entry(Operand(op), K, seed, tries, maxdeg, rank, certain); });
 }
 
 SPASM_API int spasm_amd_dcsr_wiedemann_rank(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, int maxdeg, i64 *rank, int *certain)
 {
-    return abi_call("spasm_amd_dcsr_wiedemann_rank", -1, [&] {
-        precond_stats_reset();
-        if (!D) throw EngineError("NULL matrix");
-        K = minpoly_K(K);
-        if (!rank || !certain) throw EngineError("NULL array");
-        precond_limits(D->n, D->m);
-        if (D->n == 0 || D->m == 0) { *rank = 0; *certain = 1; return 0; }
-        DeviceGuard g(D);
-        // the transpose stays on the device for the length of the call
-        std::unique_ptr<spasm_amd_dcsr> T(dcsr_transpose(D, "transpose"));
-        SpmvView fwd, tr;
-        dcsr_view(D, fwd, nullptr);
-        dcsr_view(T.get(), tr, nullptr);
-        i64 r = 0;
-        int c = 0;
-        precond_rank_run(fwd, tr, D->F, K, seed, tries, maxdeg, &r, &c);
-        *rank = r;
-        *certain = c;
-        return 0;
-    });
+    return abi_call("spasm_amd_dcsr_wiedemann_rank", -1, [&] { return rank_entry(Operand(D), K, seed, tries, maxdeg, rank, certain); });
 }
 
 SPASM_API int spasm_amd_wiedemann_det(const struct spasm_csr *A, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
 {
-    return abi_call("spasm_amd_wiedemann_det", -1, [&] {
-        DeviceGuard g;
-        precond_stats_reset();
-        if (const char *bad = batch_check(A)) throw EngineError(bad);
-        minpoly_square(A->n, A->m);
-        K = minpoly_K(K);
-        if (!det || !status) throw EngineError("NULL array");
-        precond_limits(A->n, A->m);
-        if (A->n == 0) { *det = 1; *status = 1; return 0; }
-        std::unique_ptr<spasm_amd_spmv> op(spmv_create(A, "spasm_amd_wiedemann_det"));
-        spasm_ZZp v = 0;
-        int st = 0;
-        precond_det_run(op->fwd, op->F, K, seed, tries, &v, &st);
-        *det = v;
-        *status = st;
-        return 0;
-    });
+    return abi_call("spasm_amd_wiedemann_det", -1, [&] { return det_entry(Operand(A, "spasm_amd_wiedemann_det"), K, seed, tries, det, status); });
 }
 
 SPASM_API int spasm_amd_spmv_wiedemann_det(spasm_amd_spmv *op, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
 {
-    return abi_call("spasm_amd_spmv_wiedemann_det", -1, [&] {
-        precond_stats_reset();
-        if (!op) throw EngineError("NULL operator");
-        minpoly_square(op->A.n, op->A.m);
-        K = minpoly_K(K);
-        if (!det || !status) throw EngineError("NULL array");
-        precond_limits(op->A.n, op->A.m);
-        if (op->A.n == 0) { *det = 1; *status = 1; return 0; }
-        DeviceGuard g(op);
-        spasm_ZZp v = 0;
-        int st = 0;
-        precond_det_run(op->fwd, op->F, K, seed, tries, &v, &st);
-        *det = v;
-        *status = st;
-        return 0;
-    });
+    return abi_call("spasm_amd_spmv_wiedemann_det", -1, [&] { return det_entry(Operand(op), K, seed, tries, det, status); });
 }
 
 SPASM_API int spasm_amd_dcsr_wiedemann_det(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status)
 {
-    return abi_call("spasm_amd_dcsr_wiedemann_det", -1, [&] {
-        precond_stats_reset();
-        if (!D) throw EngineError("NULL matrix");
-        minpoly_square(D->n, D->m);
-        K = minpoly_K(K);
-        if (!det || !status) throw EngineError("NULL array");
-        precond_limits(D->n, D->m);
-        if (D->n == 0) { *det = 1; *status = 1; return 0; }
-        DeviceGuard g(D);
-        SpmvView view;
-        dcsr_square_view(D, view, nullptr);
-        spasm_ZZp v = 0;
-        int st = 0;
-        precond_det_run(view, D->F, K, seed, tries, &v, &st);
-        *det = v;
-        *status = st;
-        return 0;
-    });
+    return abi_call("spasm_amd_dcsr_wiedemann_det", -1, [&] { return det_entry(Operand(D), K, seed, tries, det, status); });
 }
 
 SPASM_API void spasm_amd_precond_stats(i64 *out)
