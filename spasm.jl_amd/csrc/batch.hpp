@@ -78,6 +78,30 @@ template <int BS> __device__ inline void batch_lds_clear(const BatchLds &L, int 
     }
 }
 
+// How a workgroup of BS threads walks rows of `width` words: TX lanes per row (a power of two, at most a wave), TY rows at a time;
+// this thread is lane tx of row ty
+template <int BS> struct BatchLanes {
+    int TX, tx, ty, TY;
+    __device__ __forceinline__ explicit BatchLanes(int width)
+    {
+        int lt = 0;
+        while ((1 << lt) < width && lt < 6) lt++;
+        TX = 1 << lt, tx = threadIdx.x & (TX - 1), ty = threadIdx.x >> lt, TY = BS >> lt;
+    }
+};
+
+// Rows 0 .. n - 1 of a concatenated CSR (P = the row pointers of the matrix, J, X) into a cleared image of balanced residues:
+// entry (i, j) at img[i * ld + j], TRANSPOSED at img[j * ld + i].  `width` = the most entries a row holds.  No barrier.
+template <int BS, bool TRANSPOSED>
+__device__ __forceinline__ void batch_load_rows(const ZpField &F, int *img, int ld, int n, int width, const i64d *P, const int *J, const int *X)
+{
+    const BatchLanes<BS> t(width);
+    for (int i = t.ty; i < n; i += t.TY) {
+        const i64d e0 = P[i], e1 = P[i + 1];
+        for (i64d k = e0 + t.tx; k < e1; k += t.TX) img[TRANSPOSED ? J[k] * ld + i : i * ld + J[k]] = zp_reduce(F, (int64_t)X[k]);
+    }
+}
+
 // Gauss-Jordan elimination of the image (`rows` rows of stride ld) inside LDS by the whole workgroup; returns the rank.  Columns
 // 0 .. ecols - 1 are candidates for a pivot, in that order; the update reaches columns 0 .. ucols - 1 (ucols >= ecols: what lies
 // right of the candidates rides along).  The rule is the one dense.hpp:5 states: the pivot of a column is the first row, not yet a
@@ -105,10 +129,8 @@ __device__ inline int batch_eliminate(const ZpField &F, const BatchLds &L, int l
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int *img = L.img, *wmin = L.wmin;
     unsigned *rowflag = L.rowflag;
-    // the update: TX lanes per row (a power of two, at most a wave), TY rows at a time
-    int lt = 0;
-    while ((1 << lt) < ucols && lt < 6) lt++;
-    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
+    const BatchLanes<BS> t(ucols);   // the update
+    const int TX = t.TX, tx = t.tx, ty = t.ty, TY = t.TY;
 
     int r = 0, par = 0, c = 0;
     for (; c < ecols && r < rows; c++) {
@@ -191,16 +213,7 @@ __global__ __launch_bounds__(BS) void k_batch_elim(BatchArgs a)
 
     batch_lds_clear<BS>(L, n * ld, a.bw);
     __syncthreads();
-    {
-        // TX lanes per row (a power of two, at most a wave), TY rows at a time
-        int lt = 0;
-        while ((1 << lt) < m && lt < 6) lt++;
-        const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
-        for (int i = ty; i < n; i += TY) {
-            const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
-            for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
-        }
-    }
+    batch_load_rows<BS, false>(F, img, ld, n, m, a.P + d.row0, a.J, a.X);
     __syncthreads();
 
     const int r = mode == BATCH_LU ? batch_eliminate<BS, true>(F, L, ld, n, m, m, false, a.rec + d.rec + 2)

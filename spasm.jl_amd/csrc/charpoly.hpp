@@ -44,7 +44,6 @@
 
 #define CHARPOLY_NMAX 1024   // the global path: one workgroup per matrix, an image of at most 1024 x 1025 words
 
-// A type of its own: the shared launcher keeps per Args type which classes have their dynamic-LDS attribute set (see det.hpp).
 struct CharpolyArgs {
     const BatchDesc *desc;
     const int *items;          // descriptors of this launch
@@ -64,18 +63,17 @@ template <int BS> __device__ __forceinline__ void charpoly_load(const CharpolyAr
     const ZpField F = d.F;
     for (int e = tid; e < n * ld; e += BS) img[e] = 0;
     __syncthreads();
-    int lt = 0;
-    while ((1 << lt) < n && lt < 6) lt++;
-    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
-    for (int i = ty; i < n; i += TY) {
+    // (batch_load_rows with a second arm for packed entries; the select stays inside the row loop, where the compiler has it)
+    const BatchLanes<BS> t(n);
+    for (int i = t.ty; i < n; i += t.TY) {
         const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
         if (a.E) {
-            for (i64d k = e0 + tx; k < e1; k += TX) {
+            for (i64d k = e0 + t.tx; k < e1; k += t.TX) {
                 const int2 e = a.E[k];
                 img[i * ld + e.x] = zp_reduce(F, (int64_t)e.y);
             }
         } else {
-            for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
+            for (i64d k = e0 + t.tx; k < e1; k += t.TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
         }
     }
     __syncthreads();
@@ -86,10 +84,8 @@ template <int BS> __device__ __forceinline__ void charpoly_hessenberg(const ZpFi
 {
     constexpr int NW = BS / 64;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    // TX lanes per row (a power of two, at most a wave), TY rows at a time
-    int lt = 0;
-    while ((1 << lt) < n && lt < 6) lt++;
-    const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
+    const BatchLanes<BS> t(n);
+    const int TX = t.TX, tx = t.tx, ty = t.ty, TY = t.TY;
 
     int par = 0;
     for (int k = 0; k + 2 < n; k++) {

@@ -19,13 +19,9 @@
 #include "zp.hpp"
 #include "batch.hpp"
 
-// BatchArgs as k_batch_elim reads it; mode, rec, scratch and cnt are not looked at, and `rank` is det[], indexed like desc.  A type
-// of its own because the host's launcher keeps per Args type which classes have their dynamic-LDS attribute set: a second kernel
-// table over BatchArgs itself would share that record with k_batch_elim, and whichever of the two ran second would go without.
-struct DetArgs : BatchArgs {};
-
+// BatchArgs as k_batch_elim reads it; mode, rec, scratch and cnt are not looked at, and `rank` is det[], indexed like desc.
 template <int BS>
-__global__ __launch_bounds__(BS) void k_batch_det(DetArgs a)
+__global__ __launch_bounds__(BS) void k_batch_det(BatchArgs a)
 {
     extern __shared__ int s_det[];
     constexpr int NW = BS / 64;
@@ -39,16 +35,7 @@ __global__ __launch_bounds__(BS) void k_batch_det(DetArgs a)
 
     batch_lds_clear<BS>(L, n * ld, a.bw);
     __syncthreads();
-    {
-        // TX lanes per row (a power of two, at most a wave), TY rows at a time
-        int lt = 0;
-        while ((1 << lt) < n && lt < 6) lt++;
-        const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
-        for (int i = ty; i < n; i += TY) {
-            const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
-            for (i64d k = e0 + tx; k < e1; k += TX) img[i * ld + a.J[k]] = zp_reduce(F, (int64_t)a.X[k]);
-        }
-    }
+    batch_load_rows<BS, false>(F, img, ld, n, n, a.P + d.row0, a.J, a.X);
     __syncthreads();
 
     const int r = batch_eliminate<BS, false>(F, L, ld, n, n, n, true, nullptr);

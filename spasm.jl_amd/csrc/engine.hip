@@ -6923,6 +6923,31 @@ const char *batch_check(const struct spasm_csr *M)
     return nullptr;
 }
 
+// batch_check of matrix i of a list, and of a whole list in order
+void batch_check_at(int i, const struct spasm_csr *M)
+{
+    const char *bad = batch_check(M);
+    if (!bad) return;
+    char msg[160];
+    snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
+    throw EngineError(msg);
+}
+
+void batch_check_list(int count, const struct spasm_csr *const *A)
+{
+    for (int i = 0; i < count; i++) batch_check_at(i, A[i]);
+}
+
+// i >= 0: matrix i of a list; i < 0: the one matrix, operator or handle of the call
+void require_square(int i, int n, int m)
+{
+    if (n == m) return;
+    char msg[96];
+    if (i >= 0) snprintf(msg, sizeof msg, "matrix %d: not square (%d x %d)", i, n, m);
+    else snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
+    throw EngineError(msg);
+}
+
 inline size_t batch_align(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // host matrices on the device as one concatenated CSR: row pointers (global entry offsets) | columns | values in one buffer;
@@ -6967,21 +6992,54 @@ void batch_stage(const std::vector<const struct spasm_csr *> &list, BatchStaged 
     out.X = (const int *)(out.buf.p + o_x);
 }
 
-// The elimination kernels of a path, one per class: kern[c] is the instance for kBatchClass[c].bs threads.  Args is BatchArgs or
-// SolveBatchArgs; both carry items and the LDS layout (cap, bw, rmax), which are filled in here.
-template <class Args> struct ElimKernels { void (*k[BATCH_NCLASS])(Args); };
+// A matrix of the LDS path as the descriptors need it: its shape, its prime, and where its n + 1 row pointers start in P.
+struct BatchItem { int n, m; i64 row0; i64 prime; };
+
+// the matrices A[i], i in pick, staged in that order; returns what describes them
+std::vector<BatchItem> batch_stage_items(const struct spasm_csr *const *A, const std::vector<int> &pick, BatchStaged &in)
+{
+    std::vector<const struct spasm_csr *> list;
+    for (int i : pick) list.push_back(A[i]);
+    batch_stage(list, in);
+    std::vector<BatchItem> item;
+    for (size_t f = 0; f < list.size(); f++) item.push_back(BatchItem{list[f]->n, list[f]->m, in.row0[f], list[f]->field->p});
+    return item;
+}
+
+// The descriptor of an item as every kernel over the batch's image reads it (n, m, ld, F, row0; the rest zero), and its class.
+// Here and nowhere else: the row stride (batch.hpp, "Row stride") and the smallest class that holds the padded image.
+int batch_describe(const BatchItem &M, BatchDesc &d)
+{
+    memset(&d, 0, sizeof d);
+    d.n = M.n;
+    d.m = M.m;
+    d.ld = (M.m % 2 == 0 && (i64)M.n * (M.m + 1) <= BATCH_PAD_CAP) ? M.m + 1 : M.m;
+    d.F = zp_field_make(M.prime);
+    d.row0 = M.row0;
+    const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
+    int c = 0;
+    while (key > kBatchClass[c].cap) c++;
+    return c;
+}
+
+// The kernels of a path, one per class: k[c] is the instance for kBatchClass[c].bs threads.  Every Args carries items and the LDS
+// layout (cap, bw, rmax), which the launcher fills in.  attr_done: the classes of THIS table whose dynamic-LDS attribute is set,
+// per device; two tables over one Args type each keep their own.
+template <class Args> struct ElimKernels {
+    void (*k[BATCH_NCLASS])(Args);
+    mutable bool attr_done[kMaxDev][BATCH_NCLASS] = {};
+};
 const ElimKernels<BatchArgs> kBatchElim = {{k_batch_elim<64>, k_batch_elim<128>, k_batch_elim<256>, k_batch_elim<512>}};
 const ElimKernels<SolveBatchArgs> kSolveElim = {{k_solve_elim<64>, k_solve_elim<128>, k_solve_elim<256>, k_solve_elim<512>}};
 
 // one class of jobs; the dynamic-LDS attribute of a kernel is set once per device
 template <class Args> void batch_launch_class(const ElimKernels<Args> &kern, int cls, Args a, const int *items, int nitems, hipStream_t s)
 {
-    static bool attr_done[kMaxDev][BATCH_NCLASS] = {};
     a.items = items;
     a.cap = kBatchClass[cls].cap;
     batch_layout(cls, a.bw, a.rmax);
     const size_t lds = (size_t)batch_lds_words(a.cap, a.bw, a.rmax) * sizeof(int);
-    bool &done = attr_done[current_device()][cls];
+    bool &done = kern.attr_done[current_device()][cls];
     if (!done) {
         HIPCHK(hipFuncSetAttribute((const void *)kern.k[cls], hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         done = true;
@@ -7009,6 +7067,37 @@ int batch_launch_jobs(const ElimKernels<Args> &kern, const std::vector<unsigned 
         first += hist[k];
     }
     return launches;
+}
+
+// One word per item (a rank, a determinant): the descriptors up, the launches of `kern` between two events, out[f] = the word
+// the workgroup of item f left in BatchArgs::rank, one synchronize.  Returns the launches and the device time between the events.
+struct BatchTimed { int launches; double ms; };
+BatchTimed batch_one_word(const ElimKernels<BatchArgs> &kern, const std::vector<BatchDesc> &desc, const std::vector<unsigned char> &cls, const i64d *dP, const int *dJ,
+                          const int *dX, int *out)
+{
+    const int nf = (int)desc.size();
+    hipStream_t s = nullptr;
+    DevBuf<BatchDesc> d_desc;
+    DevBuf<int> d_items, d_word;
+    d_desc.alloc((size_t)nf);
+    d_items.alloc((size_t)nf);
+    d_word.alloc((size_t)nf);
+    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+    std::vector<int> items((size_t)nf);
+    BatchArgs a;
+    memset(&a, 0, sizeof a);
+    a.desc = d_desc.p;
+    a.P = dP;
+    a.J = dJ;
+    a.X = dX;
+    a.mode = BATCH_RANK;
+    a.rank = d_word.p;
+    SpgEvents ev;
+    const int launches = batch_launch_jobs(kern, cls, 0, nf, items, d_items.p, a, ev.e[0], s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    HIPCHK(hipMemcpyAsync(out, d_word.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return BatchTimed{launches, ev.ms(0, 1)};
 }
 
 // bytes of device buffers one chunk may use: a third of the free device memory (SPASM_AMD_BATCH_SCRATCH_MB: a smaller figure, for
@@ -7100,9 +7189,6 @@ struct BatchResults {
     }
 };
 
-// A matrix of the LDS path as the descriptors need it: its shape, its prime, and where its n + 1 row pointers start in P.
-struct BatchItem { int n, m; i64 row0; i64 prime; };
-
 // The LDS path from the descriptors on.  fast[f] = place, in the call's list, of the f-th matrix; item[f] describes it; P, J, X: the
 // concatenated CSR on the device (P holds global entry offsets).  Results go to res at fast[f]; g_batch_stats[3 .. 7] are filled.
 void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, BatchResults &res)
@@ -7117,19 +7203,9 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
     std::vector<unsigned char> cls((size_t)nf);
     std::vector<i64> ecap((size_t)nf), recw((size_t)nf);
     for (int f = 0; f < nf; f++) {
-        const BatchItem *M = &item[(size_t)f];
         BatchDesc &d = desc[(size_t)f];
-        memset(&d, 0, sizeof d);
-        d.n = M->n;
-        d.m = M->m;
-        d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
-        d.F = zp_field_make(M->prime);
-        d.row0 = M->row0;
-        d.nslots = mode == BATCH_LU ? std::min(M->n, M->m) : M->m;
-        const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
-        int c = 0;
-        while (key > kBatchClass[c].cap) c++;
-        cls[(size_t)f] = (unsigned char)c;
+        cls[(size_t)f] = (unsigned char)batch_describe(item[(size_t)f], d);
+        d.nslots = mode == BATCH_LU ? std::min(d.n, d.m) : d.m;
         ecap[(size_t)f] = mode == BATCH_RANK ? 0 : batch_entry_cap(mode, d.n, d.m);
         recw[(size_t)f] = mode == BATCH_LU ? ((2 + (i64)d.m + d.n + 1) & ~(i64)1) : 2;
         st[7] = std::max<i64>(st[7], (i64)d.n * d.ld);
@@ -7154,36 +7230,31 @@ void batch_fast(int mode, const std::vector<int> &fast, const std::vector<BatchI
             pl.ents += ecap[(size_t)f];
         }
     }
-    // ---- descriptors to the device (the row pointers, columns and values are there already)
-    DevBuf<BatchDesc> d_desc;
-    DevBuf<int> d_items;
-    d_desc.alloc((size_t)nf);
-    d_items.alloc((size_t)nf);
-    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
-    std::vector<int> items((size_t)nf);
-    BatchArgs a;
-    memset(&a, 0, sizeof a);
-    a.desc = d_desc.p;
-    a.P = dP;
-    a.J = dJ;
-    a.X = dX;
-    a.mode = mode;
-    SpgEvents ev;
     i64 launches = 0, entries = 0;
     double ms = 0;
 
     if (mode == BATCH_RANK) {
-        DevBuf<int> drank;
-        drank.alloc((size_t)nf);
-        a.rank = drank.p;
-        launches += batch_launch_jobs(kBatchElim, cls, 0, nf, items, d_items.p, a, ev.e[0], s);
-        HIPCHK(hipEventRecord(ev.e[1], s));
         std::vector<int> hr((size_t)nf);
-        HIPCHK(hipMemcpyAsync(hr.data(), drank.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        ms += ev.ms(0, 1);
+        const BatchTimed t = batch_one_word(kBatchElim, desc, cls, dP, dJ, dX, hr.data());
+        launches += t.launches;
+        ms += t.ms;
         for (int f = 0; f < nf; f++) res.ranks[(size_t)fast[(size_t)f]] = hr[(size_t)f];
     } else {
+        // ---- descriptors to the device (the row pointers, columns and values are there already)
+        DevBuf<BatchDesc> d_desc;
+        DevBuf<int> d_items;
+        d_desc.alloc((size_t)nf);
+        d_items.alloc((size_t)nf);
+        HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
+        std::vector<int> items((size_t)nf);
+        BatchArgs a;
+        memset(&a, 0, sizeof a);
+        a.desc = d_desc.p;
+        a.P = dP;
+        a.J = dJ;
+        a.X = dX;
+        a.mode = mode;
+        SpgEvents ev;
         DevBuf<int2> scratch;
         DevBuf<unsigned char> out;
         DevBuf<i64d> rowstart;
@@ -7290,12 +7361,7 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
     if (count < 0) throw EngineError("count < 0");
     if (count == 0) return;
     if (!A || (mode == BATCH_LU && !lu_out) || (mode == BATCH_KERNEL && !k_out) || (mode == BATCH_RANK && !rank_out)) throw EngineError("NULL array");
-    for (int i = 0; i < count; i++)
-        if (const char *bad = batch_check(A[i])) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
-            throw EngineError(msg);
-        }
+    batch_check_list(count, A);
     require_device();
     const bool fast_ok = !opts || !opts->L;
     std::vector<int> fast, slow;
@@ -7310,12 +7376,8 @@ void batch_run(int mode, int count, const struct spasm_csr *const *A, struct ech
     st[1] = (i64)fast.size();
     st[2] = (i64)slow.size();
     if (!fast.empty()) {
-        std::vector<const struct spasm_csr *> list;
-        for (int i : fast) list.push_back(A[i]);
         BatchStaged in;
-        batch_stage(list, in);
-        std::vector<BatchItem> item;
-        for (size_t f = 0; f < list.size(); f++) item.push_back(BatchItem{list[f]->n, list[f]->m, in.row0[f], list[f]->field->p});
+        const std::vector<BatchItem> item = batch_stage_items(A, fast, in);
         batch_fast(mode, fast, item, in.P, in.J, in.X, res);
     }
     // ---- the others through the general path, one at a time
@@ -7522,18 +7584,10 @@ void blocks_check_host(const struct spasm_csr *A)
     if (A->p[A->n] > 0 && !A->j) throw EngineError("malformed matrix");
 }
 
-void blocks_check_square(int n, int m)
-{
-    if (n == m) return;
-    char msg[96];
-    snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
-    throw EngineError(msg);
-}
-
 spasm_amd_blocks *blocks_create(const struct spasm_csr *A, bool index = false)
 {
     blocks_check_host(A);
-    if (index) blocks_check_square(A->n, A->m);
+    if (index) require_square(-1, A->n, A->m);
     require_device();
     hipStream_t s = nullptr;
     const int n = A->n, m = A->m;
@@ -7565,7 +7619,7 @@ spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D, bool index = false
     if (!D) throw EngineError("NULL matrix");
     if (D->F.p <= 2 || D->F.p > 0xfffffffbLL) throw EngineError("prime out of range (2 < p <= 0xfffffffb)");
     if ((i64)D->n + (i64)D->m >= ((i64)1 << 31)) throw EngineError("n + m must be below 2^31");
-    if (index) blocks_check_square(D->n, D->m);
+    if (index) require_square(-1, D->n, D->m);
     hipStream_t s = nullptr;
     DevBuf<int> dj, dx;
     dj.alloc((size_t)D->nnz);
@@ -7580,6 +7634,13 @@ spasm_amd_blocks *blocks_create_dcsr(const spasm_amd_dcsr *D, bool index = false
 void blocks_need(const spasm_amd_blocks *B)
 {
     if (!B) throw EngineError("NULL handle");
+}
+
+// block b as the LDS path reads it from the handle's concatenated CSR (every block has rows + 1 pointers of its own)
+BatchItem blocks_item(const spasm_amd_blocks *B, int b)
+{
+    const i64 r0 = B->h_row_start[(size_t)b], c0 = B->h_col_start[(size_t)b];
+    return BatchItem{(int)(B->h_row_start[(size_t)b + 1] - r0), (int)(B->h_col_start[(size_t)b + 1] - c0), r0 + b, B->prime};
 }
 
 // block b as a host matrix (the caller frees it)
@@ -7656,7 +7717,7 @@ void blocks_run(int mode, spasm_amd_blocks *B, struct echelonize_opts *opts, str
         else if (B->h_nnz[(size_t)b] == 0) none.push_back(b);
         else {
             fast.push_back(b);
-            item.push_back(BatchItem{(int)rn, (int)cn, B->h_row_start[(size_t)b] + b, B->prime});
+            item.push_back(blocks_item(B, b));
         }
     }
     BatchResults res(mode, count);
@@ -7950,17 +8011,13 @@ void solve_batch_run(int count, const struct spasm_csr *const *A, const struct s
     st[1] += (i64)fast.size();
     st[2] = (i64)slow.size();
     if (!fast.empty()) {
-        std::vector<const struct spasm_csr *> la, lb;
-        for (int i : fast) { la.push_back(A[i]); lb.push_back(B[i]); }
         BatchStaged ina, inb;
-        batch_stage(la, ina);
-        batch_stage(lb, inb);
+        const std::vector<BatchItem> ia = batch_stage_items(A, fast, ina), ib = batch_stage_items(B, fast, inb);
         std::vector<SolveSys> sys;
         i64 nslots = 0;
         for (size_t f = 0; f < fast.size(); f++) {
-            const int i = fast[f];
-            sys.push_back(SolveSys{A[i]->n, A[i]->m, B[i]->n, ina.row0[f], inb.row0[f], nslots, A[i]->field->p});
-            nslots += B[i]->n;
+            sys.push_back(SolveSys{ia[f].n, ia[f].m, ib[f].n, ia[f].row0, ib[f].row0, nslots, ia[f].prime});
+            nslots += ib[f].n;
         }
         std::vector<int> h_cnt;
         std::vector<unsigned char> h_ok;
@@ -8507,12 +8564,7 @@ spasm_amd_solver *solver_create(int count, const struct spasm_csr *const *A)
     std::unique_ptr<spasm_amd_solver> S(new spasm_amd_solver());
     if (count == 0) return S.release();
     if (!A) throw EngineError("NULL array");
-    for (int i = 0; i < count; i++)
-        if (const char *bad = batch_check(A[i])) {
-            char msg[160];
-            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
-            throw EngineError(msg);
-        }
+    batch_check_list(count, A);
     S->sys.resize((size_t)count);
     std::vector<int> fast, slow;
     for (int i = 0; i < count; i++) {
@@ -8529,10 +8581,8 @@ spasm_amd_solver *solver_create(int count, const struct spasm_csr *const *A)
         HIPCHK(hipGetDevice(&S->dev));
     }
     if (!fast.empty()) {
-        std::vector<const struct spasm_csr *> la;
-        for (int i : fast) la.push_back(A[i]);
         BatchStaged in;
-        batch_stage(la, in);
+        batch_stage_items(A, fast, in);
         solver_factor(S.get(), fast, in.row0, in.P, in.J, in.X);
     }
     for (int i : slow) solver_factor_slow(S->sys[(size_t)i], A[i]);
@@ -8691,16 +8741,14 @@ void solver_apply_run(spasm_amd_solver *S, const struct spasm_csr *const *B, str
     st[1] += (i64)fast.size();
     st[2] += (i64)slow.size();
     if (!fast.empty()) {
-        std::vector<const struct spasm_csr *> lb;
-        for (int i : fast) lb.push_back(B[i]);
         BatchStaged inb;
-        batch_stage(lb, inb);
+        const std::vector<BatchItem> ib = batch_stage_items(B, fast, inb);
         std::vector<SolveSys> sys;
         i64 nslots = 0;
         for (size_t f = 0; f < fast.size(); f++) {
             const SolverSys &Y = S->sys[(size_t)fast[f]];
-            sys.push_back(SolveSys{Y.n, Y.m, B[fast[f]]->n, 0, inb.row0[f], nslots, Y.prime});
-            nslots += B[fast[f]]->n;
+            sys.push_back(SolveSys{Y.n, Y.m, ib[f].n, 0, ib[f].row0, nslots, Y.prime});
+            nslots += ib[f].n;
         }
         std::vector<SolverApplyDesc> desc;
         std::vector<unsigned char> cls;
@@ -9991,7 +10039,7 @@ namespace {
 // count, LDS items, general-path items, items zero by structure, launches, device us, host-parity us, spare
 thread_local i64 g_det_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
-const ElimKernels<DetArgs> kBatchDet = {{k_batch_det<64>, k_batch_det<128>, k_batch_det<256>, k_batch_det<512>}};
+const ElimKernels<BatchArgs> kBatchDet = {{k_batch_det<64>, k_batch_det<128>, k_batch_det<256>, k_batch_det<512>}};
 
 // 0 for an even permutation of 0 .. n - 1, 1 for an odd one: n - cycles mod 2
 int det_perm_parity(const std::vector<i64> &perm)
@@ -10011,52 +10059,19 @@ int det_perm_parity(const std::vector<i64> &perm)
     return (int)((n - cycles) & 1);
 }
 
-// The LDS path from the descriptors on, as batch_fast runs BATCH_RANK: item[f] describes the f-th matrix of the concatenated CSR on
-// the device; out[f] = its determinant.  g_det_stats[4], [5] are added to.
+// The LDS path from the descriptors on: batch_one_word over k_batch_det.  item[f] describes the f-th matrix of the concatenated
+// CSR on the device; out[f] = its determinant.  g_det_stats[4], [5] are added to.
 void det_fast(const std::vector<BatchItem> &item, const i64d *dP, const int *dJ, const int *dX, std::vector<int> &out)
 {
     const int nf = (int)item.size();
     out.assign((size_t)nf, 0);
     if (nf == 0) return;
-    hipStream_t s = nullptr;
     std::vector<BatchDesc> desc((size_t)nf);
     std::vector<unsigned char> cls((size_t)nf);
-    for (int f = 0; f < nf; f++) {
-        const BatchItem *M = &item[(size_t)f];
-        BatchDesc &d = desc[(size_t)f];
-        memset(&d, 0, sizeof d);
-        d.n = M->n;
-        d.m = M->m;
-        d.ld = (M->m % 2 == 0 && (i64)M->n * (M->m + 1) <= BATCH_PAD_CAP) ? M->m + 1 : M->m;
-        d.F = zp_field_make(M->prime);
-        d.row0 = M->row0;
-        const i64 key = std::max<i64>((i64)d.n * d.ld, std::max(d.n, d.m));
-        int c = 0;
-        while (key > kBatchClass[c].cap) c++;
-        cls[(size_t)f] = (unsigned char)c;
-    }
-    DevBuf<BatchDesc> d_desc;
-    DevBuf<int> d_items, d_det;
-    d_desc.alloc((size_t)nf);
-    d_items.alloc((size_t)nf);
-    d_det.alloc((size_t)nf);
-    HIPCHK(hipMemcpyAsync(d_desc.p, desc.data(), (size_t)nf * sizeof(BatchDesc), hipMemcpyHostToDevice, s));
-    std::vector<int> items((size_t)nf);
-    DetArgs a;
-    memset(&a, 0, sizeof a);
-    a.desc = d_desc.p;
-    a.P = dP;
-    a.J = dJ;
-    a.X = dX;
-    a.mode = BATCH_RANK;
-    a.rank = d_det.p;
-    SpgEvents ev;
-    const int launches = batch_launch_jobs(kBatchDet, cls, 0, nf, items, d_items.p, a, ev.e[0], s);
-    HIPCHK(hipEventRecord(ev.e[1], s));
-    HIPCHK(hipMemcpyAsync(out.data(), d_det.p, (size_t)nf * sizeof(int), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    g_det_stats[4] += launches;
-    g_det_stats[5] += (i64)(ev.ms(0, 1) * 1000.0);
+    for (int f = 0; f < nf; f++) cls[(size_t)f] = (unsigned char)batch_describe(item[(size_t)f], desc[(size_t)f]);
+    const BatchTimed t = batch_one_word(kBatchDet, desc, cls, dP, dJ, dX, out.data());
+    g_det_stats[4] += t.launches;
+    g_det_stats[5] += (i64)(t.ms * 1000.0);
 }
 
 // one square matrix through the general path
@@ -10101,15 +10116,8 @@ void det_run(int count, const struct spasm_csr *const *A, spasm_ZZp *det)
     if (count == 0) return;
     if (!A || !det) throw EngineError("NULL array");
     for (int i = 0; i < count; i++) {
-        char msg[160];
-        if (const char *bad = batch_check(A[i])) {
-            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
-            throw EngineError(msg);
-        }
-        if (A[i]->n != A[i]->m) {
-            snprintf(msg, sizeof msg, "matrix %d: not square (%d x %d)", i, A[i]->n, A[i]->m);
-            throw EngineError(msg);
-        }
+        batch_check_at(i, A[i]);
+        require_square(i, A[i]->n, A[i]->m);
     }
     require_device();
     std::vector<int> fast, slow;
@@ -10123,12 +10131,8 @@ void det_run(int count, const struct spasm_csr *const *A, spasm_ZZp *det)
     st[2] = (i64)slow.size();
     std::vector<int> res((size_t)count, 0);
     if (!fast.empty()) {
-        std::vector<const struct spasm_csr *> list;
-        for (int i : fast) list.push_back(A[i]);
         BatchStaged in;
-        batch_stage(list, in);
-        std::vector<BatchItem> item;
-        for (size_t f = 0; f < list.size(); f++) item.push_back(BatchItem{list[f]->n, list[f]->m, in.row0[f], list[f]->field->p});
+        const std::vector<BatchItem> item = batch_stage_items(A, fast, in);
         std::vector<int> d;
         det_fast(item, in.P, in.J, in.X, d);
         for (size_t f = 0; f < fast.size(); f++) res[(size_t)fast[f]] = d[f];
@@ -10145,11 +10149,7 @@ void blocks_det(spasm_amd_blocks *B, spasm_ZZp *det)
     det_stats_reset();
     blocks_need(B);
     if (!det) throw EngineError("NULL array");
-    if (B->n != B->m) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "not square (%d x %d)", B->n, B->m);
-        throw EngineError(msg);
-    }
+    require_square(-1, B->n, B->m);
     i64 *st = g_det_stats;
     const int count = B->nb;
     const ZpField F = zp_field_make(B->prime);
@@ -10161,7 +10161,7 @@ void blocks_det(spasm_amd_blocks *B, spasm_ZZp *det)
         if (rn != cn || B->h_nnz[(size_t)b] == 0) st[3]++;
         else if (rn * rn <= BATCH_LIMIT) {
             fast.push_back(b);
-            item.push_back(BatchItem{(int)rn, (int)cn, B->h_row_start[(size_t)b] + b, B->prime});
+            item.push_back(blocks_item(B, b));
         } else slow.push_back(b);
     }
     if (st[3] > 0) { *det = 0; return; }
@@ -10225,11 +10225,7 @@ SPASM_API int spasm_amd_det(const struct spasm_csr *A, spasm_ZZp *det)
         det_stats_reset();
         if (const char *bad = batch_check(A)) throw EngineError(bad);
         if (!det) throw EngineError("NULL array");
-        if (A->n != A->m) {
-            char msg[96];
-            snprintf(msg, sizeof msg, "not square (%d x %d)", A->n, A->m);
-            throw EngineError(msg);
-        }
+        require_square(-1, A->n, A->m);
         det_split([&] { return blocks_create(A); }, det);
         return 0;
     });
@@ -10247,11 +10243,7 @@ SPASM_API int spasm_amd_dcsr_det(const spasm_amd_dcsr *D, spasm_ZZp *det)
         det_stats_reset();
         if (!D) throw EngineError("NULL matrix");
         if (!det) throw EngineError("NULL array");
-        if (D->n != D->m) {
-            char msg[96];
-            snprintf(msg, sizeof msg, "not square (%d x %d)", D->n, D->m);
-            throw EngineError(msg);
-        }
+        require_square(-1, D->n, D->m);
         det_split([&] { return blocks_create_dcsr(D); }, det);
         return 0;
     });
@@ -10338,27 +10330,22 @@ void charpoly_launch(CharpolyJob &job, const std::vector<BatchItem> &item, const
     items.resize((size_t)nf);
     i64 words = 0, image = 0;
     for (int q = 0; q < nf; q++) {
-        const BatchItem *M = &item[(size_t)order[(size_t)q]];
+        const BatchItem &M = item[(size_t)order[(size_t)q]];
         BatchDesc &d = desc[(size_t)q];
-        memset(&d, 0, sizeof d);
-        const int n = M->n;
-        d.n = d.m = n;
-        d.F = zp_field_make(M->prime);
-        d.row0 = M->row0;
-        d.rec = rec ? rec[order[(size_t)q]] : words;
-        words += (i64)n + 1;
         if (q < nl) {
-            d.ld = (n % 2 == 0 && (i64)n * (n + 1) <= BATCH_PAD_CAP) ? n + 1 : n;
-            const i64 key = std::max<i64>((i64)n * d.ld, n);
-            int c = 0;
-            while (key > kBatchClass[c].cap) c++;
-            cls[(size_t)q] = (unsigned char)c;
+            cls[(size_t)q] = (unsigned char)batch_describe(M, d);
         } else {
-            d.ld = n | 1;
+            memset(&d, 0, sizeof d);
+            d.n = d.m = M.n;
+            d.F = zp_field_make(M.prime);
+            d.row0 = M.row0;
+            d.ld = M.n | 1;
             d.slice = image;
-            image += (i64)n * d.ld;
+            image += (i64)M.n * d.ld;
             items[(size_t)q] = q;
         }
+        d.rec = rec ? rec[order[(size_t)q]] : words;
+        words += (i64)M.n + 1;
     }
     job.d_desc.alloc((size_t)nf);
     job.d_items.alloc((size_t)nf);
@@ -10422,27 +10409,20 @@ void charpoly_run(int count, const struct spasm_csr *const *A, spasm_ZZp *const 
     if (count == 0) return;
     if (!A || !coef) throw EngineError("NULL array");
     for (int i = 0; i < count; i++) {
-        char msg[160];
-        if (const char *bad = batch_check(A[i])) {
-            snprintf(msg, sizeof msg, "matrix %d: %s", i, bad);
-            throw EngineError(msg);
-        }
-        if (A[i]->n != A[i]->m) {
-            snprintf(msg, sizeof msg, "matrix %d: not square (%d x %d)", i, A[i]->n, A[i]->m);
-            throw EngineError(msg);
-        }
+        batch_check_at(i, A[i]);
+        require_square(i, A[i]->n, A[i]->m);
         if (!coef[i]) {
+            char msg[160];
             snprintf(msg, sizeof msg, "matrix %d: NULL array", i);
             throw EngineError(msg);
         }
         charpoly_check_size(i, A[i]->n);
     }
     require_device();
-    std::vector<const struct spasm_csr *> list(A, A + count);
+    std::vector<int> all;
+    for (int i = 0; i < count; i++) all.push_back(i);
     BatchStaged in;
-    batch_stage(list, in);
-    std::vector<BatchItem> item;
-    for (int i = 0; i < count; i++) item.push_back(BatchItem{A[i]->n, A[i]->m, in.row0[(size_t)i], A[i]->field->p});
+    const std::vector<BatchItem> item = batch_stage_items(A, all, in);
     std::vector<std::vector<int>> res;
     charpoly_device(item, in.P, in.J, in.X, nullptr, res);
     for (int i = 0; i < count; i++) memcpy(coef[i], res[(size_t)i].data(), res[(size_t)i].size() * sizeof(int));
@@ -10465,11 +10445,7 @@ SPASM_API int spasm_amd_charpoly(const struct spasm_csr *A, spasm_ZZp *coef)
         charpoly_stats_reset();
         if (const char *bad = batch_check(A)) throw EngineError(bad);
         if (!coef) throw EngineError("NULL array");
-        if (A->n != A->m) {
-            char msg[96];
-            snprintf(msg, sizeof msg, "not square (%d x %d)", A->n, A->m);
-            throw EngineError(msg);
-        }
+        require_square(-1, A->n, A->m);
         charpoly_check_size(-1, A->n);
         charpoly_run(1, &A, &coef);
         return 0;
@@ -10483,11 +10459,7 @@ SPASM_API int spasm_amd_dcsr_charpoly(const spasm_amd_dcsr *D, spasm_ZZp *coef)
         charpoly_stats_reset();
         if (!D) throw EngineError("NULL matrix");
         if (!coef) throw EngineError("NULL array");
-        if (D->n != D->m) {
-            char msg[96];
-            snprintf(msg, sizeof msg, "not square (%d x %d)", D->n, D->m);
-            throw EngineError(msg);
-        }
+        require_square(-1, D->n, D->m);
         charpoly_check_size(-1, D->n);
         std::vector<BatchItem> item(1, BatchItem{D->n, D->m, 0, D->F.p});
         std::vector<std::vector<int>> res;
@@ -10692,10 +10664,9 @@ void blocks_charpoly(spasm_amd_blocks *B, spasm_ZZp *coef, bool factors)
     std::vector<i64> rec((size_t)nb);
     std::vector<int> len((size_t)nb);
     for (int b = 0; b < nb; b++) {
-        const i64 r0 = B->h_row_start[(size_t)b], rn = B->h_row_start[(size_t)b + 1] - r0;
-        item[(size_t)b] = BatchItem{(int)rn, (int)rn, r0 + b, B->prime};
-        rec[(size_t)b] = r0 + b;
-        len[(size_t)b] = (int)rn + 1;
+        item[(size_t)b] = blocks_item(B, b);   // (square: the row and the column starts of an index split are the same)
+        rec[(size_t)b] = item[(size_t)b].row0;
+        len[(size_t)b] = item[(size_t)b].n + 1;
     }
     PolyProduct pp;
     DevBuf<int> x0, x1;
@@ -10765,7 +10736,7 @@ SPASM_API int spasm_amd_charpoly_split(const struct spasm_csr *A, spasm_ZZp *coe
         charpoly_split_stats_reset();
         blocks_check_host(A);
         if (!coef) throw EngineError("NULL array");
-        blocks_check_square(A->n, A->m);
+        require_square(-1, A->n, A->m);
         charpoly_split([&] { return blocks_create(A, true); }, coef);
         return 0;
     });
@@ -10778,7 +10749,7 @@ SPASM_API int spasm_amd_dcsr_charpoly_split(const spasm_amd_dcsr *D, spasm_ZZp *
         charpoly_split_stats_reset();
         if (!D) throw EngineError("NULL matrix");
         if (!coef) throw EngineError("NULL array");
-        blocks_check_square(D->n, D->m);
+        require_square(-1, D->n, D->m);
         charpoly_split([&] { return blocks_create_dcsr(D, true); }, coef);
         return 0;
     });
@@ -10898,11 +10869,7 @@ int sequence_run(const SeqOperator &op, const ZpField &F, int K, i64 len, const 
 void krylov_check(const spasm_amd_spmv *op, int trans, int K, i64 len, const void *U, i64 ldu, const void *V, i64 ldv, const void *S)
 {
     if (!op) throw EngineError("NULL operator");
-    if (op->A.n != op->A.m) {
-        char msg[96];
-        snprintf(msg, sizeof msg, "not square (%d x %d)", op->A.n, op->A.m);
-        throw EngineError(msg);
-    }
+    require_square(-1, op->A.n, op->A.m);
     if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
     if (len < 0 || len * 64 >= ((i64)1 << 31) || ldu < K || ldv < K || (trans != 0 && trans != 1))
         throw EngineError("bad arguments (trans 0/1, 0 <= len < 2^25, ldu >= K, ldv >= K)");
@@ -11254,14 +11221,6 @@ void minpoly_run(const SpmvView &V, const ZpField &F, int K, uint64_t seed, int 
 // the view of a resident matrix (n, m > 0): the row pointers serve as starts, the lengths are their differences
 void dcsr_view(const spasm_amd_dcsr *D, SpmvView &view, hipStream_t s) { view.from_row_pointers(D->n, D->m, D->p.p, D->ent.p, s); }
 
-void minpoly_square(int n, int m)
-{
-    if (n == m) return;
-    char msg[96];
-    snprintf(msg, sizeof msg, "not square (%d x %d)", n, m);
-    throw EngineError(msg);
-}
-
 // The matrix of a family entry: a host CSR, an SpMV operator or a resident matrix.  check() reads n, m and F without a device;
 // views() takes the device (put back when this goes) and builds the views that are asked for.  It owns what it had to make:
 // the temporary operator of a CSR, the transpose of a resident matrix, the views of a resident matrix.
@@ -11323,7 +11282,7 @@ int minpoly_entry(Operand &&o, int K, uint64_t seed, int maxdeg, const spasm_ZZp
 {
     minpoly_stats_reset();
     o.check();
-    minpoly_square(o.n, o.m);
+    require_square(-1, o.n, o.m);
     K = minpoly_K(K);
     if (!coef || !deg) throw EngineError("NULL array");
     if ((U == nullptr) != (X == nullptr)) throw EngineError("U and V must both be given or both be NULL");
@@ -11518,7 +11477,7 @@ void poly_apply_check(const spasm_amd_spmv *op, int trans, int K, const int *deg
                       const spasm_ZZp *X, i64 ldx)
 {
     if (!op) throw EngineError("NULL operator");
-    minpoly_square(op->A.n, op->A.m);
+    require_square(-1, op->A.n, op->A.m);
     if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
     if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
     if (ldv < K) throw EngineError("ldv < K");
@@ -11573,7 +11532,7 @@ int poly_apply_dev(spasm_amd_spmv *op, int trans, int K, const int *deg, const s
 
 void wied_check(int n, int m, int trans, int K, const void *B, i64 ldb, const void *X, i64 ldx, const int *status)
 {
-    minpoly_square(n, m);
+    require_square(-1, n, m);
     if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
     if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
     if (ldb < K) throw EngineError("ldb < K");
@@ -11981,7 +11940,7 @@ void precond_sequence(spasm_amd_spmv *op, int mode, int K, int len, const spasm_
     if (!op) throw EngineError("NULL operator");
     if (mode != 0 && mode != 1) throw EngineError("mode must be 0 (D A) or 1 (E A^T D2 A)");
     const int n = op->A.n, m = op->A.m;
-    if (mode == 0) minpoly_square(n, m);
+    if (mode == 0) require_square(-1, n, m);
     if (K < 1 || K > 64) throw EngineError("K out of range (1 <= K <= 64)");
     if (len < 0 || (i64)len * 64 >= ((i64)1 << 31) || ldu < K || ldv < K) throw EngineError("bad arguments (0 <= len < 2^25, ldu >= K, ldv >= K)");
     if (len == 0) return;
@@ -12051,7 +12010,7 @@ int det_entry(Operand &&o, int K, uint64_t seed, int tries, spasm_ZZp *det, int 
 {
     precond_stats_reset();
     o.check();
-    minpoly_square(o.n, o.m);
+    require_square(-1, o.n, o.m);
     K = minpoly_K(K);
     if (!det || !status) throw EngineError("NULL array");
     precond_limits(o.n, o.m);

@@ -71,10 +71,9 @@ __global__ __launch_bounds__(BS) void k_solve_elim(SolveBatchArgs a)
     batch_lds_clear<BS>(L, m * ld, a.bw);
     __syncthreads();
     {
-        // TX lanes per row of A or of B (a power of two, at most a wave), TY rows at a time; a row holds at most m entries
-        int lt = 0;
-        while ((1 << lt) < m && lt < 6) lt++;
-        const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
+        // A and B in one loop (the transposed twin of batch_load_rows with a select per row); a row of either holds at most m entries
+        const BatchLanes<BS> t(m);
+        const int TX = t.TX, tx = t.tx, ty = t.ty, TY = t.TY;
         for (int i = ty; i < W; i += TY) {
             const bool rhs = i >= n;
             const i64d e0 = rhs ? a.BP[d.brow0 + (i - n)] : a.P[d.row0 + i], e1 = rhs ? a.BP[d.brow0 + (i - n) + 1] : a.P[d.row0 + i + 1];

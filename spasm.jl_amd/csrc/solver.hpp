@@ -68,17 +68,8 @@ __global__ __launch_bounds__(BS) void k_solver_factor(SolverFactorArgs a)
 
     batch_lds_clear<BS>(L, m * ld, a.bw);
     __syncthreads();
-    {
-        // TX lanes per row of A (a power of two, at most a wave), TY rows at a time; a row holds at most m entries
-        int lt = 0;
-        while ((1 << lt) < m && lt < 6) lt++;
-        const int TX = 1 << lt, tx = tid & (TX - 1), ty = tid >> lt, TY = BS >> lt;
-        for (int i = ty; i < n; i += TY) {
-            const i64d e0 = a.P[d.row0 + i], e1 = a.P[d.row0 + i + 1];
-            for (i64d k = e0 + tx; k < e1; k += TX) img[a.J[k] * ld + i] = zp_reduce(F, (int64_t)a.X[k]);
-        }
-        for (int t = tid; t < d.w; t += BS) img[(d.t0 + t) * ld + n + t] = 1;
-    }
+    batch_load_rows<BS, true>(F, img, ld, n, m, a.P + d.row0, a.J, a.X);   // (a row of A holds at most m entries)
+    for (int t = tid; t < d.w; t += BS) img[(d.t0 + t) * ld + n + t] = 1;
     __syncthreads();
 
     const int r = batch_eliminate<BS, false>(F, L, ld, m, n, W, false, nullptr);
