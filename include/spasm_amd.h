@@ -1094,6 +1094,60 @@ int spasm_amd_spmv_wiedemann_det(spasm_amd_spmv *op, int K, uint64_t seed, int t
 int spasm_amd_dcsr_wiedemann_det(const spasm_amd_dcsr *D, int K, uint64_t seed, int tries, spasm_ZZp *det, int *status);
 void spasm_amd_precond_stats(i64 *out);   /* of the last preconditioned Wiedemann call of this thread */
 
+/* ---- block Wiedemann: block Krylov sequences, Berlekamp-Massey over matrix sequences, determinant (engine extension; DESIGN
+ *      section 27; csrc/block_krylov.hpp, csrc/block_bm.hpp) ----
+ * A block projection U^T M^i V with U, V of b columns carries in about 2 n / b terms what the scalar routines above read off 2 n
+ * terms.  b is 2, 4, 8 or 16.
+ *   block_sequence    op is a resident SQUARE operator; d_left (n words or NULL), U, V (n x b, ldu, ldv >= b) and S are HOST arrays,
+ *                 any int32 is reduced where it is read.  S[(i * b + r) * b + c] = sum_k U[k, r] * (M^i V)[k, c] mod p for
+ *                 0 <= i < len, balanced residues, with M = A (trans 0), A^T (trans 1), and D A or D A^T when d_left is given,
+ *                 D = diag(d_left), every word non-zero mod p.  One launch set per step (the step kernels of the resident
+ *                 product with a b x b projection as epilogue), no host synchronization inside the run.  The diagonal of a
+ *                 term is the K = b term of krylov_sequence for the same U, V.
+ *   block_sequence_dev  the same on DEVICE arrays of the operator's device (S: len * b * b words), enqueued on stream (NULL: the
+ *                 null stream, and the call waits); d_left is not checked for zeros.
+ *   block_berlekamp_massey  S is a HOST array of len terms of b * b words.  Returns a left generator F(x) = sum_t F_t x^t:
+ *                 coef[(t * b + r) * b + c] = F_t[r, c] for 0 <= t <= len (the caller gives (len + 1) * b * b words), low degree
+ *                 first, balanced residues; rowdeg[r] is the degree of row r, the words of a row above its degree are zero,
+ *                 *dmax is the largest row degree.
+ *                   (A) for every row r and every 0 <= i < len - rowdeg[r]: sum_{t <= rowdeg[r]} F_t[r, :] S_{i+t} = 0;
+ *                   (B) the b x b matrix of leading row coefficients (row r taken at x^rowdeg[r]) is non-singular;
+ *                   (C) the row degrees are those of a minimal approximant basis of [S(x); I] at order len, taken by
+ *                       ascending (degree, index) with independent leading rows; their sum is the rank of the block Hankel
+ *                       matrix of the sequence when len covers the left and right generator degrees.
+ *                 F is unique only up to row operations: it is specified by (A), (B), (C) and by being the same bytes in
+ *                 two runs.  The zero sequence gives F = I, all degrees 0.  The state lives in device memory; a step is three
+ *                 ordinary launches on one stream (discrepancy, elimination, update), no grid-wide barrier.
+ *   block_wiedemann_det, spmv_block_wiedemann_det, dcsr_block_wiedemann_det
+ *                 A host matrix, a resident operator, a resident matrix; A must be square.  tries <= 0 means 3.  Try t takes
+ *                 D = precond_diagonal(n, seed + t, 0), U, V = minpoly_vectors(n, b, seed + t), the block sequence of D A with
+ *                 len = 2 * ceil(n / b) + 2 terms, and its generator F.  When the row degrees sum to n:
+ *                 det A = (-1)^n det F_0 / det(leading row coefficients of F) / prod d_i (0 when F_0 is singular), *status = 1;
+ *                 the two b x b determinants and prod d_i are exact host arithmetic.  Otherwise the next seed is tried; after
+ *                 the last try *status = 0 and *det = 0.
+ *                 *status = 1 IS MONTE CARLO, unlike wiedemann_det: the proof there rests on the 2 n terms of a scalar
+ *                 sequence and does not carry over to a block sequence of about 2 n / b terms.  The value is right with a
+ *                 probability that grows with p (and is poor over GF(3)); nothing verifies it.
+ *                 The empty matrix has determinant 1, status 1, and needs no device.
+ *   stats         of the last of these calls of this thread: out[10] = b, len, steps of the sequence (products with A, summed
+ *                 over the tries), launches, sum of the row degrees (last try), tries used, device microseconds of the
+ *                 sequences and of Berlekamp-Massey (HIP events), n, largest row degree.  Every call clears what it does not fill.
+ *   deterministic two runs give the same bytes (the projection and the discrepancy add integers)
+ *   errors        "b must be 2, 4, 8 or 16", a NULL operator / matrix / array, a matrix that is not square ("not square (3 x 2)"),
+ *                 len outside 1 .. 2^24 - 1 ("len out of range"), trans outside 0 .. 1, ldu or ldv < b, a word of d_left that is
+ *                 zero mod p ("d_left[3] is zero mod p"), a prime outside 3 .. 0xFFFFFFFB or even ("prime must be odd"),
+ *                 n >= 2^24, no device ("no HIP device"), out of memory: -1, NO output word is written,
+ *                 spasm_amd_last_error() names the cause. */
+int spasm_amd_block_sequence(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *U, i64 ldu,
+                             const spasm_ZZp *V, i64 ldv, spasm_ZZp *S);
+int spasm_amd_block_sequence_dev(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *U, i64 ldu,
+                                 const spasm_ZZp *V, i64 ldv, spasm_ZZp *S, void *stream);
+int spasm_amd_block_berlekamp_massey(int b, int len, const spasm_ZZp *S, i64 prime, spasm_ZZp *coef, int *rowdeg, int *dmax);
+int spasm_amd_block_wiedemann_det(const struct spasm_csr *A, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+int spasm_amd_spmv_block_wiedemann_det(spasm_amd_spmv *op, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+int spasm_amd_dcsr_block_wiedemann_det(const spasm_amd_dcsr *D, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status);
+void spasm_amd_block_stats(i64 *out);   /* of the last block Wiedemann call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

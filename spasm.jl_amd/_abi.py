@@ -350,6 +350,13 @@ SIGNATURES = {
     "spasm_amd_spmv_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "spasm_amd_dcsr_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
     "spasm_amd_precond_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_block_sequence": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_block_sequence_dev": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "spasm_amd_block_berlekamp_massey": (C.c_int32, [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_block_wiedemann_det": (C.c_int32, [_P(CsrStruct), C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_spmv_block_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_dcsr_block_wiedemann_det": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64, C.c_int32, _P(C.c_int32), _P(C.c_int32)]),
+    "spasm_amd_block_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -2411,3 +2411,119 @@ SpMV.wiedemann_det = wiedemann_det
 SpMV.precond_sequence = precond_sequence
 DeviceCSR.wiedemann_rank = wiedemann_rank
 DeviceCSR.wiedemann_det = wiedemann_det
+
+
+# ---------------------------------------------------------------------------------------------
+# Block Wiedemann  (spasm_amd_block_sequence*, _block_berlekamp_massey, _block_wiedemann_det*; csrc/block_krylov.hpp, block_bm.hpp)
+# ---------------------------------------------------------------------------------------------
+BLOCK_STATS = ("b", "len", "steps", "launches", "degree_sum", "tries", "sequence_device_us", "bm_device_us", "n", "max_degree")
+
+
+def block_sequence(op, U, V, length, trans=False, d_left=None):
+    """block_sequence(op, U, V, length, trans=False, d_left=None) -> S of shape (length, b, b):
+    S[i, r, c] = sum_k U[k, r] * (M^i V)[k, c] mod p as balanced residues, M = A, the square matrix of the SpMV operator op (A^T
+    with trans=True), or diag(d_left) times it.  U and V are n x b, b in (2, 4, 8, 16); d_left has n words, none zero mod p.
+    int32 numpy arrays (spasm_amd_block_sequence) or int32 torch tensors on the current device (enqueued on the current stream
+    without a host synchronization; S is a tensor and d_left is not checked: spasm_amd_block_sequence_dev).  Any int32 is reduced
+    where it is read; U, V and d_left are not modified."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n = op.shape[0]
+    length = int(length)
+    lib = _abi.lib()
+    if type(U).__module__.startswith("torch") or type(V).__module__.startswith("torch"):
+        import torch
+
+        tensors = [(U, "U"), (V, "V")] + ([(d_left, "d_left")] if d_left is not None else [])
+        for t, name in tensors:
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.device.type != "cuda" or t.device.index != torch.cuda.current_device():
+                raise TypeError(f"{name} must be an int32 tensor on the current device")
+        for t, name in tensors[:2]:
+            if t.dim() != 2 or t.shape[0] != n or tuple(t.shape) != tuple(U.shape):
+                raise ValueError(f"U and V must both have shape ({n}, b), not {tuple(t.shape)}")
+        b = int(U.shape[1])
+        for t, name in tensors[:2]:
+            if t.stride(-1) != 1 or (t.shape[0] > 1 and t.stride(0) < b):
+                raise ValueError(f"{name} must have unit stride along its rows")
+        if d_left is not None and (tuple(d_left.shape) != (n,) or not d_left.is_contiguous()):
+            raise ValueError(f"d_left must be a contiguous tensor of {n} words")
+        S = torch.empty((max(length, 0), b, b), dtype=torch.int32, device=U.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.spasm_amd_block_sequence_dev(op._op, int(bool(trans)), b, length, None if d_left is None else C.c_void_p(d_left.data_ptr()),
+                                              C.c_void_p(U.data_ptr()), max(U.stride(0), b), C.c_void_p(V.data_ptr()), max(V.stride(0), b),
+                                              C.c_void_p(S.data_ptr()), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return S
+    for a, name in ((U, "U"), (V, "V")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+            raise TypeError(f"{name} must be an int32 numpy array or torch tensor")
+        if a.ndim != 2 or a.shape[0] != n or a.shape != U.shape:
+            raise ValueError(f"U and V must both have shape ({n}, b), not {a.shape}")
+    b = U.shape[1]
+    Uc, Vc = np.ascontiguousarray(U), np.ascontiguousarray(V)
+    dptr = None
+    if d_left is not None:
+        if not isinstance(d_left, np.ndarray) or d_left.dtype != np.int32 or d_left.shape != (n,):
+            raise TypeError(f"d_left must be an int32 numpy array of {n} words")
+        dl = np.ascontiguousarray(d_left)
+        dptr = dl.ctypes.data
+    S = np.zeros((max(length, 0), b, b), dtype=np.int32)
+    rc = lib.spasm_amd_block_sequence(op._op, int(bool(trans)), int(b), length, dptr, Uc.ctypes.data, b, Vc.ctypes.data, b, S.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error())
+    return S
+
+
+def block_berlekamp_massey(S_, prime):
+    """block_berlekamp_massey(S, prime) -> (F, rowdeg): a left generator of the matrix sequence S (len x b x b integers, b in
+    (2, 4, 8, 16)) mod prime by Berlekamp-Massey over matrix sequences on the device (spasm_amd_block_berlekamp_massey).  F is an
+    int32 array of shape (max(rowdeg) + 1, b, b), F[t] the coefficient of x^t, balanced residues; rowdeg[r] is the degree of row r.
+    For every row r and 0 <= i < len - rowdeg[r]: sum_t F[t, r, :] @ S[i + t] = 0 mod prime; the matrix of the leading row
+    coefficients F[rowdeg[r], r, :] is non-singular; the degrees are minimal.  F is unique only up to row operations: two runs give
+    the same bytes, another implementation may give another F.  The zero sequence gives F = I."""
+    S_ = np.asarray(S_)
+    if S_.dtype.kind not in "iu":
+        raise TypeError("integer entries expected")
+    if S_.ndim != 3 or S_.shape[1] != S_.shape[2]:
+        raise ValueError("a len x b x b array expected")
+    S_ = np.ascontiguousarray(balanced(S_, int(prime)))
+    length, b = int(S_.shape[0]), int(S_.shape[1])
+    coef = np.zeros((length + 1, b, b), dtype=np.int32)
+    rowdeg = np.zeros(max(b, 1), dtype=np.int32)
+    dmax = C.c_int32(0)
+    rc = _abi.lib().spasm_amd_block_berlekamp_massey(b, length, S_.ctypes.data, int(prime), coef.ctypes.data, rowdeg.ctypes.data, C.byref(dmax))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_block_berlekamp_massey failed")
+    return coef[: dmax.value + 1].copy(), rowdeg[:b].copy()
+
+
+def block_wiedemann_det(A, b=8, seed=0, tries=3):
+    """block_wiedemann_det(A, b=8, seed=0, tries=3) -> (det, status): the determinant of the square matrix A mod p as a balanced
+    residue by block Wiedemann, without elimination or fill-in, from about 2 n / b products with A where wiedemann_det takes 2 n.
+    A is a CSR (spasm_amd_block_wiedemann_det), an SpMV operator (spasm_amd_spmv_block_wiedemann_det) or a DeviceCSR
+    (spasm_amd_dcsr_block_wiedemann_det); b is 2, 4, 8 or 16.  status 1: the generator of the block sequence has full degree and
+    det was read off it.  This is a Monte Carlo answer, not a verified one: it is right with a probability that grows with p (and
+    is poor for p = 3), and unlike wiedemann_det nothing proves it, because the block sequence has only about 2 n / b terms.
+    status 0: undecided after `tries` tries with the seeds seed, seed + 1, .. (det is 0 then and says nothing)."""
+    who, fn, arg, _ = _family_target(A, "block_wiedemann_det")
+    det, status = C.c_int32(0), C.c_int32(0)
+    with _quiet(True):
+        rc = fn(arg, int(b), int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), C.byref(det), C.byref(status))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return int(det.value), int(status.value)
+
+
+def block_stats():
+    """Counters of the last block Wiedemann call of this thread (spasm_amd_block_stats), keyed by BLOCK_STATS."""
+    out = (C.c_int64 * 10)()
+    _abi.lib().spasm_amd_block_stats(out)
+    return {k: int(v) for k, v in zip(BLOCK_STATS, out)}
+
+
+SpMV.block_sequence = block_sequence
+SpMV.block_wiedemann_det = block_wiedemann_det
+DeviceCSR.block_wiedemann_det = block_wiedemann_det

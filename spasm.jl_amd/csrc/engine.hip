@@ -10768,6 +10768,8 @@ SPASM_API void spasm_amd_charpoly_split_stats(i64 *out)
 // ------------------------------------------------------------------------------------------------
 #include "krylov.hpp"
 #include "precond.hpp"
+#include "block_krylov.hpp"
+#include "block_bm.hpp"
 
 namespace {
 
@@ -10808,9 +10810,12 @@ int spmv_step_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, 
 
 // The operator B of a projected sequence.  No diagonal: B = A, fwd the view of a square matrix.  dl alone: B = D A, dl the n words
 // of D.  tr: B = E A^T D2 A, fwd and tr the two views of the n x m matrix, dl = D2 (n words), dr = E (m words).
+// block: the sequence is the b x b projection U^T B^i X of block_krylov.hpp (b = K in {2, 4, 8, 16}, B = A or D A, no tr; b * b
+// words a term) and not its diagonal.
 struct SeqOperator {
     const SpmvView *fwd = nullptr, *tr = nullptr;
     const int *dl = nullptr, *dr = nullptr;
+    bool block = false;
     int dim() const { return tr ? fwd->cols : fwd->rows; }
 };
 
@@ -10821,18 +10826,30 @@ int sequence_launch(const SeqOperator &op, const ZpField &F, int kc, i64 len, co
                     hipStream_t s)
 {
     const int hp = (int)F.halfp, mhp = (int)F.mhalfp, dim = op.dim();
+    constexpr bool BLOCKW = KW >= 2 && KW <= 16; // the widths a block sequence has
+    const i64 aw = op.block ? (i64)KW * KW : KW; // sums a term
     int launches = 0;
-    HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * KW * sizeof(long long), s));
+    HIPCHK(hipMemsetAsync(W.acc.p, 0, (size_t)len * aw * sizeof(long long), s));
     if (dim > 0) {
-        hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+        if (op.block) {
+            if constexpr (BLOCKW)
+                hipLaunchKernelGGL((k_block_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0, W.acc.p);
+        } else {
+            hipLaunchKernelGGL((k_krylov_dot<KW>), step_grid((i64)dim * KW, cap), dim3(KRY_BS), 0, s, dim, kc, F, hp, mhp, U, (i64d)ldu, X0, (i64d)ldx0,
+                               W.acc.p);
+        }
         launches++;
     }
     const int *X = X0;
     i64d ldx = (i64d)ldx0;
     int *Y = W.w0.p;
     for (i64 i = 1; i < len && dim > 0; i++) {
-        long long *acc = W.acc.p + i * KW;
-        if (op.tr) {
+        long long *acc = W.acc.p + i * aw;
+        if (op.block) {
+            if constexpr (BLOCKW) launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, Y, (i64d)KW, BlockEpi<KW>{op.dl, U, (i64d)ldu, acc}, cap, s);
+            X = Y;
+            Y = Y == W.w0.p ? W.w1.p : W.w0.p;
+        } else if (op.tr) {
             launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, W.w0.p, (i64d)KW, DiagEpi{op.dl, nullptr, 0, nullptr}, cap, s);
             launches += spmv_step_launch<SMALL, KW>(*op.tr, F, kc, W.w0.p, (i64d)KW, W.w1.p, (i64d)KW, DiagEpi{op.dr, U, (i64d)ldu, acc}, cap, s);
             X = W.w1.p;
@@ -10844,14 +10861,14 @@ int sequence_launch(const SeqOperator &op, const ZpField &F, int kc, i64 len, co
         }
         ldx = KW;
     }
-    const i64 total = len * kc;
-    hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, kc, KW, F, W.acc.p, S);
+    const i64 total = op.block ? len * aw : len * kc;
+    hipLaunchKernelGGL(k_krylov_finish, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, op.block ? (int)aw : kc, (int)aw, F, W.acc.p, S);
     HIPCHK(hipGetLastError());
     return launches + 1;
 }
 
 // S[i * K + c] = sum_r U[r, c] * (B^i X)[r, c], 0 <= i < len, on device arrays, enqueued on s; no host synchronization.
-// 1 <= K <= 64, len >= 1.  Returns the launches.
+// 1 <= K <= 64, len >= 1.  With op.block: S[(i * K + r) * K + c] = sum_k U[k, r] * (B^i X)[k, c].  Returns the launches.
 int sequence_run(const SeqOperator &op, const ZpField &F, int K, i64 len, const int *U, i64 ldu, const int *X, i64 ldx, KrylovWork &W, int *S, hipStream_t s)
 {
     const int kw = spmv_kw(K), cap = step_grid_cap();
@@ -10859,7 +10876,7 @@ int sequence_run(const SeqOperator &op, const ZpField &F, int K, i64 len, const 
         W.w0.ensure((size_t)op.fwd->rows * kw);
         if (op.tr || len > 2) W.w1.ensure((size_t)op.dim() * kw);
     }
-    W.acc.ensure((size_t)len * kw);
+    W.acc.ensure((size_t)len * kw * (op.block ? kw : 1));
     return dispatch_kw(kw, [&](auto KW) {
         return F.small ? sequence_launch<true, KW()>(op, F, K, len, U, ldu, X, ldx, W, S, cap, s)
                        : sequence_launch<false, KW()>(op, F, K, len, U, ldu, X, ldx, W, S, cap, s);
@@ -10968,6 +10985,130 @@ void berlekamp_massey(int count, int len, const spasm_ZZp *S, i64 lds, i64 prime
     st[7] = (i64)(ev.ms(0, 1) * 1000.0);
     memcpy(coef, hc.data(), hc.size() * sizeof(int));
     memcpy(deg, hd.data(), hd.size() * sizeof(int));
+}
+
+// ---- Berlekamp-Massey over matrix sequences (block_bm.hpp)
+int block_width(int b)
+{
+    if (b != 2 && b != 4 && b != 8 && b != 16) throw EngineError("b must be 2, 4, 8 or 16");
+    return b;
+}
+
+// Nothing in k_bbm_disc counts lazy terms, and no len can overrun them: a lane takes at most BBM_CHUNK * 16 of them whatever len
+// is, below the 65043 the i32 accumulator of the largest p < 2^16 holds (zp_lazy_terms; more for smaller primes).  So the i32 lazy
+// limit refuses no len here, unlike bm_check_len; len is bounded by the words of g alone.
+static_assert(BBM_CHUNK * 16 <= 65043, "a lane of k_bbm_disc stays inside the i32 lazy accumulator");
+void block_bm_check_len(i64 len)
+{
+    if (len < 1 || len >= ((i64)1 << 24)) throw EngineError("len out of range (1 <= len < 2^24)");
+}
+
+// the device state of one matrix Berlekamp-Massey run, kept from one try to the next
+struct BlockBmWork {
+    DevBuf<int> g0, g1, small;
+    DevBuf<long long> dacc;
+    BbmState st;
+    void ensure(int b, int len)
+    {
+        const size_t r = 2 * (size_t)b, words = ((size_t)len + 2) * r * b;
+        g0.ensure(words);
+        g1.ensure(words);
+        dacc.ensure(r * b);
+        small.ensure(r * b + r * r + 2 * r + 1 + b);
+        st.g[0] = g0.p;
+        st.g[1] = g1.p;
+        st.dacc = dacc.p;
+        st.hk = small.p;
+        st.T = st.hk + r * b;
+        st.deg = st.T + r * r;
+        st.piv = st.deg + r;
+        st.maxdeg = st.piv + r;
+        st.sel = st.maxdeg + 1;
+    }
+};
+
+template <bool SMALL, int B>
+int block_bm_launch(const ZpField &F, int len, const int *dS, BlockBmWork &W, int *d_coef, int *d_rowdeg, int *d_dmax, hipStream_t s)
+{
+    constexpr int R = 2 * B;
+    const size_t words = ((size_t)len + 2) * R * B;
+    HIPCHK(hipMemsetAsync(W.st.g[0], 0, words * sizeof(int), s));
+    HIPCHK(hipMemsetAsync(W.st.g[1], 0, words * sizeof(int), s));
+    hipLaunchKernelGGL((k_bbm_init<B>), dim3(1), dim3(BBM_BS), 0, s, W.st);
+    int cur = 0;
+    for (int k = 0; k < len; k++) {
+        hipLaunchKernelGGL((k_bbm_disc<SMALL, B>), dim3(cdiv((i64)k + 1, BBM_CHUNK)), dim3(BBM_DISC_BS), 0, s, k, F, dS, W.st.g[cur], W.st.maxdeg, W.st.dacc);
+        hipLaunchKernelGGL((k_bbm_elim<B>), dim3(1), dim3(BBM_BS), 0, s, F, W.st);
+        hipLaunchKernelGGL((k_bbm_update<SMALL, B>), dim3(cdiv(((i64)k + 2) * R * B, BBM_BS)), dim3(BBM_BS), 0, s, k, F, W.st.g[cur], W.st.g[cur ^ 1], W.st.T,
+                           W.st.piv, W.st.maxdeg);
+        cur ^= 1;
+    }
+    hipLaunchKernelGGL((k_bbm_select<B>), dim3(1), dim3(BBM_BS), 0, s, F, W.st, W.st.g[cur], d_rowdeg, d_dmax);
+    const i64 total = ((i64)len + 1) * B * B;
+    hipLaunchKernelGGL((k_bbm_write<B>), dim3(cdiv(total, BBM_BS)), dim3(BBM_BS), 0, s, (i64d)total, W.st.g[cur], W.st.sel, d_rowdeg, d_coef);
+    HIPCHK(hipGetLastError());
+    return 3 * len + 3;
+}
+
+// The left generator of the len terms dS (b * b words a term) -> d_coef ((len + 1) * b * b words, F_t at t * b * b), d_rowdeg (b),
+// d_dmax (1), all on the device; enqueued on s, no host synchronization.  Returns the launches.
+int block_bm_device(const ZpField &F, int b, int len, const int *dS, BlockBmWork &W, int *d_coef, int *d_rowdeg, int *d_dmax, hipStream_t s)
+{
+    W.ensure(b, len);
+    auto go = [&](auto B) {
+        return F.small ? block_bm_launch<true, B()>(F, len, dS, W, d_coef, d_rowdeg, d_dmax, s)
+                       : block_bm_launch<false, B()>(F, len, dS, W, d_coef, d_rowdeg, d_dmax, s);
+    };
+    switch (b) {
+    case 2: return go(std::integral_constant<int, 2>());
+    case 4: return go(std::integral_constant<int, 4>());
+    case 8: return go(std::integral_constant<int, 8>());
+    default: return go(std::integral_constant<int, 16>());
+    }
+}
+
+// b, len, steps of the sequence, launches, sum of the row degrees, tries used, device us of the sequence, device us of
+// Berlekamp-Massey, n, largest row degree
+thread_local i64 g_block_stats[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+
+void block_stats_reset() { memset(g_block_stats, 0, sizeof g_block_stats); }
+
+void block_berlekamp_massey(int b, int len, const spasm_ZZp *S, i64 prime, spasm_ZZp *coef, int *rowdeg, int *dmax)
+{
+    block_stats_reset();
+    block_width(b);
+    check_prime(prime);
+    if ((prime & 1) == 0) throw EngineError("prime must be odd");
+    const ZpField F = zp_field_make(prime);
+    block_bm_check_len(len);
+    if (!S || !coef || !rowdeg || !dmax) throw EngineError("NULL array");
+    require_device();
+    hipStream_t s = nullptr;
+    const size_t bb = (size_t)b * b;
+    DevBuf<int> dS, d_coef, d_small;
+    BlockBmWork W;
+    dS.alloc((size_t)len * bb);
+    d_coef.alloc(((size_t)len + 1) * bb);
+    d_small.alloc((size_t)b + 1);
+    HIPCHK(hipMemcpyAsync(dS.p, S, (size_t)len * bb * sizeof(int), hipMemcpyHostToDevice, s));
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    const int launches = block_bm_device(F, b, len, dS.p, W, d_coef.p, d_small.p, d_small.p + b, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> hc(((size_t)len + 1) * bb), hs((size_t)b + 1);
+    HIPCHK(hipMemcpyAsync(hc.data(), d_coef.p, hc.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(hs.data(), d_small.p, hs.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memcpy(coef, hc.data(), hc.size() * sizeof(int));
+    memcpy(rowdeg, hs.data(), (size_t)b * sizeof(int));
+    *dmax = hs[(size_t)b];
+    i64 *st = g_block_stats;
+    st[0] = b;
+    st[1] = len;
+    st[3] = launches;
+    for (int r = 0; r < b; r++) st[4] += rowdeg[r];
+    st[7] = (i64)(ev.ms(0, 1) * 1000.0);
+    st[9] = *dmax;
 }
 
 // ---- polynomials over GF(p) on the host, as residues in [0, p), low degree first, no zero leading word (the zero polynomial is empty)
@@ -12084,6 +12225,261 @@ SPASM_API int spasm_amd_dcsr_wiedemann_det(const spasm_amd_dcsr *D, int K, uint6
 SPASM_API void spasm_amd_precond_stats(i64 *out)
 {
     if (out) memcpy(out, g_precond_stats, sizeof g_precond_stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Block Wiedemann (block_krylov.hpp, block_bm.hpp): the b x b projected sequence of A, A^T or D A, its left generator by
+// Berlekamp-Massey over matrix sequences, and the determinant from the generator.
+// ------------------------------------------------------------------------------------------------
+namespace {
+
+// what a block sequence adds to the terms the generic case needs (2 * ceil(n / b)): the two terms of sequence_terms
+constexpr int BLOCK_SLACK = 2;
+
+int block_terms(int n, int b) { return 2 * ((n + b - 1) / b) + BLOCK_SLACK; }
+
+void block_sequence_check(const spasm_amd_spmv *op, int trans, int b, i64 len, const void *U, i64 ldu, const void *V, i64 ldv, const void *S)
+{
+    if (!op) throw EngineError("NULL operator");
+    block_width(b);
+    require_square(-1, op->A.n, op->A.m);
+    if (len < 1 || len >= ((i64)1 << 24)) throw EngineError("len out of range (1 <= len < 2^24)");
+    if (ldu < b || ldv < b || (trans != 0 && trans != 1)) throw EngineError("bad arguments (trans 0/1, ldu >= b, ldv >= b)");
+    if (!S || (op->A.n > 0 && (!U || !V))) throw EngineError("NULL array");
+}
+
+// a zero word (mod p) of the caller's diagonal is refused: D must be invertible
+void block_diagonal_check(const int *d, int n, i64 prime)
+{
+    for (int i = 0; i < n; i++)
+        if ((i64)d[i] % prime == 0) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "d_left[%d] is zero mod p", i);
+            throw EngineError(msg);
+        }
+}
+
+// the b x b determinant mod p of residues in [0, p), by elimination on the host (exact: products of two residues fit a u64)
+uint64_t hdet_small(std::vector<uint64_t> a, int b, uint64_t p)
+{
+    uint64_t det = 1;
+    for (int c = 0; c < b; c++) {
+        int piv = -1;
+        for (int r = c; r < b && piv < 0; r++)
+            if (a[(size_t)r * b + c] != 0) piv = r;
+        if (piv < 0) return 0;
+        if (piv != c) {
+            for (int k = 0; k < b; k++) std::swap(a[(size_t)piv * b + k], a[(size_t)c * b + k]);
+            det = (p - det) % p;
+        }
+        const uint64_t pv = a[(size_t)c * b + c], inv = hinv(pv, p);
+        det = det * pv % p;
+        for (int r = c + 1; r < b; r++) {
+            const uint64_t f = a[(size_t)r * b + c] * inv % p;
+            if (f == 0) continue;
+            const uint64_t nf = p - f;
+            for (int k = c; k < b; k++) a[(size_t)r * b + k] = (a[(size_t)r * b + k] + nf * a[(size_t)c * b + k]) % p;
+        }
+    }
+    return det;
+}
+
+// The determinant behind the three entries: V is the view of the square matrix, n > 0.  Per try: D and U, V of the seed, the
+// block sequence of D A with block_terms(n, b) terms, its generator F; when the row degrees sum to n,
+// det A = (-1)^n det F_0 / det(leading row coefficients) / prod d_i.  Monte Carlo: see the header.
+void block_det_run(const SpmvView &V, const ZpField &F, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    const int n = V.rows;
+    const uint64_t p = (uint64_t)F.p;
+    const int len = block_terms(n, b);
+    block_bm_check_len(len);
+    hipStream_t s = nullptr;
+    const size_t nb = (size_t)n * b, bb = (size_t)b * b;
+    std::vector<int> hu(nb), hv(nb), diag((size_t)n), hdeg((size_t)b + 1), row((size_t)b);
+    DevBuf<int> dU, dV, dl, dS, d_coef, d_small;
+    KrylovWork W;
+    BlockBmWork BW;
+    SpgEvents ev;
+    dU.alloc(nb);
+    dV.alloc(nb);
+    dl.alloc((size_t)n);
+    dS.alloc((size_t)len * bb);
+    d_coef.alloc(((size_t)len + 1) * bb);
+    d_small.alloc((size_t)b + 1);
+    i64 *st = g_block_stats;
+    st[0] = b;
+    st[1] = len;
+    st[8] = n;
+    const int ntries = precond_tries(tries);
+    *det = 0;
+    *status = 0;
+    for (int t = 0; t < ntries; t++) {
+        const uint64_t sd = seed + (uint64_t)t;
+        minpoly_vectors(n, b, sd, F.p, hu.data(), hv.data());
+        precond_diagonal(n, sd, 0, F.p, diag.data());
+        HIPCHK(hipMemcpyAsync(dU.p, hu.data(), nb * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dV.p, hv.data(), nb * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl.p, diag.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        SeqOperator op{&V, nullptr, dl.p, nullptr};
+        op.block = true;
+        int launches = sequence_run(op, F, b, len, dU.p, b, dV.p, b, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        launches += block_bm_device(F, b, len, dS.p, BW, d_coef.p, d_small.p, d_small.p + b, s);
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        HIPCHK(hipMemcpyAsync(hdeg.data(), d_small.p, hdeg.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        i64 sum = 0;
+        for (int r = 0; r < b; r++) sum += hdeg[(size_t)r];
+        st[2] += len - 1;
+        st[3] += launches;
+        st[4] = sum;
+        st[5]++;
+        st[6] += (i64)(ev.ms(0, 1) * 1000.0);
+        st[7] += (i64)(ev.ms(1, 2) * 1000.0);
+        st[9] = hdeg[(size_t)b];
+        if (sum != n) continue;
+        // F_0 is term 0 of coef; the leading coefficient of row r is row r of term rowdeg[r]
+        std::vector<uint64_t> f0(bb), lc(bb);
+        std::vector<int> h0(bb);
+        HIPCHK(hipMemcpy(h0.data(), d_coef.p, bb * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < bb; e++) f0[e] = hresidue(h0[e], p);
+        for (int r = 0; r < b; r++) {
+            HIPCHK(hipMemcpy(row.data(), d_coef.p + ((size_t)hdeg[(size_t)r] * b + r) * b, (size_t)b * sizeof(int), hipMemcpyDeviceToHost));
+            for (int c = 0; c < b; c++) lc[(size_t)r * b + c] = hresidue(row[(size_t)c], p);
+        }
+        const uint64_t dlc = hdet_small(lc, b, p);
+        if (dlc == 0) continue; // cannot happen (the generator is row-reduced); try the next seed rather than divide by it
+        uint64_t prod = 1;
+        for (int i = 0; i < n; i++) prod = prod * hresidue(diag[(size_t)i], p) % p;
+        uint64_t v = hdet_small(f0, b, p) * hinv(dlc, p) % p * hinv(prod, p) % p;
+        if (n & 1) v = (p - v) % p;
+        *det = hbalanced(v, p);
+        *status = 1;
+        return;
+    }
+}
+
+int block_det_entry(Operand &&o, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    block_stats_reset();
+    o.check();
+    require_square(-1, o.n, o.m);
+    block_width(b);
+    if (!det || !status) throw EngineError("NULL array");
+    precond_limits(o.n, o.m);
+    if (o.n == 0) { *det = 1; *status = 1; return 0; }
+    o.views(true, false);
+    spasm_ZZp v = 0;
+    int st = 0;
+    block_det_run(*o.fwd, o.F, b, seed, tries, &v, &st);
+    *det = v;
+    *status = st;
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- block Wiedemann (block_krylov.hpp, block_bm.hpp; engine extension) ----
+SPASM_API int spasm_amd_block_sequence(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *U, i64 ldu,
+                                       const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    return abi_call("spasm_amd_block_sequence", -1, [&] {
+        block_stats_reset();
+        block_sequence_check(op, trans, b, len, U, ldu, V, ldv, S);
+        const size_t n = (size_t)op->A.n, kk = (size_t)b, bb = kk * kk;
+        if (d_left) block_diagonal_check(d_left, (int)n, op->F.p);
+        if (n == 0) { memset(S, 0, (size_t)len * bb * sizeof(int)); return 0; }
+        DeviceGuard g(op);
+        if (trans) op->build_transpose();
+        hipStream_t s = nullptr;
+        DevBuf<int> dU, dV, dS, dl;
+        KrylovWork W;
+        dU.alloc(n * kk);
+        dV.alloc(n * kk);
+        dS.alloc((size_t)len * bb);
+        HIPCHK(hipMemcpy2DAsync(dU.p, kk * sizeof(int), U, (size_t)ldu * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(dV.p, kk * sizeof(int), V, (size_t)ldv * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+        if (d_left) {
+            dl.alloc(n);
+            HIPCHK(hipMemcpyAsync(dl.p, d_left, n * sizeof(int), hipMemcpyHostToDevice, s));
+        }
+        SpgEvents ev;
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        SeqOperator sq{trans ? &op->tr : &op->fwd, nullptr, d_left ? dl.p : nullptr, nullptr};
+        sq.block = true;
+        const int launches = sequence_run(sq, op->F, b, len, dU.p, b, dV.p, b, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        std::vector<int> out((size_t)len * bb);
+        HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        i64 *st = g_block_stats;
+        st[0] = b;
+        st[1] = len;
+        st[2] = len - 1;
+        st[3] = launches;
+        st[6] = (i64)(ev.ms(0, 1) * 1000.0);
+        st[8] = (i64)n;
+        memcpy(S, out.data(), out.size() * sizeof(int));
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_block_sequence_dev(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *U, i64 ldu,
+                                           const spasm_ZZp *V, i64 ldv, spasm_ZZp *S, void *stream)
+{
+    return abi_call("spasm_amd_block_sequence_dev", -1, [&] {
+        block_stats_reset();
+        block_sequence_check(op, trans, b, len, U, ldu, V, ldv, S);
+        DeviceGuard g(op);
+        hipStream_t s = (hipStream_t)stream;
+        if (op->A.n == 0) {
+            HIPCHK(hipMemsetAsync(S, 0, (size_t)len * b * b * sizeof(int), s));
+            return 0;
+        }
+        if (trans) op->build_transpose();
+        SeqOperator sq{trans ? &op->tr : &op->fwd, nullptr, d_left, nullptr};
+        sq.block = true;
+        const int launches = sequence_run(sq, op->F, b, len, U, ldu, V, ldv, op->kry, S, s);
+        if (!stream) HIPCHK(hipStreamSynchronize(s));
+        i64 *st = g_block_stats;
+        st[0] = b;
+        st[1] = len;
+        st[2] = len - 1;
+        st[3] = launches;
+        st[8] = op->A.n;
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_block_berlekamp_massey(int b, int len, const spasm_ZZp *S, i64 prime, spasm_ZZp *coef, int *rowdeg, int *dmax)
+{
+    return abi_call("spasm_amd_block_berlekamp_massey", -1, [&] { DeviceGuard g; block_berlekamp_massey(b, len, S, prime, coef, rowdeg, dmax); return 0; });
+}
+
+SPASM_API int spasm_amd_block_wiedemann_det(const struct spasm_csr *A, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_block_wiedemann_det", -1,
+                    [&] { return block_det_entry(Operand(A, "spasm_amd_block_wiedemann_det"), b, seed, tries, det, status); });
+}
+
+SPASM_API int spasm_amd_spmv_block_wiedemann_det(spasm_amd_spmv *op, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_spmv_block_wiedemann_det", -1, [&] { return block_det_entry(Operand(op), b, seed, tries, det, status); });
+}
+
+SPASM_API int spasm_amd_dcsr_block_wiedemann_det(const spasm_amd_dcsr *D, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status)
+{
+    return abi_call("spasm_amd_dcsr_block_wiedemann_det", -1, [&] { return block_det_entry(Operand(D), b, seed, tries, det, status); });
+}
+
+SPASM_API void spasm_amd_block_stats(i64 *out)
+{
+    if (out) memcpy(out, g_block_stats, sizeof g_block_stats);
 }
 
 } // extern "C"

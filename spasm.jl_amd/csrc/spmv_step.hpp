@@ -18,6 +18,13 @@
 //                                     y0 is the canonical (A X)[row, v] and c = coef(v): stores the entry at yp, returns its term;
 //   bool projects() const             whether the terms are summed at all;
 //   long long *sums() const           where: KW words, |sum| < 2^62.
+// An epilogue that returns B > 1 terms per entry (the b x b projection of block_krylov.hpp) names B in EpiTerms and has instead
+//   void own(F, hp, mhp, row, v, y0, yp, long long (&t)[B]) const
+//                                     stores the entry at yp and adds its B terms to t[0 .. B);
+//   template <int KW> void project(long long (&t)[B]) const
+//                                     sums t over the workgroup and adds the sums to global memory (every lane calls it).
+// The one-term epilogues do not name EpiTerms and compile to what they compiled to before it existed: the branch is taken at
+// compile time (profiles/block_wiedemann_asm_diff.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zp.hpp"
@@ -45,6 +52,9 @@ template <int KW> __device__ __forceinline__ void krylov_project(long long t, lo
     }
 }
 
+// the terms an epilogue returns per entry of Y: 1 unless it says otherwise
+template <class Epi> struct EpiTerms { static constexpr int value = 1; };
+
 // One team of TEAM lanes per work item (SPMV_TEAM_SUM); a team strides over the items of its class.  Not PARTIAL: the epilogue
 // gets the row's sum.  PARTIAL: part[it * KW + v] <- the segment's sum, no epilogue.
 template <bool SMALL, int KW, int TEAM, bool PARTIAL, class Epi>
@@ -54,19 +64,32 @@ __global__ __launch_bounds__(KRY_BS) void k_spmv_step(int nitems, const int *__r
                                                       i64d ldy, int *__restrict__ part, Epi epi)
 {
     constexpr int TPB = KRY_BS / TEAM;
+    constexpr int NT = EpiTerms<Epi>::value;
     const SpmvLane<KW, TEAM> L(kc);
-    const int c = (!PARTIAL && L.vok) ? epi.coef(L.v) : 0;
-    long long t = 0;
-    // whole teams leave the loop together: the shuffles stay inside a team
-    for (i64d it = (i64d)blockIdx.x * TPB + threadIdx.x / TEAM; it < nitems; it += (i64d)gridDim.x * TPB) {
-        SPMV_TEAM_SUM(row, r, it);
-        if (L.e == 0 && L.vok) {
-            const int y0 = zp_reduce(F, (int64_t)r);
-            if (PARTIAL) part[it * KW + L.v] = y0;
-            else t += epi.own(F, hp, mhp, c, row, L.v, y0, Y + (i64d)row * ldy + L.v);
+    if constexpr (PARTIAL || NT == 1) {
+        // (a segment launch never consults the epilogue, of either kind)
+        int c = 0;
+        if constexpr (!PARTIAL) c = L.vok ? epi.coef(L.v) : 0;
+        long long t = 0;
+        // whole teams leave the loop together: the shuffles stay inside a team
+        for (i64d it = (i64d)blockIdx.x * TPB + threadIdx.x / TEAM; it < nitems; it += (i64d)gridDim.x * TPB) {
+            SPMV_TEAM_SUM(row, r, it);
+            if (L.e == 0 && L.vok) {
+                const int y0 = zp_reduce(F, (int64_t)r);
+                if constexpr (PARTIAL) part[it * KW + L.v] = y0;
+                else t += epi.own(F, hp, mhp, c, row, L.v, y0, Y + (i64d)row * ldy + L.v);
+            }
         }
+        if constexpr (!PARTIAL)
+            if (epi.projects()) krylov_project<KW>(t, epi.sums());
+    } else {
+        long long t[NT] = {};
+        for (i64d it = (i64d)blockIdx.x * TPB + threadIdx.x / TEAM; it < nitems; it += (i64d)gridDim.x * TPB) {
+            SPMV_TEAM_SUM(row, r, it);
+            if (L.e == 0 && L.vok) epi.own(F, hp, mhp, row, L.v, zp_reduce(F, (int64_t)r), Y + (i64d)row * ldy + L.v, t);
+        }
+        epi.template project<KW>(t);
     }
-    if (!PARTIAL && epi.projects()) krylov_project<KW>(t, epi.sums());
 }
 
 // the long rows: row rows[l] owns the segments off[l] .. off[l+1]-1; one lane per (row, column); y is complete here, so the
@@ -77,16 +100,30 @@ __global__ __launch_bounds__(KRY_BS) void k_spmv_step_combine(int nlong, const i
                                                               int *__restrict__ Y, i64d ldy, Epi epi)
 {
     constexpr int RPB = KRY_BS / KW;
+    constexpr int NT = EpiTerms<Epi>::value;
     const int v = threadIdx.x % KW;
-    long long t = 0;
-    if (v < kc) {
-        const int c = epi.coef(v);
-        for (i64d l = (i64d)blockIdx.x * RPB + threadIdx.x / KW; l < nlong; l += (i64d)gridDim.x * RPB) {
-            int64_t s = 0; // |s| <= (2^31 / SPMV_SEG) * 2^31 < 2^48: exact
-            for (int it = off[l]; it < off[l + 1]; it++) s += part[(i64d)it * KW + v];
-            const int row = rows[l];
-            t += epi.own(F, hp, mhp, c, row, v, zp_reduce(F, s), Y + (i64d)row * ldy + v);
+    if constexpr (NT == 1) {
+        long long t = 0;
+        if (v < kc) {
+            const int c = epi.coef(v);
+            for (i64d l = (i64d)blockIdx.x * RPB + threadIdx.x / KW; l < nlong; l += (i64d)gridDim.x * RPB) {
+                int64_t s = 0; // |s| <= (2^31 / SPMV_SEG) * 2^31 < 2^48: exact
+                for (int it = off[l]; it < off[l + 1]; it++) s += part[(i64d)it * KW + v];
+                const int row = rows[l];
+                t += epi.own(F, hp, mhp, c, row, v, zp_reduce(F, s), Y + (i64d)row * ldy + v);
+            }
         }
+        if (epi.projects()) krylov_project<KW>(t, epi.sums());
+    } else {
+        long long t[NT] = {};
+        if (v < kc) {
+            for (i64d l = (i64d)blockIdx.x * RPB + threadIdx.x / KW; l < nlong; l += (i64d)gridDim.x * RPB) {
+                int64_t s = 0; // as above
+                for (int it = off[l]; it < off[l + 1]; it++) s += part[(i64d)it * KW + v];
+                const int row = rows[l];
+                epi.own(F, hp, mhp, row, v, zp_reduce(F, s), Y + (i64d)row * ldy + v, t);
+            }
+        }
+        epi.template project<KW>(t);
     }
-    if (epi.projects()) krylov_project<KW>(t, epi.sums());
 }
