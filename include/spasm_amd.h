@@ -1148,6 +1148,55 @@ int spasm_amd_spmv_block_wiedemann_det(spasm_amd_spmv *op, int b, uint64_t seed,
 int spasm_amd_dcsr_block_wiedemann_det(const spasm_amd_dcsr *D, int b, uint64_t seed, int tries, spasm_ZZp *det, int *status);
 void spasm_amd_block_stats(i64 *out);   /* of the last block Wiedemann call of this thread */
 
+/* ---- block Horner and the block Wiedemann solve (engine extension; csrc/block_horner.hpp) ----
+ * A solve from the block sequence above: about 2 n / b products for the sequence and n / b for block Horner, where
+ * spasm_amd_wiedemann_solve takes 2 n and up to n, and one run serves up to b right-hand sides.  b is 2, 4, 8 or 16.
+ *   block_poly_apply  op is a resident SQUARE operator; coef, V (n x b, ldv >= b) and X (n x K, ldx >= K, 1 <= K <= b) are HOST
+ *                 arrays, any int32 is reduced where it is read.  X <- sum_{t=0}^{D} op(A)^t V C_t mod p as balanced residues,
+ *                 C_t[c, j] = coef[(t * b + c) * K + j] (b x K), op(A) = A (trans 0) or A^T (trans 1); -1 <= D < 2^24 and
+ *                 D = -1 gives X = 0 (coef may be NULL then).  Block Horner: Y <- op(A) Y + V C_s for s = D .. 0, the first
+ *                 step without a product, so D products; one launch set per step (the step kernels of the resident product
+ *                 with the b x K combination as epilogue).  V must not overlap X.  n = 0 returns at once.
+ *   block_poly_apply_dev  the same on DEVICE arrays V and X of the operator's device (coef stays a HOST array), enqueued on stream
+ *                 (NULL: the null stream) without a host synchronization, like poly_apply_dev.
+ *   block_wiedemann_solve, spmv_block_wiedemann_solve, dcsr_block_wiedemann_solve
+ *                 A host matrix, a resident operator, a resident matrix; A must be square, n < 2^24.  B (n x K, ldb >= K,
+ *                 1 <= K <= b) and X (n x K, ldx >= K) are HOST arrays.  Solves op(A) x = b_j for every column of B; trans = 1
+ *                 solves x A = b on the transposed view.  tries <= 0 means 3.  Try t takes U, Z = minpoly_vectors(n, b,
+ *                 seed + t, p), overwrites the leading columns of Z by the undecided right-hand sides (packed in their order):
+ *                 V = [B | Z]; the block sequence S_i = U^T op(A)^i V of len = 2 * ceil(n / b) + 2 terms; the left generator F of
+ *                 the transposed terms S_i^T (block_berlekamp_massey on the device), so sum_t S_{i+t} F_t^T = 0; Gauss-Jordan
+ *                 on [F_0 | I] (host, b^3).  Column j is regular when e_j lies in the row space of F_0: lambda F_0 = e_j; else
+ *                 lambda is the (j mod nullity)-th vector of the left null space of F_0 in the order the elimination leaves
+ *                 them.  With h = lambda F: x_j = -sum_{s < D} op(A)^s V h_{s+1}^T, D the largest row degree, by one block
+ *                 Horner run for all undecided columns.  Then ONE more product forms r_j = op(A) x_j - b_j on the regular columns
+ *                 and op(A) x_j on the others, and the non-zeros of x_j and r_j are counted on the device.
+ *                 status[j] = 1: regular and r_j = 0, op(A) x_j = b_j IS PROVED;  2: not regular, r_j = 0 and x_j != 0, a proved
+ *                 non-zero kernel vector (A is singular; nothing is said about b_j);  0: undecided after the last try, the column
+ *                 of X is zero.  Undecided columns are retried with the next seed.  Nothing is written to X or status before
+ *                 the last try has run.  n = 0: status 1 everywhere, no device needed.
+ *   solve_stats   of the last of these calls of this thread: out[16] = n, b, K, len, tries used, products with A (all), those of
+ *                 the sequences ((len - 1) a try), those of Horner and the check (max(D - 1, 0) + 1 a try; D for block_poly_apply),
+ *                 launches, sum of the row degrees (last try), largest row degree, columns solved, columns with a kernel vector,
+ *                 device microseconds of the sequences, of Berlekamp-Massey, of Horner + check (HIP events).  Every call clears
+ *                 what it does not fill.  spasm_amd_block_stats keeps its ten slots and is not touched by these calls.
+ *   deterministic two runs give the same bytes (the counts and projections add integers)
+ *   errors        "b must be 2, 4, 8 or 16", "K out of range (1 <= K <= b)", "trans must be 0 or 1", "D out of range
+ *                 (-1 <= D < 2^24)", "ldv < b", "ldb < K", "ldx < K", a NULL operator / matrix / array, a matrix that is not
+ *                 square ("not square (3 x 2)"), "V must not overlap X", n >= 2^24, len outside 1 .. 2^24 - 1, no device
+ *                 ("no HIP device"), out of memory: -1, NO output word is written, spasm_amd_last_error() names the cause. */
+int spasm_amd_block_poly_apply(spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const spasm_ZZp *V, i64 ldv,
+                               spasm_ZZp *X, i64 ldx);
+int spasm_amd_block_poly_apply_dev(spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const spasm_ZZp *V, i64 ldv,
+                                   spasm_ZZp *X, i64 ldx, void *stream);
+int spasm_amd_block_wiedemann_solve(const struct spasm_csr *A, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                    spasm_ZZp *X, i64 ldx, int *status);
+int spasm_amd_spmv_block_wiedemann_solve(spasm_amd_spmv *op, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                         spasm_ZZp *X, i64 ldx, int *status);
+int spasm_amd_dcsr_block_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                         spasm_ZZp *X, i64 ldx, int *status);
+void spasm_amd_block_solve_stats(i64 *out);   /* of the last block Horner / block Wiedemann solve call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -2527,3 +2527,96 @@ def block_stats():
 SpMV.block_sequence = block_sequence
 SpMV.block_wiedemann_det = block_wiedemann_det
 DeviceCSR.block_wiedemann_det = block_wiedemann_det
+
+
+# ---------------------------------------------------------------------------------------------
+# Block Horner and the block Wiedemann solve  (spasm_amd_block_poly_apply*, _block_wiedemann_solve*; csrc/block_horner.hpp)
+# ---------------------------------------------------------------------------------------------
+BLOCK_SOLVE_STATS = ("n", "b", "K", "len", "tries", "products", "sequence_products", "horner_products", "launches", "degree_sum",
+                     "max_degree", "solved", "kernel_vectors", "sequence_device_us", "bm_device_us", "horner_device_us")
+
+
+def block_poly_apply(op, coef, V, trans=False):
+    """block_poly_apply(op, C, V, trans=False) -> X = sum_t A^t V C[t] mod p as balanced residues, n x K: A the square matrix of
+    the SpMV operator op (A^T with trans=True), V n x b with b in (2, 4, 8, 16), C an integer array of shape (D + 1, b, K) with
+    1 <= K <= b (any int32; D + 1 = 0 gives X = 0).  int32 numpy arrays (spasm_amd_block_poly_apply) or V an int32 torch tensor
+    on the current device (enqueued on the current stream without a host synchronization; X is a tensor:
+    spasm_amd_block_poly_apply_dev).  Block Horner: D products with A, each followed by the b x K combination.  V is not modified."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n = op.shape[0]
+    Cc = np.asarray(coef)
+    if Cc.ndim != 3:
+        raise ValueError("C must have shape (D + 1, b, K)")
+    if Cc.size and (Cc.dtype.kind not in "iu" or Cc.min() < -2**31 or Cc.max() > 2**31 - 1):
+        raise TypeError("the coefficients must be integers that fit int32")
+    Cc = np.ascontiguousarray(Cc, dtype=np.int32)
+    D, b, k = int(Cc.shape[0]) - 1, int(Cc.shape[1]), int(Cc.shape[2])
+    is_torch = type(V).__module__.startswith("torch")
+    ndim = V.dim() if is_torch else getattr(V, "ndim", 0)
+    if ndim != 2 or tuple(V.shape) != (n, b):
+        raise ValueError(f"V must have shape ({n}, {b})")
+    lib = _abi.lib()
+    cptr = Cc.ctypes.data if Cc.size else None
+    if is_torch:
+        import torch
+
+        if V.dtype != torch.int32 or V.device.type != "cuda" or V.device.index != torch.cuda.current_device():
+            raise TypeError("V must be an int32 tensor on the current device")
+        if V.stride(-1) != 1 or (V.shape[0] > 1 and V.stride(0) < b):
+            raise ValueError("V must have unit stride along its rows")
+        X = torch.empty((n, k), dtype=torch.int32, device=V.device)
+        stream = torch.cuda.current_stream().cuda_stream
+        rc = lib.spasm_amd_block_poly_apply_dev(op._op, int(bool(trans)), b, k, D, cptr, C.c_void_p(V.data_ptr()), max(V.stride(0), b),
+                                                C.c_void_p(X.data_ptr()), max(k, 1), C.c_void_p(stream) if stream else None)
+        if rc != 0:
+            raise SpasmError(_abi.last_error())
+        return X
+    if not isinstance(V, np.ndarray) or V.dtype != np.int32:
+        raise TypeError("V must be an int32 numpy array or torch tensor")
+    Vc = np.ascontiguousarray(V)
+    X = np.zeros((n, k), dtype=np.int32)
+    rc = lib.spasm_amd_block_poly_apply(op._op, int(bool(trans)), b, k, D, cptr, Vc.ctypes.data, b, X.ctypes.data, max(k, 1))
+    if rc != 0:
+        raise SpasmError(_abi.last_error())
+    return X
+
+
+def block_wiedemann_solve(A, B, b=8, trans=False, seed=0, tries=3):
+    """block_wiedemann_solve(A, B, b=8, trans=False, seed=0, tries=3) -> (X, status): A x = b (x A = b with trans=True) for every
+    column of B by block Wiedemann, without elimination or fill-in, from about 3 n / b products with A where wiedemann_solve takes
+    up to 3 n.  A is a square CSR (spasm_amd_block_wiedemann_solve), an SpMV operator (spasm_amd_spmv_block_wiedemann_solve) or a
+    DeviceCSR (spasm_amd_dcsr_block_wiedemann_solve); the block width b is 2, 4, 8 or 16.  B is n x K, 1 <= K <= b, or n entries:
+    one right-hand side (X then has n entries).  X is int32, balanced residues; status is an int32 array, one per column:
+    1  solved, A x = b verified on the device by one more product;  2  the column of X is a non-zero vector of the kernel of A,
+    verified the same way (nothing is said about b);  0  undecided after `tries` tries with the seeds seed, seed + 1, .. (the
+    column of X is zero).  Statuses 1 and 2 are proofs, not Monte Carlo answers: the residual is computed."""
+    who, fn, arg, n = _family_target(A, "block_wiedemann_solve")
+    if not isinstance(B, np.ndarray) or B.dtype != np.int32 or B.ndim not in (1, 2) or B.shape[0] != n:
+        raise TypeError(f"B must be an int32 numpy array of shape ({n},) or ({n}, K)")
+    k = 1 if B.ndim == 1 else B.shape[1]
+    Bc = _rows_view(B, "B") if n > 0 else B   # (numpy gives an array without rows strides of its own)
+    ldb = k if B.ndim == 1 or n == 0 else max(Bc.strides[0] // 4, k)
+    X = np.zeros(B.shape, dtype=np.int32)
+    status = np.zeros(max(k, 1), dtype=np.int32)
+    with _quiet(True):
+        rc = fn(arg, int(bool(trans)), int(b), int(k), Bc.ctypes.data, ldb, int(seed) & 0xFFFFFFFFFFFFFFFF, int(tries), X.ctypes.data, max(k, 1),
+                status.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return X, status[:k]
+
+
+def block_solve_stats():
+    """Counters of the last block_poly_apply / block_wiedemann_solve call of this thread (spasm_amd_block_solve_stats), keyed by
+    BLOCK_SOLVE_STATS."""
+    out = (C.c_int64 * len(BLOCK_SOLVE_STATS))()
+    _abi.lib().spasm_amd_block_solve_stats(out)
+    return {k: int(v) for k, v in zip(BLOCK_SOLVE_STATS, out)}
+
+
+SpMV.block_poly_apply = block_poly_apply
+SpMV.block_wiedemann_solve = block_wiedemann_solve
+DeviceCSR.block_wiedemann_solve = block_wiedemann_solve

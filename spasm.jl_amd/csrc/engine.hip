@@ -12483,3 +12483,419 @@ SPASM_API void spasm_amd_block_stats(i64 *out)
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Block Wiedemann solve (block_horner.hpp): a matrix polynomial applied to a block of vectors by block Horner steps, and on top of
+// it sparse solves from the right generator of a block sequence that certify their own answers.
+// ------------------------------------------------------------------------------------------------
+#include "block_horner.hpp"
+
+namespace {
+
+// n, b, K, len, tries used, products with A, those of the sequences, those of Horner and the check, launches, sum of the row
+// degrees (last try), largest row degree, columns solved, columns with a kernel vector, device us of the sequences, of
+// Berlekamp-Massey, of Horner + check
+constexpr int BLOCK_SOLVE_NSTATS = 16;
+thread_local i64 g_block_solve_stats[BLOCK_SOLVE_NSTATS] = {0};
+
+void block_solve_stats_reset() { memset(g_block_solve_stats, 0, sizeof g_block_solve_stats); }
+
+// the steps of table slices T[0 .. rows) (B x KW words each) from Y = 0: the first is the plain combination, rows - 1 products
+// follow.  The last step writes Yout (leading dimension ldyo) and, when cnt is given, adds its non-zero counts to cnt[0 .. KW); the
+// steps between ping-pong in W.
+template <bool SMALL, int B, int KW>
+int block_horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo, KrylovWork &W,
+                        long long *cnt, int cap, hipStream_t s)
+{
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
+    int launches = 0;
+    const int *X = nullptr;
+    i64d ldx = 0;
+    for (int i = 0; i < rows && n > 0; i++) {
+        const bool last = i == rows - 1;
+        int *Y = last ? Yout : (X == W.w0.p ? W.w1.p : W.w0.p);
+        const i64d ldy = last ? (i64d)ldyo : (i64d)KW;
+        long long *cp = last ? cnt : nullptr;
+        const int *Ti = T + (size_t)i * B * KW;
+        if (!X) {
+            hipLaunchKernelGGL((k_block_horner_first<SMALL, B, KW>), step_grid((i64)n * KW, cap), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, Ti, Vb, (i64d)ldv, Y,
+                               ldy, cp);
+            launches++;
+        } else {
+            launches += spmv_step_launch<SMALL, KW>(V, F, kc, X, ldx, Y, ldy, BlockHornerEpi<SMALL, B>{Ti, Vb, (i64d)ldv, KW, cp}, cap, s);
+        }
+        HIPCHK(hipGetLastError());
+        X = Y;
+        ldx = ldy;
+    }
+    return launches;
+}
+
+// rows >= 1 block Horner steps on device arrays, enqueued on s; no host synchronization.  Vb is n x b (leading dimension ldv), T
+// the device table, rows x b x spmv_kw(K) canonical residues; Yout gets K columns.  Returns the launches.
+int block_horner_run(const SpmvView &V, const ZpField &F, int b, int K, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo, KrylovWork &W,
+                     long long *cnt, hipStream_t s)
+{
+    const int kw = spmv_kw(K), cap = step_grid_cap();
+    const size_t words = (size_t)V.rows * kw;
+    if (rows > 1) {
+        W.w0.ensure(words);
+        if (rows > 2) W.w1.ensure(words);
+    }
+    auto go = [&](auto B) {
+        return dispatch_kw(kw, [&](auto KW) -> int {
+            if constexpr (KW() <= B()) {
+                return F.small ? block_horner_launch<true, B(), KW()>(V, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s)
+                               : block_horner_launch<false, B(), KW()>(V, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s);
+            } else {
+                throw EngineError("K out of range (1 <= K <= b)");
+            }
+        });
+    };
+    switch (b) {
+    case 2: return go(std::integral_constant<int, 2>());
+    case 4: return go(std::integral_constant<int, 4>());
+    case 8: return go(std::integral_constant<int, 8>());
+    default: return go(std::integral_constant<int, 16>());
+    }
+}
+
+void block_poly_check(const spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const spasm_ZZp *V, i64 ldv, const spasm_ZZp *X,
+                      i64 ldx)
+{
+    if (!op) throw EngineError("NULL operator");
+    block_width(b);
+    require_square(-1, op->A.n, op->A.m);
+    if (K < 1 || K > b) throw EngineError("K out of range (1 <= K <= b)");
+    if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
+    if (D < -1 || D >= (1 << 24)) throw EngineError("D out of range (-1 <= D < 2^24)");
+    if (ldv < b) throw EngineError("ldv < b");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (D >= 0 && !coef) throw EngineError("NULL array");
+    const i64 n = op->A.n;
+    if (n > 0) {
+        if (!V || !X) throw EngineError("NULL array");
+        const uintptr_t v0 = (uintptr_t)V, v1 = v0 + (size_t)((n - 1) * ldv + b) * sizeof(int);
+        const uintptr_t x0 = (uintptr_t)X, x1 = x0 + (size_t)((n - 1) * ldx + K) * sizeof(int);
+        if (v0 < x1 && x0 < v1) throw EngineError("V must not overlap X");
+    }
+}
+
+// X <- sum_{t <= D} op(A)^t V C_t on device arrays, enqueued on s: the table goes up once (slice i holds C_{D - i}), then D
+// products.  Returns the launches.
+int block_poly_apply_dev(spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const int *dV, i64 ldv, int *dX, i64 ldx, hipStream_t s)
+{
+    const size_t n = (size_t)op->A.n;
+    if (D < 0) {
+        HIPCHK(hipMemset2DAsync(dX, (size_t)ldx * sizeof(int), 0, (size_t)K * sizeof(int), n, s));
+        return 0;
+    }
+    if (trans) op->build_transpose();
+    const SpmvView &view = trans ? op->tr : op->fwd;
+    KrylovWork &W = op->kry;
+    // the host copy of the previous call's table may still be on its way up
+    if (W.tab_up) HIPCHK(hipEventSynchronize(W.tab_up));
+    else HIPCHK(hipEventCreateWithFlags(&W.tab_up, hipEventDisableTiming));
+    const int kw = spmv_kw(K);
+    const uint64_t p = (uint64_t)op->F.p;
+    W.htab.assign((size_t)(D + 1) * b * kw, 0);
+    for (int i = 0; i <= D; i++)
+        for (int c = 0; c < b; c++)
+            for (int j = 0; j < K; j++)
+                W.htab[((size_t)i * b + c) * kw + j] = hbalanced(hresidue(coef[((size_t)(D - i) * b + c) * K + j], p), p);
+    W.tab.ensure(W.htab.size());
+    HIPCHK(hipMemcpyAsync(W.tab.p, W.htab.data(), W.htab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(W.tab_up, s));
+    return block_horner_run(view, op->F, b, K, D + 1, W.tab.p, dV, ldv, dX, ldx, W, nullptr, s);
+}
+
+void block_poly_stats(i64 n, int b, int K, int D, int launches)
+{
+    i64 *st = g_block_solve_stats;
+    st[0] = n;
+    st[1] = b;
+    st[2] = K;
+    st[5] = st[7] = std::max(D, 0);
+    st[8] = launches;
+}
+
+void block_wied_check(int n, int m, int trans, int b, int K, const void *B, i64 ldb, const void *X, i64 ldx, const int *status)
+{
+    require_square(-1, n, m);
+    block_width(b);
+    if (K < 1 || K > b) throw EngineError("K out of range (1 <= K <= b)");
+    if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
+    if (ldb < K) throw EngineError("ldb < K");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (!status || (n > 0 && (!B || !X))) throw EngineError("NULL array");
+    if (n >= (1 << 24)) throw EngineError("Wiedemann solve limited to n < 2^24");
+}
+
+// Gauss-Jordan on [G | I] over GF(p), G b x b residues in [0, p): column by column, the first row at or below the rank with a
+// non-zero word is swapped up, scaled to 1 and cleared from every other row.  Leaves R = T G reduced, T in t; returns the rank and
+// in pivrow[c] the row whose pivot is column c (-1: none).  Rows rank .. b - 1 of R are zero: those rows of T span the left null
+// space of G, in this order.
+int block_reduce_g(std::vector<uint64_t> &g, std::vector<uint64_t> &t, int b, uint64_t p, std::vector<int> &pivrow)
+{
+    t.assign((size_t)b * b, 0);
+    for (int r = 0; r < b; r++) t[(size_t)r * b + r] = 1;
+    pivrow.assign((size_t)b, -1);
+    int rank = 0;
+    for (int c = 0; c < b && rank < b; c++) {
+        int piv = -1;
+        for (int r = rank; r < b && piv < 0; r++)
+            if (g[(size_t)r * b + c] != 0) piv = r;
+        if (piv < 0) continue;
+        if (piv != rank)
+            for (int k = 0; k < b; k++) {
+                std::swap(g[(size_t)piv * b + k], g[(size_t)rank * b + k]);
+                std::swap(t[(size_t)piv * b + k], t[(size_t)rank * b + k]);
+            }
+        const uint64_t inv = hinv(g[(size_t)rank * b + c], p);
+        for (int k = 0; k < b; k++) {
+            g[(size_t)rank * b + k] = g[(size_t)rank * b + k] * inv % p;
+            t[(size_t)rank * b + k] = t[(size_t)rank * b + k] * inv % p;
+        }
+        for (int r = 0; r < b; r++) {
+            const uint64_t f = g[(size_t)r * b + c];
+            if (r == rank || f == 0) continue;
+            const uint64_t nf = p - f;
+            for (int k = 0; k < b; k++) {
+                g[(size_t)r * b + k] = (g[(size_t)r * b + k] + nf * g[(size_t)rank * b + k] % p) % p;
+                t[(size_t)r * b + k] = (t[(size_t)r * b + k] + nf * t[(size_t)rank * b + k] % p) % p;
+            }
+        }
+        pivrow[(size_t)c] = rank++;
+    }
+    return rank;
+}
+
+// The solve behind the three entries: V is the view of op(A), square, n > 0; the arguments have been checked.  Per try: U and
+// [B | Z] of the seed, the block sequence, the left generator F of its transposed terms (a right generator of the sequence), the
+// reduction of [F_0 | I], one combination h = lambda F per undecided column, the block Horner run and the residual with its counts.
+// Nothing is written to X or status before every try has run.
+void block_wied_run(const SpmvView &V, const ZpField &F, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, spasm_ZZp *X, i64 ldx,
+                    int *status)
+{
+    const int n = V.rows, len = block_terms(n, b);
+    const uint64_t p = (uint64_t)F.p;
+    block_bm_check_len(len);
+    const int ntries = tries <= 0 ? 3 : tries;
+    hipStream_t s = nullptr;
+    const size_t nb = (size_t)n * b, bb = (size_t)b * b;
+    std::vector<int> outX((size_t)n * K, 0), outS((size_t)K, 0), act((size_t)K);
+    for (int c = 0; c < K; c++) act[(size_t)c] = c;
+    std::vector<int> hu(nb), hv(nb), hdeg((size_t)b + 1), hcoef, tab, hx, pivrow;
+    std::vector<uint64_t> g, tg, lam((size_t)b);
+    std::vector<long long> hcnt;
+    std::vector<char> regular;
+    DevBuf<int> dU, dV, dS, dSt, d_coef, d_small, dX, dR, dT;
+    DevBuf<long long> dcnt;
+    KrylovWork W;
+    BlockBmWork BW;
+    SpgEvents ev, evh;
+    dU.alloc(nb);
+    dV.alloc(nb);
+    dS.alloc((size_t)len * bb);
+    dSt.alloc((size_t)len * bb);
+    d_coef.alloc(((size_t)len + 1) * bb);
+    d_small.alloc((size_t)b + 1);
+    i64 *st = g_block_solve_stats;
+    st[0] = n;
+    st[1] = b;
+    st[2] = K;
+    st[3] = len;
+    for (int t = 0; t < ntries && !act.empty(); t++) {
+        const int ka = (int)act.size(), kw = spmv_kw(ka);
+        const size_t nk = (size_t)n * ka;
+        // V = [B | Z]: the undecided right-hand sides, packed, over the leading columns of the seed's V
+        minpoly_vectors(n, b, seed + (uint64_t)t, F.p, hu.data(), hv.data());
+        for (int r = 0; r < n; r++)
+            for (int a = 0; a < ka; a++) hv[(size_t)r * b + a] = B[(i64)r * ldb + act[(size_t)a]];
+        HIPCHK(hipMemcpyAsync(dU.p, hu.data(), nb * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dV.p, hv.data(), nb * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        SeqOperator op{&V};
+        op.block = true;
+        int launches = sequence_run(op, F, b, len, dU.p, b, dV.p, b, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        const i64 total = (i64)len * (i64)bb;
+        hipLaunchKernelGGL(k_block_transpose_terms, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, b, dS.p, dSt.p);
+        HIPCHK(hipGetLastError());
+        launches += 1 + block_bm_device(F, b, len, dSt.p, BW, d_coef.p, d_small.p, d_small.p + b, s);
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        HIPCHK(hipMemcpyAsync(hdeg.data(), d_small.p, hdeg.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int D = hdeg[(size_t)b];
+        hcoef.resize(((size_t)D + 1) * bb);
+        HIPCHK(hipMemcpy(hcoef.data(), d_coef.p, hcoef.size() * sizeof(int), hipMemcpyDeviceToHost));
+        i64 sum = 0;
+        for (int r = 0; r < b; r++) sum += hdeg[(size_t)r];
+        st[4] = t + 1;
+        st[5] += len - 1;
+        st[6] += len - 1;
+        st[8] += launches;
+        st[9] = sum;
+        st[10] = std::max(st[10], (i64)D);
+        st[13] += (i64)(ev.ms(0, 1) * 1000.0);
+        st[14] += (i64)(ev.ms(1, 2) * 1000.0);
+        // lambda_a F_0 = e_a where e_a lies in the row space of F_0 (column a is regular), else lambda_a F_0 = 0
+        g.resize(bb);
+        for (size_t e = 0; e < bb; e++) g[e] = hresidue(hcoef[e], p);
+        const int rank = block_reduce_g(g, tg, b, p, pivrow), nullity = b - rank;
+        // slice i of the table is C_{D - 1 - i} = -(h_{D - i} of the ka columns)^T; one more row for the check: -1 where x is
+        // expected to solve the system, 0 where it is expected to lie in the kernel
+        tab.assign((size_t)D * b * kw + kw, 0);
+        regular.assign((size_t)ka, 0);
+        for (int a = 0; a < ka; a++) {
+            int lr = -1;
+            const int pr = pivrow[(size_t)a];
+            if (pr >= 0) {
+                bool unit = true;
+                for (int k = 0; k < b && unit; k++) unit = g[(size_t)pr * b + k] == (k == a ? 1u : 0u);
+                if (unit) lr = pr;
+            }
+            regular[(size_t)a] = lr >= 0;
+            if (lr < 0) lr = rank + a % nullity; // (a column that is not regular leaves nullity > 0)
+            for (int k = 0; k < b; k++) lam[(size_t)k] = tg[(size_t)lr * b + k];
+            for (int d = 1; d <= D; d++) {
+                const int *Fd = hcoef.data() + (size_t)d * bb;
+                for (int c = 0; c < b; c++) {
+                    uint64_t h = 0;
+                    for (int r = 0; r < b; r++) h += lam[(size_t)r] * hresidue(Fd[(size_t)r * b + c], p) % p;
+                    tab[((size_t)(D - d) * b + c) * kw + a] = hbalanced((p - h % p) % p, p);
+                }
+            }
+            tab[(size_t)D * b * kw + a] = regular[(size_t)a] ? -1 : 0;
+        }
+        dX.ensure(nk);
+        dR.ensure((size_t)n * kw);
+        dcnt.ensure((size_t)2 * kw);
+        dT.ensure(tab.size());
+        HIPCHK(hipMemcpyAsync(dT.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)2 * kw * sizeof(long long), s));
+        HIPCHK(hipEventRecord(evh.e[0], s));
+        launches = 0;
+        if (D == 0) HIPCHK(hipMemsetAsync(dX.p, 0, nk * sizeof(int), s));
+        else launches += block_horner_run(V, F, b, ka, D, dT.p, dV.p, b, dX.p, ka, W, dcnt.p, s);
+        // the certificate: R <- op(A) X + r B, with the non-zero counts of X (above) and of R
+        launches += horner_run(V, F, ka, 1, dT.p + (size_t)D * b * kw, dV.p, b, dX.p, ka, dR.p, kw, W, dcnt.p + kw, s);
+        HIPCHK(hipEventRecord(evh.e[1], s));
+        hcnt.resize((size_t)2 * kw);
+        hx.resize(nk);
+        HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt.p, hcnt.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hx.data(), dX.p, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        const int hp_ = std::max(D - 1, 0) + 1;
+        st[5] += hp_;
+        st[7] += hp_;
+        st[8] += launches;
+        st[15] += (i64)(evh.ms(0, 1) * 1000.0);
+        std::vector<int> left;
+        for (int a = 0; a < ka; a++) {
+            const int c = act[(size_t)a];
+            const bool rzero = hcnt[(size_t)kw + a] == 0, xzero = hcnt[(size_t)a] == 0;
+            int verdict = 0;
+            if (regular[(size_t)a] && rzero) verdict = 1;
+            else if (!regular[(size_t)a] && rzero && !xzero) verdict = 2;
+            if (!verdict) {
+                left.push_back(c);
+                continue;
+            }
+            outS[(size_t)c] = verdict;
+            st[10 + verdict]++;
+            for (int r = 0; r < n; r++) outX[(size_t)r * K + c] = hx[(size_t)r * ka + a];
+        }
+        act.swap(left);
+    }
+    for (int r = 0; r < n; r++) memcpy(X + (i64)r * ldx, outX.data() + (size_t)r * K, (size_t)K * sizeof(int));
+    memcpy(status, outS.data(), (size_t)K * sizeof(int));
+}
+
+int block_wied_entry(Operand &&o, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries, spasm_ZZp *X, i64 ldx, int *status)
+{
+    block_solve_stats_reset();
+    o.check();
+    block_wied_check(o.n, o.m, trans, b, K, B, ldb, X, ldx, status);
+    if (o.n == 0) {
+        for (int c = 0; c < K; c++) status[c] = 1;
+        g_block_solve_stats[1] = b;
+        g_block_solve_stats[2] = g_block_solve_stats[11] = K;
+        return 0;
+    }
+    block_bm_check_len(block_terms(o.n, b));
+    o.views(!trans, trans != 0); // x A = b is A^T x = b
+    block_wied_run(trans ? *o.tr : *o.fwd, o.F, b, K, B, ldb, seed, tries, X, ldx, status);
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- block Horner and the block Wiedemann solve (block_horner.hpp; engine extension) ----
+SPASM_API int spasm_amd_block_poly_apply(spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const spasm_ZZp *V, i64 ldv,
+                                         spasm_ZZp *X, i64 ldx)
+{
+    return abi_call("spasm_amd_block_poly_apply", -1, [&] {
+        block_solve_stats_reset();
+        block_poly_check(op, trans, b, K, D, coef, V, ldv, X, ldx);
+        const size_t n = (size_t)op->A.n, kk = (size_t)K, wb = (size_t)b;
+        if (n == 0) return 0;
+        DeviceGuard g(op);
+        hipStream_t s = nullptr;
+        DevBuf<int> dV, dX;
+        dV.alloc(n * wb);
+        dX.alloc(n * kk);
+        HIPCHK(hipMemcpy2DAsync(dV.p, wb * sizeof(int), V, (size_t)ldv * sizeof(int), wb * sizeof(int), n, hipMemcpyHostToDevice, s));
+        const int launches = block_poly_apply_dev(op, trans, b, K, D, coef, dV.p, b, dX.p, K, s);
+        std::vector<int> out(n * kk);
+        HIPCHK(hipMemcpyAsync(out.data(), dX.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        block_poly_stats((i64)n, b, K, D, launches);
+        for (size_t r = 0; r < n; r++) memcpy(X + (i64)r * ldx, out.data() + r * kk, kk * sizeof(int));
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_block_poly_apply_dev(spasm_amd_spmv *op, int trans, int b, int K, int D, const spasm_ZZp *coef, const spasm_ZZp *V, i64 ldv,
+                                             spasm_ZZp *X, i64 ldx, void *stream)
+{
+    return abi_call("spasm_amd_block_poly_apply_dev", -1, [&] {
+        block_solve_stats_reset();
+        block_poly_check(op, trans, b, K, D, coef, V, ldv, X, ldx);
+        if (op->A.n == 0) return 0;
+        DeviceGuard g(op);
+        const int launches = block_poly_apply_dev(op, trans, b, K, D, coef, V, ldv, X, ldx, (hipStream_t)stream);
+        block_poly_stats(op->A.n, b, K, D, launches);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_block_wiedemann_solve(const struct spasm_csr *A, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                              spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_block_wiedemann_solve", -1,
+                    [&] { return block_wied_entry(Operand(A, "spasm_amd_block_wiedemann_solve"), trans, b, K, B, ldb, seed, tries, X, ldx, status); });
+}
+
+SPASM_API int spasm_amd_spmv_block_wiedemann_solve(spasm_amd_spmv *op, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                                   spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_spmv_block_wiedemann_solve", -1,
+                    [&] { return block_wied_entry(Operand(op), trans, b, K, B, ldb, seed, tries, X, ldx, status); });
+}
+
+SPASM_API int spasm_amd_dcsr_block_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int b, int K, const spasm_ZZp *B, i64 ldb, uint64_t seed, int tries,
+                                                   spasm_ZZp *X, i64 ldx, int *status)
+{
+    return abi_call("spasm_amd_dcsr_block_wiedemann_solve", -1,
+                    [&] { return block_wied_entry(Operand(D), trans, b, K, B, ldb, seed, tries, X, ldx, status); });
+}
+
+SPASM_API void spasm_amd_block_solve_stats(i64 *out)
+{
+    if (out) memcpy(out, g_block_solve_stats, sizeof g_block_solve_stats);
+}
+
+} // extern "C"

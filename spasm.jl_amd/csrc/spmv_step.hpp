@@ -25,6 +25,10 @@
 //                                     sums t over the workgroup and adds the sums to global memory (every lane calls it).
 // The one-term epilogues do not name EpiTerms and compile to what they compiled to before it existed: the branch is taken at
 // compile time (profiles/block_wiedemann_asm_diff.txt).
+// A one-term epilogue whose lane keeps more than one word for its column (the B coefficients of block_horner.hpp) names the
+// trivially copyable type in EpiCoef: coef(v) returns it, own takes it as c, and a lane that owns nothing holds its zero value.
+// The others do not name EpiCoef, their c is the int it was, and they compile to what they compiled to before
+// (profiles/block_solve_asm_diff.txt).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "zp.hpp"
@@ -55,6 +59,9 @@ template <int KW> __device__ __forceinline__ void krylov_project(long long t, lo
 // the terms an epilogue returns per entry of Y: 1 unless it says otherwise
 template <class Epi> struct EpiTerms { static constexpr int value = 1; };
 
+// what a lane keeps for its column over all its rows, the result of coef(v): an int unless the epilogue says otherwise
+template <class Epi> struct EpiCoef { typedef int type; };
+
 // One team of TEAM lanes per work item (SPMV_TEAM_SUM); a team strides over the items of its class.  Not PARTIAL: the epilogue
 // gets the row's sum.  PARTIAL: part[it * KW + v] <- the segment's sum, no epilogue.
 template <bool SMALL, int KW, int TEAM, bool PARTIAL, class Epi>
@@ -68,8 +75,9 @@ __global__ __launch_bounds__(KRY_BS) void k_spmv_step(int nitems, const int *__r
     const SpmvLane<KW, TEAM> L(kc);
     if constexpr (PARTIAL || NT == 1) {
         // (a segment launch never consults the epilogue, of either kind)
-        int c = 0;
-        if constexpr (!PARTIAL) c = L.vok ? epi.coef(L.v) : 0;
+        typedef typename EpiCoef<Epi>::type Coef;
+        Coef c = Coef();
+        if constexpr (!PARTIAL) c = L.vok ? epi.coef(L.v) : Coef();
         long long t = 0;
         // whole teams leave the loop together: the shuffles stay inside a team
         for (i64d it = (i64d)blockIdx.x * TPB + threadIdx.x / TEAM; it < nitems; it += (i64d)gridDim.x * TPB) {
@@ -105,7 +113,7 @@ __global__ __launch_bounds__(KRY_BS) void k_spmv_step_combine(int nlong, const i
     if constexpr (NT == 1) {
         long long t = 0;
         if (v < kc) {
-            const int c = epi.coef(v);
+            const typename EpiCoef<Epi>::type c = epi.coef(v);
             for (i64d l = (i64d)blockIdx.x * RPB + threadIdx.x / KW; l < nlong; l += (i64d)gridDim.x * RPB) {
                 int64_t s = 0; // |s| <= (2^31 / SPMV_SEG) * 2^31 < 2^48: exact
                 for (int it = off[l]; it < off[l + 1]; it++) s += part[(i64d)it * KW + v];
