@@ -1197,6 +1197,66 @@ int spasm_amd_dcsr_block_wiedemann_solve(const spasm_amd_dcsr *D, int trans, int
                                          spasm_ZZp *X, i64 ldx, int *status);
 void spasm_amd_block_solve_stats(i64 *out);   /* of the last block Horner / block Wiedemann solve call of this thread */
 
+/* ---- kernel bases without fill-in (engine extension; csrc/colechelon.hpp) ----
+ * Verified kernel vectors of a sparse matrix, rectangular or square, by block Wiedemann on M = op(A)^T D2 op(A), collected in the
+ * reduced column echelon form of their span; with certify the basis can be PROVED complete.  Memory is O(nnz + dim * 64).
+ *   dense_column_echelon  X is a HOST array, rows x K, row-major, leading dimension ldx >= K, 0 <= K <= 64, 0 <= rows < 2^30; any
+ *                 int32 is reduced where it is read.  X is replaced by the reduced column echelon form of its column space:
+ *                 column j < *rank has its first non-zero entry, a 1, in row pivots[j]; pivots ascends strictly; row pivots[j] is
+ *                 zero in every other column; columns *rank .. K - 1 are zero; every word is the balanced residue.  The form is
+ *                 unique: two runs, and two blocks with the same column space, give the same bytes.  pivots has room for K words.
+ *                 Column by column on the device: a first-non-zero search (one integer atomicMin a workgroup), a copy of the pivot
+ *                 row with the inverse of the pivot, one elimination pass over rows x K; no host synchronization between columns,
+ *                 one read-back of the K pivot rows, one permutation.  O(rows * K^2) words moved.  rows = 0 or K = 0: rank 0, no
+ *                 device needed.
+ *   block_precond_sequence  op is a resident operator, rectangular or square; op(A) = A (trans 0) or A^T (trans 1) is n x m.
+ *                 S[(i * b + r) * b + c] = sum_k U[k, r] * (M^i V)[k, c] mod p, 0 <= i < len, balanced residues, with
+ *                 M = diag(d_right) op(A)^T diag(d_left) op(A) (m x m); d_right = NULL means the identity.  U and V are m x b HOST
+ *                 arrays (ldu, ldv >= b), d_left has n words, d_right m, S len * b * b; b is 2, 4, 8 or 16, 1 <= len < 2^24.  A
+ *                 step is two launch sets of the step kernels: the forward view with the diagonal d_left, the transposed view with
+ *                 the block projection.  n = 0 or m = 0: M = 0, S_0 = U^T V, no device needed.
+ *   wiedemann_kernel, spmv_wiedemann_kernel, dcsr_wiedemann_kernel
+ *                 A host matrix, a resident operator, a resident matrix, n x m, n, m < 2^24.  Returns vectors x with A x = 0
+ *                 (trans 1: x A = 0) as the columns of N: dim x *found, dim = m (n with trans), *found <= want <= 64, a HOST array
+ *                 with ldn >= want, in the reduced column echelon form above; pivots (room for want words) gets its pivot rows.
+ *                 b is 2, 4, 8 or 16; tries >= 1.  Try t = 0, 1, ..: D2 = precond_diagonal(rows of op(A), seed + t, 0) and
+ *                 U, Y = minpoly_vectors(dim, b, seed + t, p); V = M Y; the block sequence U^T M^i V of 2 * ceil(dim / b) + 2
+ *                 terms; the left generator F of its transposed terms (block_berlekamp_massey); the candidates
+ *                 W = sum_s M^s Y F_s^T (dim x b) by ONE composite block Horner pass over Y, not V; then ONE product op(A) W with
+ *                 the non-zero counts of every column of W and of op(A) W.  A column is accepted only when its residual count is 0
+ *                 and it is non-zero: the residual is taken against A itself, not against M, so EVERY RETURNED COLUMN IS A PROVED
+ *                 KERNEL VECTOR.  At most want - *found accepted columns (the first ones) join the basis, which is brought to
+ *                 echelon form on the device: a dependent column falls out.  Over a small field ker M may exceed ker A; such
+ *                 candidates are rejected, never returned.  The tries stop when *found = want, when the certification closes, or
+ *                 after `tries`.
+ *                 certify != 0: the preconditioned rank of spasm_amd_wiedemann_rank (K = 8, the same seed and tries) runs first;
+ *                 its r is ALWAYS a lower bound of rank A, so dim - r bounds the nullity from above.  *complete = 1 exactly when
+ *                 *found = dim - r: then the columns of N are a basis of the WHOLE kernel, and THIS IS A PROOF, never a Monte
+ *                 Carlo claim.  *complete = 0 says nothing: certify was 0, the numbers did not meet, or want cut the basis short.
+ *                 dim = 0: *found = 0, *complete = 1, no device needed.  A matrix op(A) without rows: unit vectors, no device.
+ *   kernel_stats  of the last of these calls of this thread: out[19] = n, m, b, want, tries used, products with A (all), those of
+ *                 the sequences (2 * len a try), of Horner (2 * D a try), of the check (1 a try), of the certification, launches,
+ *                 candidates formed (b a try), accepted (joined the basis), dropped as dependent, found, device microseconds of the
+ *                 sequences, of Berlekamp-Massey, of Horner + check, of the echelon form (HIP events).  found = accepted - dropped;
+ *                 the rejected candidates have no slot: rejected = candidates - accepted.  dense_column_echelon fills launches,
+ *                 found (the rank) and the echelon microseconds; block_precond_sequence the slots of its sequence.
+ *   deterministic two runs give the same bytes
+ *   errors        "K out of range (0 <= K <= 64)", "ldx < K", "rows out of range (0 <= rows < 2^30)", "prime out of range (2 < p <=
+ *                 0xfffffffb)", "b must be 2, 4, 8 or 16", "trans must be 0 or 1", "want out of range (0 <= want <= 64)",
+ *                 "ldn < want", "tries < 1", "len out of range (1 <= len < 2^24)", "bad arguments (trans 0/1, ldu >= b, ldv >= b)",
+ *                 "Wiedemann kernel limited to dim < 2^24", a NULL operator / matrix / array, no device ("no HIP device"), out of
+ *                 memory: -1, NO output word is written, spasm_amd_last_error() names the cause. */
+int spasm_amd_dense_column_echelon(i64 rows, int K, spasm_ZZp *X, i64 ldx, i64 prime, int *rank, int *pivots);
+int spasm_amd_block_precond_sequence(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *d_right /* or NULL */,
+                                     const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S);
+int spasm_amd_wiedemann_kernel(const struct spasm_csr *A, int trans, int b, int want, uint64_t seed, int tries, int certify,
+                               spasm_ZZp *N, i64 ldn, int *found, int *pivots, int *complete);
+int spasm_amd_spmv_wiedemann_kernel(spasm_amd_spmv *op, int trans, int b, int want, uint64_t seed, int tries, int certify,
+                                    spasm_ZZp *N, i64 ldn, int *found, int *pivots, int *complete);
+int spasm_amd_dcsr_wiedemann_kernel(const spasm_amd_dcsr *D, int trans, int b, int want, uint64_t seed, int tries, int certify,
+                                    spasm_ZZp *N, i64 ldn, int *found, int *pivots, int *complete);
+void spasm_amd_wiedemann_kernel_stats(i64 *out);   /* of the last kernel-basis call of this thread */
+
 #ifdef __cplusplus
 }
 #endif

@@ -363,6 +363,12 @@ SIGNATURES = {
     "spasm_amd_spmv_block_wiedemann_solve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_dcsr_block_wiedemann_solve": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_uint64, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p]),
     "spasm_amd_block_solve_stats": (None, [_P(C.c_int64)]),
+    "spasm_amd_dense_column_echelon": (C.c_int32, [C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64, _P(C.c_int32), C.c_void_p]),
+    "spasm_amd_block_precond_sequence": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]),
+    "spasm_amd_wiedemann_kernel": (C.c_int32, [_P(CsrStruct), C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int32), C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_spmv_wiedemann_kernel": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int32), C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_dcsr_wiedemann_kernel": (C.c_int32, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, _P(C.c_int32), C.c_void_p, _P(C.c_int32)]),
+    "spasm_amd_wiedemann_kernel_stats": (None, [_P(C.c_int64)]),
 }
 DATA_SYMBOLS = ["logcallback"]
 

@@ -2620,3 +2620,108 @@ def block_solve_stats():
 SpMV.block_poly_apply = block_poly_apply
 SpMV.block_wiedemann_solve = block_wiedemann_solve
 DeviceCSR.block_wiedemann_solve = block_wiedemann_solve
+
+
+# ---------------------------------------------------------------------------------------------
+# Kernel bases without fill-in  (spasm_amd_dense_column_echelon, _block_precond_sequence, _wiedemann_kernel*; csrc/colechelon.hpp)
+# ---------------------------------------------------------------------------------------------
+WIEDEMANN_KERNEL_STATS = ("n", "m", "b", "want", "tries", "products", "sequence_products", "horner_products", "check_products",
+                          "certify_products", "launches", "candidates", "accepted", "dependent", "found", "sequence_device_us",
+                          "bm_device_us", "horner_device_us", "echelon_device_us")
+
+
+def column_echelon(X, prime):
+    """column_echelon(X, prime) -> (E, pivots): the reduced column echelon form mod prime of the column space of X, an int32 numpy
+    array of shape (rows, K), K <= 64 (any int32 is reduced), by column-wise elimination on the device
+    (spasm_amd_dense_column_echelon).  E has the shape of X: column j < len(pivots) has its first non-zero entry, a 1, in row
+    pivots[j]; pivots ascends strictly; row pivots[j] is zero in every other column; the remaining columns are zero; balanced
+    residues.  The form is unique: two blocks with the same column space give the same bytes.  X is not modified."""
+    if not isinstance(X, np.ndarray) or X.dtype != np.int32 or X.ndim != 2:
+        raise TypeError("X must be a two-dimensional int32 numpy array")
+    rows, k = X.shape
+    E = np.array(X, dtype=np.int32, order="C")
+    pivots = np.zeros(max(k, 1), dtype=np.int32)
+    rank = C.c_int32(0)
+    rc = _abi.lib().spasm_amd_dense_column_echelon(rows, k, E.ctypes.data, max(k, 1), int(prime), C.byref(rank), pivots.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_dense_column_echelon failed")
+    return E, pivots[: rank.value].copy()
+
+
+def block_precond_sequence(op, U, V, length, d_left, d_right=None, trans=False):
+    """block_precond_sequence(op, U, V, length, d_left, d_right=None, trans=False) -> S of shape (length, b, b):
+    S[i, r, c] = sum_k U[k, r] * (M^i V)[k, c] mod p as balanced residues, M = diag(d_right) op(A)^T diag(d_left) op(A) for the
+    SpMV operator op of a matrix A that may be rectangular (op(A) = A^T with trans=True); d_right=None is the identity.  U and V
+    are dim x b int32 numpy arrays, dim the number of columns of op(A), b in (2, 4, 8, 16); d_left has one word per row of op(A),
+    d_right dim words (spasm_amd_block_precond_sequence).  Any int32 is reduced where it is read."""
+    if not isinstance(op, SpMV):
+        raise TypeError("an SpMV operator expected")
+    if not op._op:
+        raise SpasmError("the operator is closed")
+    n, m = (op.shape[1], op.shape[0]) if trans else (op.shape[0], op.shape[1])
+    for a, name in ((U, "U"), (V, "V")):
+        if not isinstance(a, np.ndarray) or a.dtype != np.int32:
+            raise TypeError(f"{name} must be an int32 numpy array")
+        if a.ndim != 2 or a.shape[0] != m or a.shape != U.shape:
+            raise ValueError(f"U and V must both have shape ({m}, b), not {a.shape}")
+    b = int(U.shape[1])
+    diag = []
+    for d, name, words in ((d_left, "d_left", n), (d_right, "d_right", m)):
+        if d is None and name == "d_right":
+            diag.append(None)
+            continue
+        if not isinstance(d, np.ndarray) or d.dtype != np.int32 or d.shape != (words,):
+            raise TypeError(f"{name} must be an int32 numpy array of {words} words")
+        diag.append(np.ascontiguousarray(d))
+    Uc, Vc = np.ascontiguousarray(U), np.ascontiguousarray(V)
+    length = int(length)
+    S = np.zeros((max(length, 0), b, b), dtype=np.int32)
+    rc = _abi.lib().spasm_amd_block_precond_sequence(op._op, int(bool(trans)), b, length, diag[0].ctypes.data,
+                                                     None if diag[1] is None else diag[1].ctypes.data, Uc.ctypes.data, b, Vc.ctypes.data, b,
+                                                     S.ctypes.data)
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or "spasm_amd_block_precond_sequence failed")
+    return S
+
+
+def wiedemann_kernel(A, want=None, b=8, trans=False, seed=0, tries=3, certify=False):
+    """wiedemann_kernel(A, want=None, b=8, trans=False, seed=0, tries=3, certify=False) -> (N, pivots, complete): vectors x with
+    A x = 0 (x A = 0 with trans=True) as the columns of N, dim x found, int32 balanced residues, by block Wiedemann on
+    A^T D2 A without elimination or fill-in.  A is a CSR, rectangular or square (spasm_amd_wiedemann_kernel), an SpMV operator
+    (spasm_amd_spmv_wiedemann_kernel) or a DeviceCSR (spasm_amd_dcsr_wiedemann_kernel); b is 2, 4, 8 or 16; found <= want <= 64
+    and want=None means min(64, tries * b).  N is in the reduced column echelon form of column_echelon, with the pivot rows pivots.
+    Every column is a proved kernel vector (its residual against A is computed on the device) and the columns are independent.
+    complete is True only with certify=True and only when found equals dim minus the lower bound of the rank that wiedemann_rank's
+    procedure gives (K = 8, the same seeds): then N is a basis of the whole kernel, and that is a proof, not a Monte Carlo claim.
+    complete False says nothing: no certificate was asked for, the numbers did not meet, or want cut the basis short."""
+    who, fn, arg, _ = _family_target(A, "wiedemann_kernel")
+    n, m = (A.n, A.m) if isinstance(A, CSR) else (A.shape[0], A.shape[1])
+    dim = n if trans else m
+    tries = int(tries)
+    b = int(b)
+    if want is None:
+        want = max(0, min(64, tries * b))
+    want = int(want)
+    N = np.zeros((dim, max(want, 0)), dtype=np.int32)
+    pivots = np.zeros(max(want, 1), dtype=np.int32)
+    found, complete = C.c_int32(0), C.c_int32(0)
+    with _quiet(True):
+        rc = fn(arg, int(bool(trans)), b, want, int(seed) & 0xFFFFFFFFFFFFFFFF, tries, int(bool(certify)), N.ctypes.data, max(want, 1),
+                C.byref(found), pivots.ctypes.data, C.byref(complete))
+    if rc != 0:
+        raise SpasmError(_abi.last_error() or f"{who} failed")
+    return np.ascontiguousarray(N[:, : found.value]), pivots[: found.value].copy(), bool(complete.value)
+
+
+def wiedemann_kernel_stats():
+    """Counters of the last wiedemann_kernel call of this thread (spasm_amd_wiedemann_kernel_stats), keyed by
+    WIEDEMANN_KERNEL_STATS.  block_precond_sequence fills the slots of its sequence; column_echelon fills launches, found (the
+    rank) and echelon_device_us."""
+    out = (C.c_int64 * len(WIEDEMANN_KERNEL_STATS))()
+    _abi.lib().spasm_amd_wiedemann_kernel_stats(out)
+    return {k: int(v) for k, v in zip(WIEDEMANN_KERNEL_STATS, out)}
+
+
+SpMV.block_precond_sequence = block_precond_sequence
+SpMV.wiedemann_kernel = wiedemann_kernel
+DeviceCSR.wiedemann_kernel = wiedemann_kernel

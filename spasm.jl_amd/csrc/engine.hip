@@ -5591,6 +5591,7 @@ void spmv_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, i64 
 // the ping-pong buffers and the projection sums of one Krylov sequence (krylov.hpp; the section at the end of this file)
 struct KrylovWork {
     DevBuf<int> w0, w1;
+    DevBuf<int> mid;                       // the n x KW intermediate D2 A X of a composite block Horner step
     DevBuf<long long> acc;
     // the coefficient table of a Horner run (horner.hpp): the host copy lives here until its upload has completed
     DevBuf<int> tab;
@@ -10810,8 +10811,8 @@ int spmv_step_launch(const SpmvView &V, const ZpField &F, int kc, const int *X, 
 
 // The operator B of a projected sequence.  No diagonal: B = A, fwd the view of a square matrix.  dl alone: B = D A, dl the n words
 // of D.  tr: B = E A^T D2 A, fwd and tr the two views of the n x m matrix, dl = D2 (n words), dr = E (m words).
-// block: the sequence is the b x b projection U^T B^i X of block_krylov.hpp (b = K in {2, 4, 8, 16}, B = A or D A, no tr; b * b
-// words a term) and not its diagonal.
+// block: the sequence is the b x b projection U^T B^i X of block_krylov.hpp (b = K in {2, 4, 8, 16}; b * b words a term) and not
+// its diagonal.  block with tr: B = E A^T D2 A as above, dr == NULL for E = I.
 struct SeqOperator {
     const SpmvView *fwd = nullptr, *tr = nullptr;
     const int *dl = nullptr, *dr = nullptr;
@@ -10820,7 +10821,8 @@ struct SeqOperator {
 };
 
 // One step is one launch set (KrylovEpi, or DiagEpi with dl) whose iterates ping-pong in W.w0 / W.w1, or with tr two sets: W.w0
-// holds the n x KW intermediate and W.w1 the m x KW iterate.
+// holds the n x KW intermediate and W.w1 the m x KW iterate.  A block step with tr is fwd with DiagEpi{d2, no projection}, then
+// tr with BlockEpi<B>{dr or NULL, U, ldu, acc}: the existing epilogues on the other view.
 template <bool SMALL, int KW>
 int sequence_launch(const SeqOperator &op, const ZpField &F, int kc, i64 len, const int *U, i64 ldu, const int *X0, i64 ldx0, KrylovWork &W, int *S, int cap,
                     hipStream_t s)
@@ -10845,7 +10847,12 @@ int sequence_launch(const SeqOperator &op, const ZpField &F, int kc, i64 len, co
     int *Y = W.w0.p;
     for (i64 i = 1; i < len && dim > 0; i++) {
         long long *acc = W.acc.p + i * aw;
-        if (op.block) {
+        if (op.block && op.tr) {
+            launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, W.w0.p, (i64d)KW, DiagEpi{op.dl, nullptr, 0, nullptr}, cap, s);
+            if constexpr (BLOCKW)
+                launches += spmv_step_launch<SMALL, KW>(*op.tr, F, kc, W.w0.p, (i64d)KW, W.w1.p, (i64d)KW, BlockEpi<KW>{op.dr, U, (i64d)ldu, acc}, cap, s);
+            X = W.w1.p;
+        } else if (op.block) {
             if constexpr (BLOCKW) launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, Y, (i64d)KW, BlockEpi<KW>{op.dl, U, (i64d)ldu, acc}, cap, s);
             X = Y;
             Y = Y == W.w0.p ? W.w1.p : W.w0.p;
@@ -12502,12 +12509,13 @@ void block_solve_stats_reset() { memset(g_block_solve_stats, 0, sizeof g_block_s
 
 // the steps of table slices T[0 .. rows) (B x KW words each) from Y = 0: the first is the plain combination, rows - 1 products
 // follow.  The last step writes Yout (leading dimension ldyo) and, when cnt is given, adds its non-zero counts to cnt[0 .. KW); the
-// steps between ping-pong in W.
+// steps between ping-pong in W.  With op.tr a product is two launch sets, M = A^T D2 A: fwd with DiagEpi{d2} writes W.mid, tr with
+// BlockHornerEpi reads it (BlockHornerEpi has no diagonal: E = I).
 template <bool SMALL, int B, int KW>
-int block_horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo, KrylovWork &W,
+int block_horner_launch(const SeqOperator &op, const ZpField &F, int kc, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo, KrylovWork &W,
                         long long *cnt, int cap, hipStream_t s)
 {
-    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = V.rows;
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, n = op.dim();
     int launches = 0;
     const int *X = nullptr;
     i64d ldx = 0;
@@ -12521,8 +12529,11 @@ int block_horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, c
             hipLaunchKernelGGL((k_block_horner_first<SMALL, B, KW>), step_grid((i64)n * KW, cap), dim3(KRY_BS), 0, s, n, kc, F, hp, mhp, Ti, Vb, (i64d)ldv, Y,
                                ldy, cp);
             launches++;
+        } else if (op.tr) {
+            launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, W.mid.p, (i64d)KW, DiagEpi{op.dl, nullptr, 0, nullptr}, cap, s);
+            launches += spmv_step_launch<SMALL, KW>(*op.tr, F, kc, W.mid.p, (i64d)KW, Y, ldy, BlockHornerEpi<SMALL, B>{Ti, Vb, (i64d)ldv, KW, cp}, cap, s);
         } else {
-            launches += spmv_step_launch<SMALL, KW>(V, F, kc, X, ldx, Y, ldy, BlockHornerEpi<SMALL, B>{Ti, Vb, (i64d)ldv, KW, cp}, cap, s);
+            launches += spmv_step_launch<SMALL, KW>(*op.fwd, F, kc, X, ldx, Y, ldy, BlockHornerEpi<SMALL, B>{Ti, Vb, (i64d)ldv, KW, cp}, cap, s);
         }
         HIPCHK(hipGetLastError());
         X = Y;
@@ -12531,22 +12542,24 @@ int block_horner_launch(const SpmvView &V, const ZpField &F, int kc, int rows, c
     return launches;
 }
 
-// rows >= 1 block Horner steps on device arrays, enqueued on s; no host synchronization.  Vb is n x b (leading dimension ldv), T
-// the device table, rows x b x spmv_kw(K) canonical residues; Yout gets K columns.  Returns the launches.
-int block_horner_run(const SpmvView &V, const ZpField &F, int b, int K, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo, KrylovWork &W,
-                     long long *cnt, hipStream_t s)
+// rows >= 1 block Horner steps on device arrays, enqueued on s; no host synchronization.  Vb is dim x b (leading dimension ldv), T
+// the device table, rows x b x spmv_kw(K) canonical residues; Yout gets K columns.  op is A (fwd alone) or A^T D2 A (fwd, tr and
+// dl = D2; dr is not applied).  Returns the launches.
+int block_horner_run(const SeqOperator &op, const ZpField &F, int b, int K, int rows, const int *T, const int *Vb, i64 ldv, int *Yout, i64 ldyo,
+                     KrylovWork &W, long long *cnt, hipStream_t s)
 {
     const int kw = spmv_kw(K), cap = step_grid_cap();
-    const size_t words = (size_t)V.rows * kw;
+    const size_t words = (size_t)op.dim() * kw;
     if (rows > 1) {
         W.w0.ensure(words);
         if (rows > 2) W.w1.ensure(words);
+        if (op.tr) W.mid.ensure((size_t)op.fwd->rows * kw);
     }
     auto go = [&](auto B) {
         return dispatch_kw(kw, [&](auto KW) -> int {
             if constexpr (KW() <= B()) {
-                return F.small ? block_horner_launch<true, B(), KW()>(V, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s)
-                               : block_horner_launch<false, B(), KW()>(V, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s);
+                return F.small ? block_horner_launch<true, B(), KW()>(op, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s)
+                               : block_horner_launch<false, B(), KW()>(op, F, K, rows, T, Vb, ldv, Yout, ldyo, W, cnt, cap, s);
             } else {
                 throw EngineError("K out of range (1 <= K <= b)");
             }
@@ -12606,7 +12619,7 @@ int block_poly_apply_dev(spasm_amd_spmv *op, int trans, int b, int K, int D, con
     W.tab.ensure(W.htab.size());
     HIPCHK(hipMemcpyAsync(W.tab.p, W.htab.data(), W.htab.size() * sizeof(int), hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(W.tab_up, s));
-    return block_horner_run(view, op->F, b, K, D + 1, W.tab.p, dV, ldv, dX, ldx, W, nullptr, s);
+    return block_horner_run({&view}, op->F, b, K, D + 1, W.tab.p, dV, ldv, dX, ldx, W, nullptr, s);
 }
 
 void block_poly_stats(i64 n, int b, int K, int D, int launches)
@@ -12777,7 +12790,7 @@ void block_wied_run(const SpmvView &V, const ZpField &F, int b, int K, const spa
         HIPCHK(hipEventRecord(evh.e[0], s));
         launches = 0;
         if (D == 0) HIPCHK(hipMemsetAsync(dX.p, 0, nk * sizeof(int), s));
-        else launches += block_horner_run(V, F, b, ka, D, dT.p, dV.p, b, dX.p, ka, W, dcnt.p, s);
+        else launches += block_horner_run({&V}, F, b, ka, D, dT.p, dV.p, b, dX.p, ka, W, dcnt.p, s);
         // the certificate: R <- op(A) X + r B, with the non-zero counts of X (above) and of R
         launches += horner_run(V, F, ka, 1, dT.p + (size_t)D * b * kw, dV.p, b, dX.p, ka, dR.p, kw, W, dcnt.p + kw, s);
         HIPCHK(hipEventRecord(evh.e[1], s));
@@ -12896,6 +12909,404 @@ SPASM_API int spasm_amd_dcsr_block_wiedemann_solve(const spasm_amd_dcsr *D, int 
 SPASM_API void spasm_amd_block_solve_stats(i64 *out)
 {
     if (out) memcpy(out, g_block_solve_stats, sizeof g_block_solve_stats);
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------
+// Kernel bases without fill-in (colechelon.hpp): the reduced column echelon form of a tall dense block, the block sequence of the
+// composite operator A^T D2 A, and on top of them verified kernel vectors by block Wiedemann whose basis can be proved complete.
+// ------------------------------------------------------------------------------------------------
+#include "colechelon.hpp"
+
+namespace {
+
+// n, m, b, want, tries used, products with A, those of the sequences, of Horner, of the check, of the certification, launches,
+// candidates formed, accepted, dropped as dependent, found, device us of the sequences, of Berlekamp-Massey, of Horner + check, of
+// the echelon form
+constexpr int WKER_NSTATS = 19;
+thread_local i64 g_wker_stats[WKER_NSTATS] = {0};
+
+void wker_stats_reset() { memset(g_wker_stats, 0, sizeof g_wker_stats); }
+
+struct CeWork {
+    DevBuf<int> piv, mult;
+};
+
+// The reduced column echelon form of the rows x K block X on the device (0 < K <= 64, 0 < rows < 2^30), in place: 3 K launches
+// enqueued on s, one read-back of the K pivot rows, one permutation.  hpiv gets the rank pivot rows, ascending.  Returns the rank.
+int column_echelon_dev(i64 rows, int K, int *X, i64 ldx, const ZpField &F, CeWork &W, int *hpiv, int *launches, hipStream_t s)
+{
+    const int hp = (int)F.halfp, mhp = (int)F.mhalfp, kw = spmv_kw(K), cap = step_grid_cap();
+    W.piv.ensure(CE_MAXK);
+    W.mult.ensure((size_t)CE_MAXK * CE_SLICE);
+    HIPCHK(hipMemsetAsync(W.piv.p, 0x7f, (size_t)K * sizeof(int), s));
+    const dim3 gfind = step_grid(rows, cap), gelim = step_grid(rows * kw, cap);
+    for (int c = 0; c < K; c++) {
+        int *mult = W.mult.p + (size_t)c * CE_SLICE;
+        hipLaunchKernelGGL(k_ce_find, gfind, dim3(CE_BS), 0, s, (i64d)rows, c, F, hp, mhp, X, (i64d)ldx, W.piv.p);
+        hipLaunchKernelGGL(k_ce_pivot, dim3(1), dim3(64), 0, s, K, c, F, hp, mhp, X, (i64d)ldx, W.piv.p, mult);
+        hipLaunchKernelGGL(k_ce_elim, gelim, dim3(CE_BS), 0, s, (i64d)rows, K, kw, c, F, hp, mhp, X, (i64d)ldx, mult);
+    }
+    HIPCHK(hipGetLastError());
+    int piv[CE_MAXK];
+    HIPCHK(hipMemcpyAsync(piv, W.piv.p, (size_t)K * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::vector<std::pair<int, int>> order;
+    for (int c = 0; c < K; c++)
+        if (piv[c] != CE_NONE) order.push_back({piv[c], c});
+    std::sort(order.begin(), order.end());
+    const int rank = (int)order.size();
+    CeOrder ord;
+    memset(&ord, 0, sizeof ord);
+    for (int j = 0; j < rank; j++) {
+        ord.src[j] = (unsigned char)order[(size_t)j].second;
+        hpiv[j] = order[(size_t)j].first;
+    }
+    hipLaunchKernelGGL(k_ce_permute, gelim, dim3(CE_BS), 0, s, (i64d)rows, K, kw, rank, ord, F, hp, mhp, X, (i64d)ldx);
+    HIPCHK(hipGetLastError());
+    if (launches) *launches += 3 * K + 1;
+    return rank;
+}
+
+void dense_column_echelon(i64 rows, int K, spasm_ZZp *X, i64 ldx, i64 prime, int *rank, int *pivots)
+{
+    if (K < 0 || K > CE_MAXK) throw EngineError("K out of range (0 <= K <= 64)");
+    if (ldx < K) throw EngineError("ldx < K");
+    if (rows < 0 || rows >= ((i64)1 << 30)) throw EngineError("rows out of range (0 <= rows < 2^30)");
+    check_prime(prime);
+    if (!rank || (K > 0 && !pivots) || (rows > 0 && K > 0 && !X)) throw EngineError("NULL array");
+    if (rows == 0 || K == 0) {
+        *rank = 0;
+        return;
+    }
+    require_device();
+    DeviceGuard g;
+    const ZpField F = zp_field_make(prime);
+    hipStream_t s = nullptr;
+    const size_t kk = (size_t)K, n = (size_t)rows;
+    DevBuf<int> dX;
+    CeWork W;
+    dX.alloc(n * kk);
+    HIPCHK(hipMemcpy2DAsync(dX.p, kk * sizeof(int), X, (size_t)ldx * sizeof(int), kk * sizeof(int), n, hipMemcpyHostToDevice, s));
+    int hpiv[CE_MAXK], launches = 0;
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    const int r = column_echelon_dev(rows, K, dX.p, K, F, W, hpiv, &launches, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> out(n * kk);
+    HIPCHK(hipMemcpyAsync(out.data(), dX.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    g_wker_stats[10] = launches;
+    g_wker_stats[14] = r;
+    g_wker_stats[18] = (i64)(ev.ms(0, 1) * 1000.0); // the K columns, the read-back of the pivot rows and the permutation
+    for (size_t i = 0; i < n; i++) memcpy(X + (i64)i * ldx, out.data() + i * kk, kk * sizeof(int));
+    memcpy(pivots, hpiv, (size_t)r * sizeof(int));
+    *rank = r;
+}
+
+// Y <- d * (A X) on device arrays (K columns, Y of leading dimension spmv_kw(K)): one launch set with DiagEpi and no projection
+int diag_step_run(const SpmvView &V, const ZpField &F, int K, const int *d, const int *X, i64 ldx, int *Y, hipStream_t s)
+{
+    const int kw = spmv_kw(K), cap = step_grid_cap();
+    return dispatch_kw(kw, [&](auto KW) {
+        return F.small ? spmv_step_launch<true, KW()>(V, F, K, X, (i64d)ldx, Y, (i64d)KW(), DiagEpi{d, nullptr, 0, nullptr}, cap, s)
+                       : spmv_step_launch<false, KW()>(V, F, K, X, (i64d)ldx, Y, (i64d)KW(), DiagEpi{d, nullptr, 0, nullptr}, cap, s);
+    });
+}
+
+void block_precond_sequence(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *dl, const spasm_ZZp *dr, const spasm_ZZp *U, i64 ldu,
+                            const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    if (!op) throw EngineError("NULL operator");
+    block_width(b);
+    if (len < 1 || len >= (1 << 24)) throw EngineError("len out of range (1 <= len < 2^24)");
+    if (ldu < b || ldv < b || (trans != 0 && trans != 1)) throw EngineError("bad arguments (trans 0/1, ldu >= b, ldv >= b)");
+    // op(A) is n x m: M = diag(d_right) op(A)^T diag(d_left) op(A) is m x m
+    const int n = trans ? op->A.m : op->A.n, m = trans ? op->A.n : op->A.m;
+    if (!S || (m > 0 && (!U || !V)) || (n > 0 && !dl)) throw EngineError("NULL array");
+    const uint64_t p = (uint64_t)op->F.p;
+    const size_t kk = (size_t)b, bb = kk * kk, dim = (size_t)m;
+    if (n == 0 || m == 0) { // M is zero: S_0 = U^T V on the host, every later term is 0
+        memset(S, 0, (size_t)len * bb * sizeof(int));
+        for (int r = 0; r < b; r++)
+            for (int c = 0; c < b; c++) {
+                uint64_t a = 0;
+                for (i64 k = 0; k < m; k++) a = (a + hresidue(U[k * ldu + r], p) * hresidue(V[k * ldv + c], p)) % p;
+                S[(size_t)r * kk + c] = hbalanced(a, p);
+            }
+        return;
+    }
+    DeviceGuard g(op);
+    op->build_transpose();
+    hipStream_t s = nullptr;
+    DevBuf<int> dU, dV, dS, ddl, ddr;
+    KrylovWork W;
+    dU.alloc(dim * kk);
+    dV.alloc(dim * kk);
+    dS.alloc((size_t)len * bb);
+    ddl.alloc((size_t)n);
+    HIPCHK(hipMemcpy2DAsync(dU.p, kk * sizeof(int), U, (size_t)ldu * sizeof(int), kk * sizeof(int), dim, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpy2DAsync(dV.p, kk * sizeof(int), V, (size_t)ldv * sizeof(int), kk * sizeof(int), dim, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(ddl.p, dl, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (dr) {
+        ddr.alloc(dim);
+        HIPCHK(hipMemcpyAsync(ddr.p, dr, dim * sizeof(int), hipMemcpyHostToDevice, s));
+    }
+    SpgEvents ev;
+    HIPCHK(hipEventRecord(ev.e[0], s));
+    SeqOperator sq{trans ? &op->tr : &op->fwd, trans ? &op->fwd : &op->tr, ddl.p, dr ? ddr.p : nullptr};
+    sq.block = true;
+    const int launches = sequence_run(sq, op->F, b, len, dU.p, b, dV.p, b, W, dS.p, s);
+    HIPCHK(hipEventRecord(ev.e[1], s));
+    std::vector<int> out((size_t)len * bb);
+    HIPCHK(hipMemcpyAsync(out.data(), dS.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    i64 *st = g_wker_stats;
+    st[0] = n;
+    st[1] = m;
+    st[2] = b;
+    st[5] = st[6] = (i64)(len - 1) * 2;
+    st[10] = launches;
+    st[15] = (i64)(ev.ms(0, 1) * 1000.0);
+    memcpy(S, out.data(), out.size() * sizeof(int));
+}
+
+void wker_check(int trans, int b, int want, int tries, const void *N, i64 ldn, const int *found, const int *pivots, const int *complete, int dim)
+{
+    block_width(b);
+    if (trans != 0 && trans != 1) throw EngineError("trans must be 0 or 1");
+    if (want < 0 || want > CE_MAXK) throw EngineError("want out of range (0 <= want <= 64)");
+    if (ldn < want) throw EngineError("ldn < want");
+    if (tries < 1) throw EngineError("tries < 1");
+    if (!found || !complete || (want > 0 && !pivots) || (want > 0 && dim > 0 && !N)) throw EngineError("NULL array");
+    if (dim >= (1 << 24)) throw EngineError("Wiedemann kernel limited to dim < 2^24");
+}
+
+// The kernel of B = op(A) behind the three entries: Fw and Tr are the views of B (nr x dim) and of its transpose, nr > 0, dim > 0,
+// 0 <= want <= 64; the arguments have been checked.  Per try: D2, U and Y of the seed, V = M Y with M = B^T D2 B, the block sequence
+// of M on U, V, the left generator F of its transposed terms, the candidates W = sum_s M^s Y F_s^T by one composite block Horner
+// pass, the residual B W with its counts, and the echelon form of the basis with the accepted columns.  The basis stays on the
+// device; nothing is written to the caller's arrays before every try has run.
+void wker_run(const SpmvView &Fw, const SpmvView &Tr, const ZpField &F, int b, int want, uint64_t seed, int tries, int certify, spasm_ZZp *N, i64 ldn,
+              int *found, int *pivots, int *complete)
+{
+    const int nr = Fw.rows, dim = Fw.cols, len = block_terms(dim, b);
+    const uint64_t p = (uint64_t)F.p;
+    block_bm_check_len(len);
+    i64 *st = g_wker_stats;
+    hipStream_t s = nullptr;
+    // the lower bound of the rank first: a full-rank matrix is decided without a try
+    i64 target = -1; // dim - r once r is known
+    if (certify) {
+        precond_stats_reset(); // spasm_amd_precond_stats describes the certification run
+        i64 r = 0;
+        int certain = 0;
+        precond_rank_run(Fw, Tr, F, 8, seed, tries, 0, &r, &certain);
+        st[9] = g_precond_stats[4];
+        st[10] += g_precond_stats[5];
+        target = (i64)dim - r;
+    }
+    const size_t db = (size_t)dim * b, bb = (size_t)b * b;
+    std::vector<int> hu(db), hy(db), diag((size_t)nr), hdeg((size_t)b + 1), hcoef, tab;
+    std::vector<long long> hcnt((size_t)2 * b);
+    DevBuf<int> dU, dY, dV, dl, dS, dSt, d_coef, d_small, dW, dR, dT, dZ, dN;
+    DevBuf<long long> dcnt;
+    KrylovWork W;
+    BlockBmWork BW;
+    CeWork CW;
+    SpgEvents ev, evh;
+    dU.alloc(db);
+    dY.alloc(db);
+    dV.alloc(db);
+    dl.alloc((size_t)nr);
+    dS.alloc((size_t)len * bb);
+    dSt.alloc((size_t)len * bb);
+    d_coef.alloc(((size_t)len + 1) * bb);
+    d_small.alloc((size_t)b + 1);
+    dW.alloc(db);
+    dR.alloc((size_t)nr * b);
+    dZ.alloc(std::max(db, (size_t)nr * b));
+    W.mid.ensure((size_t)nr * b); // the intermediate of V = M Y is that of the composite Horner steps
+    dN.alloc((size_t)dim * CE_MAXK);
+    dcnt.alloc((size_t)2 * b);
+    dZ.zero(s);
+    int have = 0;
+    int hpiv[CE_MAXK];
+    bool ech_pending = false;
+    auto echelon_time = [&] { // after a wait on the stream
+        if (ech_pending) st[18] += (i64)(evh.ms(2, 3) * 1000.0);
+        ech_pending = false;
+    };
+    for (int t = 0; t < tries && have < want && have != target; t++) {
+        const uint64_t sd = seed + (uint64_t)t;
+        precond_diagonal(nr, sd, 0, F.p, diag.data());
+        minpoly_vectors(dim, b, sd, F.p, hu.data(), hy.data());
+        HIPCHK(hipMemcpyAsync(dU.p, hu.data(), db * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dY.p, hy.data(), db * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(dl.p, diag.data(), (size_t)nr * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipEventRecord(ev.e[0], s));
+        // V = M Y: fwd with the diagonal, then the plain product by tr (a Horner step with the coefficient 0)
+        int launches = diag_step_run(Fw, F, b, dl.p, dY.p, b, W.mid.p, s);
+        launches += horner_run(Tr, F, b, 1, dZ.p, dZ.p, b, W.mid.p, b, dV.p, b, W, nullptr, s);
+        SeqOperator sq{&Fw, &Tr, dl.p, nullptr};
+        sq.block = true;
+        launches += sequence_run(sq, F, b, len, dU.p, b, dV.p, b, W, dS.p, s);
+        HIPCHK(hipEventRecord(ev.e[1], s));
+        const i64 total = (i64)len * (i64)bb;
+        hipLaunchKernelGGL(k_block_transpose_terms, dim3(cdiv(total, 256)), dim3(256), 0, s, (i64d)total, b, dS.p, dSt.p);
+        HIPCHK(hipGetLastError());
+        launches += 1 + block_bm_device(F, b, len, dSt.p, BW, d_coef.p, d_small.p, d_small.p + b, s);
+        HIPCHK(hipEventRecord(ev.e[2], s));
+        HIPCHK(hipMemcpyAsync(hdeg.data(), d_small.p, hdeg.size() * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        echelon_time();
+        const int D = hdeg[(size_t)b];
+        hcoef.resize(((size_t)D + 1) * bb);
+        HIPCHK(hipMemcpy(hcoef.data(), d_coef.p, hcoef.size() * sizeof(int), hipMemcpyDeviceToHost));
+        st[4] = t + 1;
+        st[6] += (i64)len * 2;
+        st[15] += (i64)(ev.ms(0, 1) * 1000.0);
+        st[16] += (i64)(ev.ms(1, 2) * 1000.0);
+        // slice i of the table is C_{D - i}, C_s[c][j] = F_s[j][c]: column j of W is the relation of row j of the generator
+        tab.assign(((size_t)D + 1) * bb, 0);
+        for (int i = 0; i <= D; i++) {
+            const int *Fs = hcoef.data() + (size_t)(D - i) * bb;
+            for (int c = 0; c < b; c++)
+                for (int j = 0; j < b; j++) tab[((size_t)i * b + c) * b + j] = hbalanced(hresidue(Fs[(size_t)j * b + c], p), p);
+        }
+        dT.ensure(tab.size());
+        HIPCHK(hipMemcpyAsync(dT.p, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(dcnt.p, 0, (size_t)2 * b * sizeof(long long), s));
+        HIPCHK(hipEventRecord(evh.e[0], s));
+        launches += block_horner_run(sq, F, b, b, D + 1, dT.p, dY.p, b, dW.p, b, W, dcnt.p, s);
+        // the certificate: R <- B W with its non-zero counts, against B itself and not against M
+        launches += horner_run(Fw, F, b, 1, dZ.p, dZ.p, b, dW.p, b, dR.p, b, W, dcnt.p + b, s);
+        HIPCHK(hipEventRecord(evh.e[1], s));
+        HIPCHK(hipMemcpyAsync(hcnt.data(), dcnt.p, hcnt.size() * sizeof(long long), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        st[7] += (i64)D * 2;
+        st[8] += 1;
+        st[11] += b;
+        st[17] += (i64)(evh.ms(0, 1) * 1000.0);
+        CeSelect sel;
+        memset(&sel, 0, sizeof sel);
+        int take = 0;
+        for (int j = 0; j < b && have + take < want; j++)
+            if (hcnt[(size_t)b + j] == 0 && hcnt[(size_t)j] != 0) sel.c[take++] = j;
+        if (take > 0) {
+            HIPCHK(hipEventRecord(evh.e[2], s));
+            hipLaunchKernelGGL(k_ce_gather_columns, step_grid((i64)dim * take, step_grid_cap()), dim3(CE_BS), 0, s, (i64d)dim, take, sel, dW.p, (i64d)b, dN.p,
+                               (i64d)CE_MAXK, have);
+            HIPCHK(hipGetLastError());
+            int el = 1;
+            const int rank = column_echelon_dev(dim, have + take, dN.p, CE_MAXK, F, CW, hpiv, &el, s);
+            HIPCHK(hipEventRecord(evh.e[3], s));
+            ech_pending = true; // its time is read at the next wait on the stream: the rank is here already
+            launches += el;
+            st[12] += take;
+            st[13] += have + take - rank;
+            have = rank;
+        }
+        st[10] += launches;
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    echelon_time();
+    st[5] = st[6] + st[7] + st[8] + st[9];
+    st[14] = have;
+    if (have > 0) {
+        std::vector<int> out((size_t)dim * have);
+        HIPCHK(hipMemcpy2D(out.data(), (size_t)have * sizeof(int), dN.p, (size_t)CE_MAXK * sizeof(int), (size_t)have * sizeof(int), (size_t)dim,
+                           hipMemcpyDeviceToHost));
+        for (int r = 0; r < dim; r++) memcpy(N + (i64)r * ldn, out.data() + (size_t)r * have, (size_t)have * sizeof(int));
+        memcpy(pivots, hpiv, (size_t)have * sizeof(int));
+    }
+    *found = have;
+    *complete = certify && have == target;
+}
+
+int wker_entry(Operand &&o, int trans, int b, int want, uint64_t seed, int tries, int certify, spasm_ZZp *N, i64 ldn, int *found, int *pivots, int *complete)
+{
+    wker_stats_reset();
+    o.check();
+    const int nr = trans ? o.m : o.n, dim = trans ? o.n : o.m;
+    wker_check(trans, b, want, tries, N, ldn, found, pivots, complete, dim);
+    i64 *st = g_wker_stats;
+    st[0] = o.n;
+    st[1] = o.m;
+    st[2] = b;
+    st[3] = want;
+    if (dim == 0) {
+        *found = 0;
+        *complete = 1;
+        return 0;
+    }
+    if (nr == 0) { // no equation: the unit vectors, as many as are wanted
+        const int have = std::min(want, dim);
+        for (int r = 0; r < dim && have > 0; r++)
+            for (int c = 0; c < have; c++) N[(i64)r * ldn + c] = r == c;
+        for (int c = 0; c < have; c++) pivots[c] = c;
+        *found = have;
+        *complete = certify && have == dim;
+        st[14] = have;
+        return 0;
+    }
+    if (o.n >= (1 << 24) || o.m >= (1 << 24)) throw EngineError("Wiedemann kernel limited to dim < 2^24");
+    block_bm_check_len(block_terms(dim, b));
+    o.views(true, true);
+    wker_run(trans ? *o.tr : *o.fwd, trans ? *o.fwd : *o.tr, o.F, b, want, seed, tries, certify, N, ldn, found, pivots, complete);
+    return 0;
+}
+
+} // namespace
+
+extern "C" {
+
+// ---- kernel bases without fill-in (colechelon.hpp; engine extension) ----
+SPASM_API int spasm_amd_dense_column_echelon(i64 rows, int K, spasm_ZZp *X, i64 ldx, i64 prime, int *rank, int *pivots)
+{
+    return abi_call("spasm_amd_dense_column_echelon", -1, [&] {
+        wker_stats_reset();
+        dense_column_echelon(rows, K, X, ldx, prime, rank, pivots);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_block_precond_sequence(spasm_amd_spmv *op, int trans, int b, int len, const spasm_ZZp *d_left, const spasm_ZZp *d_right,
+                                               const spasm_ZZp *U, i64 ldu, const spasm_ZZp *V, i64 ldv, spasm_ZZp *S)
+{
+    return abi_call("spasm_amd_block_precond_sequence", -1, [&] {
+        wker_stats_reset();
+        block_precond_sequence(op, trans, b, len, d_left, d_right, U, ldu, V, ldv, S);
+        return 0;
+    });
+}
+
+SPASM_API int spasm_amd_wiedemann_kernel(const struct spasm_csr *A, int trans, int b, int want, uint64_t seed, int tries, int certify, spasm_ZZp *N, i64 ldn,
+                                         int *found, int *pivots, int *complete)
+{
+    return abi_call("spasm_amd_wiedemann_kernel", -1, [&] {
+        return wker_entry(Operand(A, "spasm_amd_wiedemann_kernel"), trans, b, want, seed, tries, certify, N, ldn, found, pivots, complete);
+    });
+}
+
+SPASM_API int spasm_amd_spmv_wiedemann_kernel(spasm_amd_spmv *op, int trans, int b, int want, uint64_t seed, int tries, int certify, spasm_ZZp *N, i64 ldn,
+                                              int *found, int *pivots, int *complete)
+{
+    return abi_call("spasm_amd_spmv_wiedemann_kernel", -1,
+                    [&] { return wker_entry(Operand(op), trans, b, want, seed, tries, certify, N, ldn, found, pivots, complete); });
+}
+
+SPASM_API int spasm_amd_dcsr_wiedemann_kernel(const spasm_amd_dcsr *D, int trans, int b, int want, uint64_t seed, int tries, int certify, spasm_ZZp *N,
+                                              i64 ldn, int *found, int *pivots, int *complete)
+{
+    return abi_call("spasm_amd_dcsr_wiedemann_kernel", -1,
+                    [&] { return wker_entry(Operand(D), trans, b, want, seed, tries, certify, N, ldn, found, pivots, complete); });
+}
+
+SPASM_API void spasm_amd_wiedemann_kernel_stats(i64 *out)
+{
+    if (out) memcpy(out, g_wker_stats, sizeof g_wker_stats);
 }
 
 } // extern "C"
